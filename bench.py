@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- LM iterations/sec on the BASELINE.json headline workload (the configurations live in benchlib/).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1 from a bare shell: this process starts the N rank processes itself (benchlib/launcher.py: children of this
   interpreter with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set; the parent never imports torch or touches HIP) and
   relays rank 0's JSON line. Under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
@@ -25,6 +25,12 @@ A "step" is one complete LM solve (mir_optimize_least_squares_gpu_d from x0 to t
 callbacks, Broyden updates, J^T J / J^T y, damped BOXCQP solves, step acceptance -- nothing is skipped or cached between
 solves. Inputs are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the K steps and prints the line. --full also runs the legs the headline does not
+need (survey_setting, host_callback_mode, cpu_baseline, cpu_baseline_1thread; with --config cfg5 the steady-state
+launch, with cfg2 / cfg5 their cpu_baseline); the --no-* / --survey-steps / --cfg5-replicas options trim them there.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (x and the fields of the result; cfg5: per
+problem), float64 or float32. The inputs are the same from run to run, so two builds compare output for output.
+
 The JSON line also carries
   roofline        the kernel with the most time in the timed region -- caller-side kernels included (at cfg 3 it is the
                   caller's finite-difference GEMM) --, HIP-event timed on the solver's stream; `object` names the entry
@@ -34,8 +40,9 @@ The JSON line also carries
                   + workloads_gemm.hip), event-timed on the same stream: they are most of a solve and get their own
                   roofline objects
   solve_kernel    the one-workgroup n x n kernel (latency-bound; time only)
-  cpu_baseline    the oracle (CPU port of the reference algorithm, OpenBLAS for syrk/gemv/ger/posvx) on a bounded sample
-                  of the same workload at min(nproc, 64) threads, plus cpu_baseline_1thread; rank 0, N = 1 only.
+  cpu_baseline    (--full) the oracle (CPU port of the reference algorithm, OpenBLAS for syrk/gemv/ger/posvx) on a
+                  bounded sample of the same workload at OMP_NUM_THREADS (default min(nproc, 64)) threads, plus
+                  cpu_baseline_1thread; rank 0, N = 1 only.
 """
 import argparse
 import os
@@ -81,7 +88,7 @@ def parse():
     ap.add_argument("--abs-tolerance", type=float, default=1e-5,
                     help="LeastSquaresSettings.absTolerance of the headline number (DESIGN.md section 5)")
     ap.add_argument("--survey-steps", type=int, default=10,
-                    help="solves timed at SURVEY 8d's absTolerance = 1e-9 after the main region (0 = skip)")
+                    help="--full: solves timed at SURVEY 8d's absTolerance = 1e-9 after the main region (0 = skip)")
     ap.add_argument("--control-plane", choices=["gloo", "nccl"], default="gloo",
                     help="torch.distributed backend for barriers / id exchange (the solve's collectives always use the "
                          "solver's own RCCL communicator)")
@@ -120,7 +127,7 @@ def parse():
                          "few microseconds on the stream: ~0.2 ms per cfg-3 solve when every step is instrumented)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cfg5-replicas", type=int, default=16,
-                    help="--config cfg5: also time ONE launch of this many copies of the 4096 problems (the "
+                    help="--config cfg5 --full: also time ONE launch of this many copies of the 4096 problems (the "
                          "steady-state rate of the kernel, "
                          "where the tail of long fits is amortised); 1 = skip")
     ap.add_argument("--no-host-callback", action="store_true",
@@ -129,7 +136,19 @@ def parse():
                          "one untimed + one timed solve, a few seconds of host work")
     ap.add_argument("--no-cpu-1thread", action="store_true")
     ap.add_argument("--cpu-iterations", type=int, default=6, help="accepted iterations of the CPU sample")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline does not need: the survey setting, the host-callback leg, the "
+                         "CPU baselines, cfg5's steady-state launch (without it: --survey-steps 0 --no-host-callback "
+                         "--no-cpu-baseline --cfg5-replicas 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if not args.full:
+        args.survey_steps = 0
+        args.no_host_callback = True
+        args.no_cpu_baseline = True
+        args.cfg5_replicas = 1
+    return args
 
 
 def main():

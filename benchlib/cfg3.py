@@ -6,9 +6,10 @@ import os
 import sys
 import time
 
-from .common import (F64_MFMA_PEAK_TF, HBM_PEAK_GBS, ROOT, _round_no, csrc_sha16, describe_comm, flush_c_stdio,
+from .common import (F64_MFMA_PEAK_TF, HBM_PEAK_GBS, ROOT, _round_no, csrc_sha16, describe_comm, dump_outputs,
+                     flush_c_stdio,
                      # noqa: F401
-                     pmc_field, pmc_file, step_stats, traffic_source)
+                     pmc_field, pmc_file, result_arrays, step_stats, traffic_source)
 
 
 def main_cfg3(args):
@@ -222,6 +223,8 @@ def main_cfg3(args):
 
     st, iters, dt, res, x = timed(args.steps, settings)
     main_steps = timed.last_steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result_arrays(res, x))
     sta = st["all"]
     timed_steps = len(range(0, args.steps, max(1, args.timing_every))) if not args.no_kernel_timing else 0
     if res.status < 0:
@@ -471,7 +474,7 @@ def main_cfg3(args):
                 out["host_callback_mode"] = {"error": repr(e)}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(data, m, n, args.cpu_iterations, args.abs_tolerance,
-                                               min(os.cpu_count() or 1, 64), x, res)
+                                               cpu_baseline_threads(), x, res)
             if not args.no_cpu_1thread:
                 out["cpu_baseline_1thread"] = cpu_baseline(data, m, n, 1, args.abs_tolerance, 1)
     if comm_obj is not None:
@@ -494,13 +497,21 @@ def main_cfg3(args):
 
 
 
+def cpu_baseline_threads():
+    """min(nproc, 64), or fewer where OMP_NUM_THREADS says the process may use fewer (a host that shares its cores)."""
+    cap = min(os.cpu_count() or 1, 64)
+    try:
+        return max(1, min(cap, int(os.environ.get("OMP_NUM_THREADS", cap))))
+    except ValueError:
+        return cap
+
+
 def cpu_baseline(data, m, n, iterations, abs_tolerance, threads, x_gpu=None, res_gpu=None):
     """The oracle (port of the reference algorithm; OpenBLAS from scipy for syrk/gemv/ger/posvx -- the library class the
     reference links) on the same inputs, bounded to `iterations` accepted steps, on `threads` host threads."""
     from oracle import oracle as O
     ob = O.load_openblas(threads=threads)
-    if ob:
-        O.lib().lmo_openblas_set_threads(int(threads))
+    ob_threads = O.lib().lmo_openblas_set_threads(int(threads)) if ob else 0     # at most OpenBLAS's own pool
     omp_set = getattr(O.lib(), "lmo_set_omp_threads", None)
     if omp_set is not None:
         omp_set(int(threads))
@@ -526,5 +537,6 @@ def cpu_baseline(data, m, n, iterations, abs_tolerance, threads, x_gpu=None, res
             "sample": f"the first {ro.iterations} accepted LM iteration(s) of the same m={m} x n={n} solve (bounded by "
                       f"maxIterations={iterations}; status {O.STATUS.get(ro.status, ro.status)}, "
                       f"fCalls {ro.fCalls}: FD Jacobians of {2 * n} residual calls each + Broyden passes), {dt:.1f} s, "
-                      f"OpenBLAS={'yes' if ob else 'no (plain loops)'} x{threads}, residual calls OpenMP x{threads}",
+                      f"OpenBLAS={'yes' if ob else 'no (plain loops)'} x{ob_threads if ob else threads}, "
+                      f"residual calls OpenMP x{threads}",
             "seconds": dt, "fcalls": ro.fCalls}

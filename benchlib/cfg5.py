@@ -5,7 +5,8 @@ import os
 import sys
 import time
 
-from .common import (F64_MFMA_PEAK_TF, HBM_PEAK_GBS, ROOT, _round_no, csrc_sha16, describe_comm, flush_c_stdio,
+from .common import (F64_MFMA_PEAK_TF, HBM_PEAK_GBS, ROOT, _round_no, csrc_sha16, describe_comm, dump_outputs,
+                     flush_c_stdio,
                      # noqa: F401
                      pmc_field, pmc_file, step_stats, traffic_source)
 
@@ -60,6 +61,11 @@ def main_cfg5(args):
     rec_dtype = np.dtype([("status", "<i4"), ("iterations", "<u4"), ("fCalls", "<u4"), ("gCalls", "<u4"),
                           ("residual", "<f4"), ("lambda", "<f4")])
     raw = np.frombuffer(dres.download().tobytes(), dtype=rec_dtype)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": dx.download().reshape(count, n), "status": raw["status"],
+                                         "iterations": raw["iterations"], "fcalls": raw["fCalls"],
+                                         "gcalls": raw["gCalls"], "residual": raw["residual"],
+                                         "lambda": raw["lambda"]})
     iters = int(raw["iterations"].sum())
     fcalls = int(raw["fCalls"].sum())
     ms = dt / args.steps * 1e3

@@ -83,3 +83,28 @@ def describe_comm(api, comm):
 def step_stats(ms):
     import statistics
     return [min(ms), statistics.median(ms), max(ms)] if ms else None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per array. Arrays in
+    float32 stay float32, everything else (counters, status codes) is written as float64; 64 MB at most in all."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
+def result_arrays(res, x):
+    """The arrays a caller of the solver receives: x and the fields of its LeastSquaresResult."""
+    return {"x": x, "status": [int(res.status)], "iterations": [res.iterations], "fcalls": [res.fCalls],
+            "gcalls": [res.gCalls], "residual": [res.residual], "lambda": [res.lambda_]}

@@ -26,6 +26,7 @@ typedef void (*ob_dposvx_t)(char* fact, char* uplo, int* n, int* nrhs, double* a
                             double* rcond, double* ferr, double* berr, double* work, int* iwork, int* info,
                             size_t, size_t, size_t);
 typedef void (*ob_set_threads_t)(int);
+typedef int (*ob_get_threads_t)(void);
 
 static struct {
     void* handle;
@@ -34,6 +35,7 @@ static struct {
     ob_dsyrk_t dsyrk;
     ob_dposvx_t dposvx;
     ob_set_threads_t set_threads;
+    int pool;               /* threads of OpenBLAS's pool when it was loaded (0: unknown) */
 } g_ob;
 
 int lmo_openblas_load(const char* path)
@@ -46,6 +48,8 @@ int lmo_openblas_load(const char* path)
     g_ob.dsyrk = (ob_dsyrk_t)dlsym(h, "scipy_cblas_dsyrk");
     g_ob.dposvx = (ob_dposvx_t)dlsym(h, "scipy_dposvx_");
     g_ob.set_threads = (ob_set_threads_t)dlsym(h, "scipy_openblas_set_num_threads");
+    ob_get_threads_t get_threads = (ob_get_threads_t)dlsym(h, "scipy_openblas_get_num_threads");
+    g_ob.pool = get_threads ? get_threads() : 0;
     if (!g_ob.dgemv || !g_ob.dger || !g_ob.dsyrk || !g_ob.dposvx) {
         memset(&g_ob, 0, sizeof g_ob);
         dlclose(h);
@@ -63,11 +67,15 @@ void lmo_set_omp_threads(int nthreads) { if (nthreads > 0) omp_set_num_threads(n
 void lmo_set_omp_threads(int nthreads) { (void)nthreads; }
 #endif
 
+/* OpenBLAS sizes its pool at load time (by the processors it may run on and OPENBLAS_NUM_THREADS / OMP_NUM_THREADS);
+ * growing it past that size afterwards makes later calls crash (seen with 0.3.28 at m = 1e6, n = 128), so the request
+ * is clamped to the pool. Returns the thread count set, or -1. */
 int lmo_openblas_set_threads(int nthreads)
 {
-    if (!g_ob.handle || !g_ob.set_threads) return -1;
+    if (!g_ob.handle || !g_ob.set_threads || nthreads < 1) return -1;
+    if (g_ob.pool > 0 && nthreads > g_ob.pool) nthreads = g_ob.pool;
     g_ob.set_threads(nthreads);
-    return 0;
+    return nthreads;
 }
 
 /* ---- workspace sizes and strings ---- */

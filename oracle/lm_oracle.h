@@ -164,7 +164,8 @@ int lmo_optimize_batched_fused_pad8_s(const lmo_settings_s* S, int m, const floa
 void lmo_apply_bounds_d(size_t n, double* x, const double* l, const double* u);
 void lmo_apply_bounds_s(size_t n, float* x, const float* l, const float* u);
 
-/* OpenBLAS (scipy.libs) backend control for the cpu_baseline leg. Returns 0 on success. */
+/* OpenBLAS (scipy.libs) backend control for the cpu_baseline leg. lmo_openblas_load returns 0 on success;
+ * lmo_openblas_set_threads the thread count it set (at most the pool OpenBLAS started with), or -1. */
 int lmo_openblas_load(const char* path);
 int lmo_openblas_set_threads(int nthreads);
 void lmo_set_omp_threads(int nthreads);

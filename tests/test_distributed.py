@@ -138,7 +138,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     env = dict(os.environ, BENCH_M="200000", BENCH_N="64", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--comm", "gloo-callback", "--survey-steps", "1"]
+           "--comm", "gloo-callback", "--full", "--survey-steps", "1"]
     p = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]

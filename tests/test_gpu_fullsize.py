@@ -35,8 +35,12 @@ class OracleResult:
 
 
 def oracle_run(tmp_path, abs_tolerance, max_iterations, m=M_ROWS, n=N):
-    """The oracle in a process of its own (tests/oracle_fullsize_worker.py), same inputs (counter RNG)."""
-    threads = min(os.cpu_count() or 1, 32)
+    """The oracle in a process of its own (tests/oracle_fullsize_worker.py), same inputs (counter RNG), on the threads
+    OMP_NUM_THREADS allows (tests/conftest.py: 16 unless set), at most 32."""
+    try:
+        threads = min(int(os.environ.get("OMP_NUM_THREADS") or os.cpu_count() or 1), os.cpu_count() or 1, 32)
+    except ValueError:
+        threads = min(os.cpu_count() or 1, 32)
     out = str(tmp_path / "oracle.npz")
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "oracle_fullsize_worker.py")
     p = subprocess.run([sys.executable, worker, str(m), str(n), repr(abs_tolerance), str(max_iterations), str(threads), out],
