@@ -381,7 +381,8 @@ typedef struct mir_lsq_batched_options {
     uint32_t variant;         /* MIR_LSQ_BATCHED_* bits; 0 = default */
     void* stream;             /* mir_lsq_batched_kernel_s: hipStream_t to enqueue on (NULL = the default stream) */
     float* basis;             /* optional DEVICE buffer for the model's per-row basis table (models with a basis only:
-                                 (t_stride ? count : 1) x m x nb floats, 16-byte aligned), owned by the caller and filled by
+                                 (t_stride ? count : 1) x m x nb floats, 16-byte aligned -- DOUBLES for the _d entries and
+                                 any double model: the C type stays float*, basis_bytes counts bytes), owned by the caller and filled by
                                  every call. NULL: the call allocates the table (hipMalloc) and synchronises the stream before
                                  freeing it -- the ONLY case in which mir_lsq_batched_kernel_s synchronises; pass a table to
                                  stay asynchronous (bench.py does) */
@@ -408,6 +409,21 @@ int mir_lsq_batched_kernel_s(const mir_least_squares_settings_s* settings, size_
                              float* x, const float* lower, const float* upper,
                              const float* t, size_t t_stride, const float* data,
                              mir_least_squares_result_s* results, const mir_lsq_batched_options* options);
+
+/* The same two entries in DOUBLE (LeastSquaresSettings!double, the reference's main instantiation): the same models (ids and
+ * formulas, evaluated in double), contract and return codes as their _s twins; every array is double, the records are the _d
+ * ones (32 bytes, written in place by the kernel entry), and a basis table passed in the options holds doubles. A problem
+ * needs (n + 2) m doubles of LDS: m <= 2041 at n = 8, 4083 at n = 3. Problems whose step reaches a finite bound are completed
+ * by mir_optimize_least_squares_gpu_d in the host entry, and come back with status -100 from the kernel entry. The kernel entry
+ * checks its arguments (-1) before it looks for a device. */
+int mir_optimize_least_squares_batched_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                                         double* x, const double* lower, const double* upper,
+                                         const double* t, size_t t_stride, const double* data,
+                                         mir_least_squares_result_d* results, const mir_lsq_batched_options* options);
+int mir_lsq_batched_kernel_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                             double* x, const double* lower, const double* upper,
+                             const double* t, size_t t_stride, const double* data,
+                             mir_least_squares_result_d* results, const mir_lsq_batched_options* options);
 
 /* Resident-J solver (include/mir_optim_amd_resident.hpp, launch_resident<Model>): the whole loop of least_squares.d:972-1175
  * in ONE cooperative launch for problems whose Jacobian, residuals and per-row data fit the LDS of the chip (BASELINE
@@ -457,6 +473,8 @@ typedef struct mir_lsq_resident_options {
  * >= n ignored / zero); info[p] = 0 or the order of the leading minor that is not positive (x of that system is zero).
  * Enqueued on `stream`, no synchronisation. */
 int mir_lsq_batched_posvx_s(size_t count, size_t n, const float* P, const float* rhs, float* x, int* info, void* stream);
+/* the same in double: P count x 64 doubles, rhs and x count x 8 doubles */
+int mir_lsq_batched_posvx_d(size_t count, size_t n, const double* P, const double* rhs, double* x, int* info, void* stream);
 
 /* Unit-level access to the hot kernels (parity tests and micro-benchmarks). All pointers are
  * DEVICE pointers; stream may be NULL (default stream; the call synchronises before returning).
@@ -546,7 +564,8 @@ int mir_lsq_stream_synchronize(void* stream);
 /* "mir_optim_amd <major.minor> (gfx950)". 0.2: the last argument of mir_lsq_batched_kernel_s became the options struct (it was a
  * hipStream_t in 0.1 -- same arity, so an old caller still links: both batched entries answer -1 to an options pointer whose
  * first word is not a plausible struct_size) and mir_optimize_least_squares_batched_s gained it; 0.3: the resident-J options /
- * statistics of part 2 and mir_optim_amd_resident.hpp. Callers that cache function pointers across versions check this. */
+ * statistics of part 2 and mir_optim_amd_resident.hpp; 0.4: the batched entries in double (mir_optimize_least_squares_batched_d,
+ * mir_lsq_batched_kernel_d, mir_lsq_batched_posvx_d) and double models in launch_batched<Model>. Callers that cache function pointers across versions check this. */
 const char* mir_lsq_version(void);
 
 /* =====================================================================================================

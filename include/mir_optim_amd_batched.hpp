@@ -18,8 +18,12 @@
 //     };
 // Optional, the reference's g callback: `__device__ static void grad(float t, const float* b, const float* x, float* g)` -- g[j] =
 // d eval / d x_j, j < n -- used instead of finite differences when options->variant has MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN.
+// Optional, the precision: `using value_type = double;` makes the whole fit double (LeastSquaresSettings!double, the reference's
+// main instantiation) -- basis, eval and grad then take and return double, and launch_batched takes the _d settings and result
+// records and double arrays, as mir_lsq_batched_kernel_d does. Without the member the model is float, as before.
 // The residual of row i is eval(t_i, basis_i, x) - data_i. eval must be pure (as the reference's callbacks are declared)
-// and free of lane-dependent control flow. A problem needs (n + 2) m floats of LDS ((n + 2) m * 4 <= 160 KB - 512).
+// and free of lane-dependent control flow. A problem needs (n + 2) m values of LDS ((n + 2) m sizeof(T) <= 160 KB - 512: a
+// double model at n = 8 reaches m = 2041).
 // Reproducibility: the kernel's own arithmetic is a fixed sequence of IEEE operations (contraction off, every fused multiply-add
 // written out: batched_kernel.h), so a fit is reproducible bit for bit on a host (oracle/lm_batched_fused.c does it for the
 // built-in cfg 5 model) -- PROVIDED eval is written the same way: `#pragma clang fp contract(off)` as its first statement, explicit
@@ -27,7 +31,7 @@
 // An eval written as in the example above is still deterministic on the device; only a host twin would differ in the last bit.
 //
 //     mir_optim_amd::launch_batched<MyModel>(&settings, count, m, x, lower, upper, t, t_stride, data, results, &options);
-// has the contract of mir_lsq_batched_kernel_s (include/mir_optim_amd.h): every pointer a DEVICE pointer, enqueued on
+// has the contract of mir_lsq_batched_kernel_s / _d (include/mir_optim_amd.h): every pointer a DEVICE pointer, enqueued on
 // options->stream, results in place, status -100 (MIR_LSQ_BATCHED_NEEDS_GENERAL) for a problem whose step reaches a finite
 // bound. tests/user_model/ holds a complete example that is compiled and compared with the float oracle.
 #pragma once
@@ -35,16 +39,28 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
+#include <type_traits>
 
 #include "mir_optim_amd.h"
 #include "../mir_optim_amd/csrc/batched_kernel.h"
 
 namespace mir_optim_amd {
 
+// the value type of a model (float unless it declares `using value_type = double;`) and the C records that go with it
+template <class Model> using batched_value_t = mirlsq::batched_value_t<Model>;
+template <class Model>
+using batched_settings_t = std::conditional_t<std::is_same<batched_value_t<Model>, double>::value, mir_least_squares_settings_d,
+                                              mir_least_squares_settings_s>;
+template <class Model>
+using batched_result_t = std::conditional_t<std::is_same<batched_value_t<Model>, double>::value, mir_least_squares_result_d,
+                                            mir_least_squares_result_s>;
+
 // LDS bytes one problem of `Model` needs at m rows; launch_batched returns -3 when it exceeds kBatchedLdsLimit
 constexpr size_t kBatchedLdsLimit = 160 * 1024 - 512;
-template <class Model> constexpr size_t batched_lds_bytes(size_t m) { return (size_t)(Model::n + 2) * m * sizeof(float); }
-// floats of the per-row basis table a launch needs (0 for a model without a basis): mir_lsq_batched_options.basis
+template <class Model> constexpr size_t batched_lds_bytes(size_t m) { return (size_t)(Model::n + 2) * m * sizeof(batched_value_t<Model>); }
+// values (of the model's type: floats, or doubles for a double model) of the per-row basis table a launch needs (0 for a model
+// without a basis): mir_lsq_batched_options.basis, whose basis_bytes is this times sizeof(batched_value_t<Model>)
 template <class Model> constexpr size_t batched_basis_floats(size_t count, size_t m, size_t t_stride)
 {
     return (size_t)Model::nb * (t_stride ? count : 1) * m;
@@ -52,22 +68,28 @@ template <class Model> constexpr size_t batched_basis_floats(size_t count, size_
 
 // Returns 0, or: -1 bad arguments, -3 a problem does not fit its workgroup's LDS, -4 allocation of the basis table failed,
 // -5 the launch failed. Does not synchronise (except in the documented hipMalloc fallback of the basis table).
+// A float model takes the _s records and float arrays, a double model the _d records and double arrays.
 template <class Model>
-int launch_batched(const mir_least_squares_settings_s* S, size_t count, size_t m, float* x, const float* lower, const float* upper,
-                   const float* t, size_t t_stride, const float* data, mir_least_squares_result_s* results,
+int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
+                   const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
+                   size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
                    const mir_lsq_batched_options* opt = nullptr)
 {
     using namespace mirlsq;
+    using T = batched_value_t<Model>;
+    static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "Model::value_type: float or double");
     static_assert(Model::n >= 1 && Model::n <= kBatchedNMax, "1 <= n <= 8: one matrix row per lane of a group of eight");
     static_assert(Model::nb >= 0, "nb: number of per-row basis values");
     if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
-    static_assert(sizeof(BatchedResult) == sizeof(mir_least_squares_result_s), "the kernel writes the C result records in place");
+    static_assert(sizeof(BatchedResult<T>) == sizeof(batched_result_t<Model>), "the kernel writes the C result records in place");
+    static_assert(offsetof(BatchedResult<T>, residual) == offsetof(batched_result_t<Model>, residual)
+                  && offsetof(BatchedResult<T>, lambda) == offsetof(batched_result_t<Model>, lambda), "same layout as the C record");
     if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
     if (count == 0) return 0;
     const size_t lds = batched_lds_bytes<Model>(m);
     if (m == 0 || lds > kBatchedLdsLimit) return -3;
     hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
-    BatchedArgs a{};
+    BatchedArgs<T> a{};
     a.set.jacobianEpsilon = S->jacobianEpsilon; a.set.absTolerance = S->absTolerance; a.set.relTolerance = S->relTolerance;
     a.set.gradTolerance = S->gradTolerance; a.set.maxGoodResidual = S->maxGoodResidual; a.set.maxStep = S->maxStep;
     a.set.maxLambda = S->maxLambda; a.set.minLambda = S->minLambda; a.set.minStepQuality = S->minStepQuality;
@@ -79,18 +101,18 @@ int launch_batched(const mir_least_squares_settings_s* S, size_t count, size_t m
     a.variant = opt ? opt->variant : 0;
     a.timing = opt ? opt->timing : nullptr;
     a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
-    a.results = reinterpret_cast<BatchedResult*>(results);
+    a.results = reinterpret_cast<BatchedResult<T>*>(results);
     auto kern = k_lm_batched<Model>;
     if (lds > 48 * 1024
         && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return -5;
-    float* table = nullptr;
+    T* table = nullptr;
     bool owned = false;
     if constexpr (Model::nb > 0) {
-        const size_t rows = (size_t)(t_stride ? count : 1) * m, bytes = rows * Model::nb * sizeof(float);
+        const size_t rows = (size_t)(t_stride ? count : 1) * m, bytes = rows * Model::nb * sizeof(T);
         if (opt && opt->basis) {
             if (opt->basis_bytes < bytes) return -1;
-            table = opt->basis;                                // the caller's table: no allocation in this call
+            table = reinterpret_cast<T*>(opt->basis);          // the caller's table (doubles for a double model): no allocation here
         } else {
             // No table from the caller: hipMalloc, and a stream synchronisation before hipFree below. (Until round 4 this was
             // hipMallocAsync / hipFreeAsync, and 2 of 300 calls with a 2 MB table returned wrong fits for a contiguous range of
@@ -120,9 +142,11 @@ int launch_batched(const mir_least_squares_settings_s* S, size_t count, size_t m
 }
 
 // the residual vector of ONE problem, y_i = eval(t_i, basis_i, x) - data_i, as a kernel launch on device pointers: what a
-// caller hands to the general solver as its device callback when a batched problem comes back with status -100
+// caller hands to the general solver as its device callback when a batched problem comes back with status -100 (float or
+// double, as the model is: mir_optimize_least_squares_gpu_s / _d)
 template <class Model>
-void launch_model_residual(const float* t, const float* data, const float* x, float* y, size_t m, hipStream_t stream)
+void launch_model_residual(const batched_value_t<Model>* t, const batched_value_t<Model>* data, const batched_value_t<Model>* x,
+                           batched_value_t<Model>* y, size_t m, hipStream_t stream)
 {
     hipLaunchKernelGGL(mirlsq::k_batched_model_eval<Model>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, t, data, x, y, (int)m);
 }

@@ -288,6 +288,14 @@ def lib():
         L.mir_lsq_selftest_reductions.argtypes = [C.c_int, C.POINTER(C.c_int * 4)]
         L.mir_lsq_batched_posvx_s.restype = C.c_int
         L.mir_lsq_batched_posvx_s.argtypes = [sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mir_optimize_least_squares_batched_d.restype = C.c_int
+        L.mir_optimize_least_squares_batched_d.argtypes = [C.POINTER(_Sd), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, sz, C.c_void_p, C.c_void_p, C.POINTER(BatchedOptions)]
+        L.mir_lsq_batched_kernel_d.restype = C.c_int
+        L.mir_lsq_batched_kernel_d.argtypes = [C.POINTER(_Sd), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, sz, C.c_void_p, C.c_void_p, C.POINTER(BatchedOptions)]
+        L.mir_lsq_batched_posvx_d.restype = C.c_int
+        L.mir_lsq_batched_posvx_d.argtypes = [sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mir_lsq_comm_describe.restype = C.c_int
         L.mir_lsq_comm_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         L.mir_lsq_workspace_create.restype = C.c_void_p
@@ -584,48 +592,62 @@ def optimize(f, m, x, l=None, u=None, g=None, tm=None, settings=None, dtype=np.f
     return res, xo
 
 
-def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None, variant=0):
-    """Many independent small fits, one wavefront per problem (mir_optimize_least_squares_batched_s, fp32).
-    x: count x n starts (a copy is updated and returned), t: m (shared) or count x m, data: count x m.
-    variant: BATCHED_* bits (per call). Returns (list of LeastSquaresResult, x)."""
+def _batched_suffix(dtype):
+    """'s' for float32 (the default of the batched entries), 'd' for float64"""
+    if np.dtype(dtype) == np.float32:
+        return "s"
+    if np.dtype(dtype) == np.float64:
+        return "d"
+    raise ValueError(f"the batched entries exist in float32 and float64, not {np.dtype(dtype)}")
+
+
+def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None, variant=0, dtype=np.float32):
+    """Many independent small fits, one wavefront per problem (mir_optimize_least_squares_batched_s, fp32, or with
+    dtype=np.float64 mir_optimize_least_squares_batched_d). x: count x n starts (a copy is updated and returned), t: m
+    (shared) or count x m, data: count x m. variant: BATCHED_* bits (per call). Returns (list of LeastSquaresResult, x)."""
+    suf = _batched_suffix(dtype)
+    dtype = np.float32 if suf == "s" else np.float64
     L = lib()
-    x = np.array(x, dtype=np.float32, order="C")
+    x = np.array(x, dtype=dtype, order="C")
     count, n = x.shape
-    data = np.ascontiguousarray(data, dtype=np.float32)
+    data = np.ascontiguousarray(data, dtype=dtype)
     m = data.shape[1]
-    t = np.ascontiguousarray(t, dtype=np.float32)
+    t = np.ascontiguousarray(t, dtype=dtype)
     t_stride = 0 if t.ndim == 1 else m
-    lo = np.full(n, -np.inf, dtype=np.float32) if l is None else np.ascontiguousarray(l, dtype=np.float32)
-    up = np.full(n, np.inf, dtype=np.float32) if u is None else np.ascontiguousarray(u, dtype=np.float32)
+    lo = np.full(n, -np.inf, dtype=dtype) if l is None else np.ascontiguousarray(l, dtype=dtype)
+    up = np.full(n, np.inf, dtype=dtype) if u is None else np.ascontiguousarray(u, dtype=dtype)
     if settings is None:
-        settings = LeastSquaresSettings(np.float32)
-    raw = (_Rs * count)()
-    rc = L.mir_optimize_least_squares_batched_s(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data,
-                                                up.ctypes.data, t.ctypes.data, t_stride, data.ctypes.data, raw,
-                                                C.byref(BatchedOptions(variant=variant)))
+        settings = LeastSquaresSettings(dtype)
+    raw = ((_Rs if suf == "s" else _Rd) * count)()
+    fn = getattr(L, "mir_optimize_least_squares_batched_" + suf)
+    rc = fn(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data, up.ctypes.data, t.ctypes.data, t_stride,
+            data.ctypes.data, raw, C.byref(BatchedOptions(variant=variant)))
     if rc != 0:
-        raise RuntimeError(f"mir_optimize_least_squares_batched_s failed: {rc}")
+        raise RuntimeError(f"mir_optimize_least_squares_batched_{suf} failed: {rc}")
     return [LeastSquaresResult(r) for r in raw], x
 
 
 BATCHED_NO_LADDER = 1
 
 
-def batchedPosvx(P, rhs):
-    """The damped solve of the wave-per-problem kernel on its own (mir_lsq_batched_posvx_s): P count x n x n (lower
-    triangles read), rhs count x n, n in (3, 8), fp32. Returns (x count x n, info count)."""
+def batchedPosvx(P, rhs, dtype=np.float32):
+    """The damped solve of the wave-per-problem kernel on its own (mir_lsq_batched_posvx_s, or with dtype=np.float64
+    mir_lsq_batched_posvx_d): P count x n x n (lower triangles read), rhs count x n, n in (3, 8). Returns (x count x n,
+    info count)."""
+    suf = _batched_suffix(dtype)
+    dtype = np.float32 if suf == "s" else np.float64
     L = lib()
-    P = np.asarray(P, dtype=np.float32)
+    P = np.asarray(P, dtype=dtype)
     count, n = P.shape[0], P.shape[1]
-    Pp = np.zeros((count, 8, 8), dtype=np.float32); Pp[:, :n, :n] = P
-    bp = np.zeros((count, 8), dtype=np.float32); bp[:, :n] = rhs
+    Pp = np.zeros((count, 8, 8), dtype=dtype); Pp[:, :n, :n] = P
+    bp = np.zeros((count, 8), dtype=dtype); bp[:, :n] = rhs
     dP, db = DeviceBuffer(Pp), DeviceBuffer(bp)
-    dx = DeviceBuffer(nbytes=count * 32, dtype=np.float32, shape=(count, 8))
+    dx = DeviceBuffer(nbytes=count * 8 * np.dtype(dtype).itemsize, dtype=dtype, shape=(count, 8))
     di = DeviceBuffer(nbytes=count * 4, dtype=np.int32, shape=(count,))
     st = Stream()
-    rc = L.mir_lsq_batched_posvx_s(count, n, dP.ptr, db.ptr, dx.ptr, di.ptr, st.handle)
+    rc = getattr(L, "mir_lsq_batched_posvx_" + suf)(count, n, dP.ptr, db.ptr, dx.ptr, di.ptr, st.handle)
     if rc != 0:
-        raise RuntimeError(f"mir_lsq_batched_posvx_s failed: {rc}")
+        raise RuntimeError(f"mir_lsq_batched_posvx_{suf} failed: {rc}")
     st.synchronize()
     x, info = dx.download()[:, :n].copy(), di.download().copy()
     for b in (dP, db, dx, di):

@@ -21,7 +21,7 @@ SOLVER_LIB = os.path.join(LIBDIR, "libmir_optim_amd.so")
 WORKLOADS_LIB = os.path.join(LIBDIR, "libmir_optim_amd_workloads.so")
 
 SOLVER_UNITS = ["abi.hip", "workspace.hip", "solver_loop.hip", "solver_jacobian.hip", "launch_jtj.hip", "launch_broyden.hip",
-                "launch_solve_d.hip", "launch_solve_s.hip", "batched.hip", "comm.hip", "unit_entries.hip", "fit_spline.cpp"]
+                "launch_solve_d.hip", "launch_solve_s.hip", "batched.hip", "batched_d.hip", "comm.hip", "unit_entries.hip", "fit_spline.cpp"]
 WORKLOAD_UNITS = ["workloads.hip", "workloads_gemm.hip", "workloads_resident.hip"]
 
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("MIR_OPTIM_AMD_CXXFLAGS", "").split()
@@ -98,7 +98,8 @@ if __name__ == "__main__":
 
 def build_user_model_example(force=False, verbose=False):
     """tests/user_model/: a caller's own residual models compiled against include/mir_optim_amd_batched.hpp and
-    include/mir_optim_amd_resident.hpp (the device headers of the batched fit and of the resident-J path) into a library of its own -- what a user of that header does. Built here so that it travels prebuilt."""
+    include/mir_optim_amd_resident.hpp (the device headers of the batched fit and of the resident-J path) into a library of its own -- what a user of that header does. Built here so that it travels prebuilt.
+    The double model of user_model_f64.hip goes into a library of its own next to it (user_model_f64_lib())."""
     root = os.path.dirname(HERE)
     src = os.path.join(root, "tests", "user_model", "user_model.hip")
     out = os.path.join(root, "tests", "user_model", "libuser_model.so")
@@ -108,4 +109,19 @@ def build_user_model_example(force=False, verbose=False):
             os.path.join(CSRC, "solve_wave16.h"), os.path.join(CSRC, "solve_kernel.h"), os.path.join(CSRC, "solve_lds.h")]
     if force or _stale(out, deps):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out, src], verbose)
+    src64, out64 = user_model_f64_paths()
+    if force or _stale(out64, [src64] + deps[1:6]):
+        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out64, src64], verbose)
     return out
+
+
+def user_model_f64_paths():
+    """(source, library) of the caller's double model on the batched path (tests/user_model/user_model_f64.hip)"""
+    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
+    return os.path.join(d, "user_model_f64.hip"), os.path.join(d, "libuser_model_f64.so")
+
+
+def user_model_f64_lib(force=False, verbose=False):
+    """Builds (when stale) and returns the path of tests/user_model/libuser_model_f64.so."""
+    build_user_model_example(force=force, verbose=verbose)
+    return user_model_f64_paths()[1]

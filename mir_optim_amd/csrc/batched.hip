@@ -117,7 +117,7 @@ int mir_optimize_least_squares_batched_s(const mir_least_squares_settings_s* S, 
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o_ = off; off = align_up(off + bytes, 256); return o_; };
     const size_t ot = take(tb), od = take(db), ox = take(xb), ol = take(n * sizeof(float)), ou = take(n * sizeof(float)),
-                 orr = take(count * sizeof(BatchedResult)), obasis = take(basis_b);
+                 orr = take(count * sizeof(BatchedResult<float>)), obasis = take(basis_b);
     if (hipMalloc((void**)&base, off) != hipSuccess) return -4;
     o.basis = basis_b ? (float*)(base + obasis) : nullptr;
     o.basis_bytes = basis_b;
@@ -129,12 +129,12 @@ int mir_optimize_least_squares_batched_s(const mir_least_squares_settings_s* S, 
     const float* dt = (const float*)(base + ot); const float* ddata = (const float*)(base + od); float* dx = (float*)(base + ox);
     const float* dlower = (const float*)(base + ol); const float* dupper = (const float*)(base + ou);
     mir_least_squares_result_s* dres = (mir_least_squares_result_s*)(base + orr);
-    std::vector<BatchedResult> res(count);
+    std::vector<BatchedResult<float>> res(count);
     std::vector<float> x0(x, x + count * n);       // starts, for the fallback problems
     if (good && !bad) {
         good = batched_launch(model, S, count, m, dx, dlower, dupper, dt, t_stride, ddata, dres, &o) == 0;
         good = good && hipDeviceSynchronize() == hipSuccess
-            && hipMemcpy(res.data(), dres, count * sizeof(BatchedResult), hipMemcpyDeviceToHost) == hipSuccess
+            && hipMemcpy(res.data(), dres, count * sizeof(BatchedResult<float>), hipMemcpyDeviceToHost) == hipSuccess
             && hipMemcpy(x, dx, xb, hipMemcpyDeviceToHost) == hipSuccess;
     }
     if (good) {

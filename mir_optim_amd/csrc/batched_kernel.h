@@ -25,13 +25,34 @@ enum : int { kModelExpDecay = 0, kModelExp3Affine = 1, kModelExpDecayPad8 = 2 };
 // ---- residual models: r_i = Model::eval(t_i, basis_i, x) - data_i. The contract of a model (the built-in ones below and
 // any user model handed to launch_batched<Model>, include/mir_optim_amd_batched.hpp) -- the compile-time counterpart of the
 // reference's residual callback f(x, y) (least_squares.d:73-80), restricted to residuals that are a function of ONE abscissa:
+//     using value_type = double;   optional: the precision T of the whole fit, float (the default, when the member is absent)
+//                                  or double (LeastSquaresSettings!double, the reference's main instantiation)
 //     static constexpr int n;      number of parameters, 1 <= n <= 8
 //     static constexpr int nb;     per-row BASIS values that do not depend on the parameters (0 = none)
-//     __device__ static void basis(float t, float* b);                       fills b[0 .. nb)
-//     __device__ static float eval(float t, const float* b, const float* x); the model value at t; x has 8 entries, x[n..] = 0
-// The basis values of every row are tabulated once per launch (k_batched_basis: rows x nb floats) and eval() reads the row's
-// values instead of evaluating them again at every trial point and finite-difference point: the same floats enter the same
-// expression. eval must be pure (the reference declares its callbacks pure) and wave-uniform in control flow.
+//     __device__ static void basis(T t, T* b);                       fills b[0 .. nb)
+//     __device__ static T eval(T t, const T* b, const T* x);         the model value at t; x has 8 entries, x[n..] = 0
+// The basis values of every row are tabulated once per launch (k_batched_basis: rows x nb values of T) and eval() reads the
+// row's values instead of evaluating them again at every trial point and finite-difference point: the same numbers enter the
+// same expression. eval must be pure (the reference declares its callbacks pure) and wave-uniform in control flow.
+template <class Model, class = void> struct batched_value { using type = float; };
+template <class Model> struct batched_value<Model, std::void_t<typename Model::value_type>> { using type = typename Model::value_type; };
+template <class Model> using batched_value_t = typename batched_value<Model>::type;
+
+// the operations the kernel spells out, one overload per value type. A fused multiply-add is __builtin_elementwise_fma: ONE
+// rounding (llvm.fma) in float or double, contraction being off in the kernel. It is a builtin, not a wrapper function, on
+// purpose: a call of an inline overload reorders the IR enough that the fp32 kernels scheduled differently (the same operations
+// in another order); with the builtin their code is the one __builtin_fmaf gave, instruction for instruction. The others are
+// the IEEE operations of the type (the float ones are the calls the fp32 kernel always made).
+__device__ __forceinline__ float vmax(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double vmax(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ float vmin(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double vmin(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ float vabs(float a) { return fabsf(a); }
+__device__ __forceinline__ double vabs(double a) { return fabs(a); }
+__device__ __forceinline__ float vsqrt(float a) { return sqrtf(a); }
+__device__ __forceinline__ double vsqrt(double a) { return sqrt(a); }
+// a decimal constant in T: the float literal for float (exactly the value the fp32 kernel always used), the double one else
+template <class T> __host__ __device__ constexpr T lit(float f, double d) { return std::is_same<T, float>::value ? T(f) : T(d); }
 struct ModelExpDecay {          // p0 exp(-t p1) + p2            (n = 3; reference unittest T5's family)
     static constexpr int n = 3, nb = 0;
     __device__ static inline void basis(float, float*) {}
@@ -103,20 +124,51 @@ template <> struct BuiltinModel<kModelExpDecay> { using type = ModelExpDecay; };
 template <> struct BuiltinModel<kModelExp3Affine> { using type = ModelExp3Affine; };
 template <> struct BuiltinModel<kModelExpDecayPad8> { using type = ModelExpDecayPad8; };
 
-struct BatchedResult { int32_t status; uint32_t iterations, fCalls, gCalls; float residual, lambda; };
+// ---- the same three models in DOUBLE (mir_optimize_least_squares_batched_d: same ids, same formulas). Device exp / sin / cos
+// of the type; no host twin reproduces their bits, and none is needed: the f64 path is compared with the f64 oracle to tolerance.
+struct ModelExpDecayD {
+    using value_type = double;
+    static constexpr int n = 3, nb = 0;
+    __device__ static inline void basis(double, double*) {}
+    __device__ static inline double eval(double t, const double*, const double* x) { return x[0] * exp(-t * x[1]) + x[2]; }
+};
+struct ModelExp3AffineD {
+    using value_type = double;
+    static constexpr int n = 8, nb = 0;
+    __device__ static inline void basis(double, double*) {}
+    __device__ static inline double eval(double t, const double*, const double* x)
+    {
+        return x[0] * exp(-t * x[1]) + x[2] * exp(-t * x[3]) + x[4] * exp(-t * x[5]) + x[6] + x[7] * t;
+    }
+};
+struct ModelExpDecayPad8D {     // the basis table holds doubles
+    using value_type = double;
+    static constexpr int n = 8, nb = 4;
+    __device__ static inline void basis(double t, double* b)
+    {
+        b[0] = sin(2.0 * t); b[1] = cos(2.0 * t); b[2] = sin(5.0 * t); b[3] = cos(5.0 * t);
+    }
+    __device__ static inline double eval(double t, const double* b, const double* x)
+    {
+        return x[0] * exp(-t * x[1]) + x[2] + x[3] * b[0] + x[4] * b[1] + x[5] * b[2] + x[6] * b[3] + x[7] * t;
+    }
+};
 
-struct BatchedArgs {
-    LmSettingsDev<float> set;
+// T = float: the layout of mir_least_squares_result_s (24 bytes); T = double: of mir_least_squares_result_d (32 bytes)
+template <class T> struct BatchedResult { int32_t status; uint32_t iterations, fCalls, gCalls; T residual, lambda; };
+
+template <class T> struct BatchedArgs {
+    LmSettingsDev<T> set;
     uint32_t maxIterations, maxAge;
     int count, m;
-    const float* t;        // m (shared) or count x m
+    const T* t;            // m (shared) or count x m
     int t_stride;          // 0 = shared
-    const float* data;     // count x m
-    float* x;              // count x n, in/out
-    const float* lower;    // n (shared)
-    const float* upper;    // n
-    BatchedResult* results;
-    const float* basis;    // (t_stride ? count : 1) x m x nb: the model's per-row basis (k_batched_basis), nullptr when nb == 0
+    const T* data;         // count x m
+    T* x;                  // count x n, in/out
+    const T* lower;        // n (shared)
+    const T* upper;        // n
+    BatchedResult<T>* results;
+    const T* basis;        // (t_stride ? count : 1) x m x nb: the model's per-row basis (k_batched_basis), nullptr when nb == 0
     uint64_t* timing;      // profiling builds (MIRLSQ_BATCHED_TIMING): 10 x count cycle counters (mir_lsq_batched_options.timing), else unused
     uint32_t variant;      // kBatchedNoLadder: one damping value per solve (A/B and the test of the ladder against it)
 };
@@ -124,19 +176,24 @@ constexpr uint32_t kBatchedNoLadder = 1u;
 constexpr uint32_t kBatchedAnalytic = 2u;      // MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN: Model::grad instead of finite differences
 
 // a model MAY provide the derivative of its value with respect to the parameters -- the reference's optional g callback
-// (least_squares.d:80, 1010-1014):   __device__ static void grad(float t, const float* b, const float* x, float* gi /* n */);
+// (least_squares.d:80, 1010-1014):   __device__ static void grad(T t, const T* b, const T* x, T* gi /* n */);
 template <class Model, class = void> struct batched_has_grad : std::false_type {};
 template <class Model>
-struct batched_has_grad<Model, std::void_t<decltype(Model::grad(0.0f, (const float*)nullptr, (const float*)nullptr, (float*)nullptr))>> : std::true_type {};
+struct batched_has_grad<Model, std::void_t<decltype(Model::grad(batched_value_t<Model>(0), (const batched_value_t<Model>*)nullptr,
+                                                                (const batched_value_t<Model>*)nullptr,
+                                                                (batched_value_t<Model>*)nullptr))>> : std::true_type {};
 
 // one row of the basis table: 16-byte loads when the model has four values
-template <int NB> struct BasisRow {
-    float v[NB > 0 ? NB : 1];
-    __device__ inline void load(const float* table, int i)
+template <int NB, class T = float> struct BasisRow {
+    T v[NB > 0 ? NB : 1];
+    __device__ inline void load(const T* table, int i)
     {
-        if constexpr (NB == 4) {
+        if constexpr (NB == 4 && std::is_same<T, float>::value) {
             const float4 q = reinterpret_cast<const float4*>(table)[i];
             v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else if constexpr (NB == 4) {
+            const double2 q0 = reinterpret_cast<const double2*>(table)[2 * i], q1 = reinterpret_cast<const double2*>(table)[2 * i + 1];
+            v[0] = q0.x; v[1] = q0.y; v[2] = q1.x; v[3] = q1.y;
         } else {
 #pragma unroll
             for (int k = 0; k < NB; ++k) v[k] = table[(size_t)i * NB + k];
@@ -145,11 +202,12 @@ template <int NB> struct BasisRow {
 };
 
 template <class Model>
-__global__ __launch_bounds__(256) void k_batched_basis(const float* __restrict__ t, float* __restrict__ table, size_t rows)
+__global__ __launch_bounds__(256) void k_batched_basis(const batched_value_t<Model>* __restrict__ t,
+                                                       batched_value_t<Model>* __restrict__ table, size_t rows)
 {
     constexpr int NB = Model::nb;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < rows; i += (size_t)gridDim.x * blockDim.x) {
-        float b[NB > 0 ? NB : 1];
+        batched_value_t<Model> b[NB > 0 ? NB : 1];
         Model::basis(t[i], b);
 #pragma unroll
         for (int k = 0; k < NB; ++k) table[i * NB + k] = b[k];
@@ -165,31 +223,36 @@ __global__ __launch_bounds__(256) void k_batched_basis(const float* __restrict__
 // Every element sees the operations of the oracle's loops in the oracle's order: the left-looking sums of ?potf2
 // (`s -= F[i][k] F[j][k]`, k ascending) are applied one k at a time to the whole trailing part; the forward sweep of ?potrs
 // runs by columns, its backward sweep (a chain that can only start when z[i + 1] is known) in lane i on column i of the
-// factor. Every multiply-add is ONE fused operation (__builtin_fmaf), division and square root are the IEEE ones: the result
+// factor. Every multiply-add is ONE fused operation (__builtin_elementwise_fma), division and square root are the IEEE ones: the result
 // equals, bit for bit, the oracle's float ?posvx written with fmaf in the same loops (oracle/lm_oracle.c, lmo_posvx_fused_s;
 // tests/test_gpu_batched.py) -- and this file does not depend on which products the compiler chooses to fuse.
-// Divisions and square roots per solve: 44 + 9 sequences (a copy per lane: 76 + 16).
+// Divisions and square roots per solve: 44 + 9 sequences (a copy per lane: 76 + 16). The same template serves double.
 __device__ inline float lane_get(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+__device__ inline double lane_get(double v, int k)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), k), hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
+    return __hiloint2double(hi, lo);
+}
 // a[r], r = lane & 7, as a chain of selects on VALUES: taking the array by reference lets the optimiser turn the chain into one
 // load at a computed address, which pins the whole array in scratch memory
-__device__ inline float row_pick8(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7, int r)
+template <class T> __device__ inline T row_pick8(T a0, T a1, T a2, T a3, T a4, T a5, T a6, T a7, int r)
 {
-    float v = a0;
+    T v = a0;
     v = (r == 1) ? a1 : v; v = (r == 2) ? a2 : v; v = (r == 3) ? a3 : v; v = (r == 4) ? a4 : v;
     v = (r == 5) ? a5 : v; v = (r == 6) ? a6 : v; v = (r == 7) ? a7 : v;
     return v;
 }
 #define MIRLSQ_ROW_PICK(a, r) row_pick8((a)[0], (a)[1], (a)[2], (a)[3], (a)[4], (a)[5], (a)[6], (a)[7], (r))
 // max / min over the eight rows (every lane gets it): the values repeat with period 8 along a 16-lane DPP row, so the
-// rotations by 4, 2, 1 pair each lane with the rows r ^ 4, then r ^ 2, r ^ 1. fmaxf / fminf: a NaN operand is ignored.
-__device__ inline float rows_max(float v)
+// rotations by 4, 2, 1 pair each lane with the rows r ^ 4, then r ^ 2, r ^ 1. fmax / fmin: a NaN operand is ignored.
+template <class T> __device__ inline T rows_max(T v)
 {
-    v = fmaxf(v, dpp_row_ror<4>(v)); v = fmaxf(v, dpp_row_ror<2>(v)); v = fmaxf(v, dpp_row_ror<1>(v));
+    v = vmax(v, dpp_row_ror<4>(v)); v = vmax(v, dpp_row_ror<2>(v)); v = vmax(v, dpp_row_ror<1>(v));
     return v;
 }
-__device__ inline float rows_min(float v)
+template <class T> __device__ inline T rows_min(T v)
 {
-    v = fminf(v, dpp_row_ror<4>(v)); v = fminf(v, dpp_row_ror<2>(v)); v = fminf(v, dpp_row_ror<1>(v));
+    v = vmin(v, dpp_row_ror<4>(v)); v = vmin(v, dpp_row_ror<2>(v)); v = vmin(v, dpp_row_ror<1>(v));
     return v;
 }
 
@@ -198,96 +261,96 @@ __device__ inline float rows_min(float v)
 // Prow: the full symmetric row r of this group's P; rhs_r: component r of its right-hand side. x: the group's solution in every
 // lane of the group. Returns the group's info in every lane of the group. There is no branch on a group's data: a group whose
 // factorization fails keeps computing on values nobody reads.
-template <int N, int NMAX>
-__device__ inline int posvx_rows(const float (&Prow)[NMAX], float rhs_r, int r, float (&x)[NMAX])
+template <int N, int NMAX, class T>
+__device__ inline int posvx_rows(const T (&Prow)[NMAX], T rhs_r, int r, T (&x)[NMAX])
 {
     static_assert(NMAX == 8, "row r = lane & 7");
-    const float eps = Lim<float>::eps / 2, safmin = Lim<float>::min_normal;
+    const T eps = Lim<T>::eps / 2, safmin = Lim<T>::min_normal;
     const bool live = r < N;
-    const float d_r = MIRLSQ_ROW_PICK(Prow, r);
+    const T d_r = MIRLSQ_ROW_PICK(Prow, r);
     // ?poequ
-    const float smin = rows_min(live ? d_r : Lim<float>::inf());
-    const float amax = rows_max(live ? d_r : -Lim<float>::inf());
+    const T smin = rows_min(live ? d_r : Lim<T>::inf());
+    const T amax = rows_max(live ? d_r : -Lim<T>::inf());
     const bool pos = smin > 0;
-    const float scond = sqrtf(smin) / sqrtf(amax);
-    const float s_r = (pos && live) ? 1.0f / sqrtf(d_r) : 1.0f;
-    const float small = safmin / Lim<float>::eps, large = 1.0f / small;
-    const bool rcequ = pos && !(scond >= 0.1f && amax >= small && amax <= large);
+    const T scond = vsqrt(smin) / vsqrt(amax);
+    const T s_r = (pos && live) ? T(1) / vsqrt(d_r) : T(1);
+    const T small = safmin / Lim<T>::eps, large = T(1) / small;
+    const bool rcequ = pos && !(scond >= lit<T>(0.1f, 0.1) && amax >= small && amax <= large);
     // ?laqsy
-    float Arow[NMAX], Frow[NMAX], Fcol[NMAX], s[NMAX];           // Fcol[k] = F[k][r], k > r: column r of the factor, for L^T
+    T Arow[NMAX], Frow[NMAX], Fcol[NMAX], s[NMAX];               // Fcol[k] = F[k][r], k > r: column r of the factor, for L^T
     static_for<NMAX>([&](auto K) {
         constexpr int k = K.value;
         s[k] = dpp_row_bcast<k>(s_r);
-        const float v = Prow[k];
-        Arow[k] = (live && k < N) ? (rcequ ? s[k] * s_r * v : v) : (r == k ? 1.0f : 0.0f);
+        const T v = Prow[k];
+        Arow[k] = (live && k < N) ? (rcequ ? s[k] * s_r * v : v) : (r == k ? T(1) : T(0));
         Frow[k] = Arow[k];
-        Fcol[k] = 0.0f;
+        Fcol[k] = T(0);
     });
-    const float b_r = live ? (rcequ ? s_r * rhs_r : rhs_r) : 0.0f;
+    const T b_r = live ? (rcequ ? s_r * rhs_r : rhs_r) : T(0);
     // ?potf2 'L': after step j, Frow[jj] (jj > j) of row r >= jj holds A[r][jj] - sum_{k <= j} F[r][k] F[jj][k]
     int info = 0;
     static_for<NMAX>([&](auto J) {
         constexpr int j = J.value;
         if constexpr (j < N) {
-            float ajj = dpp_row_bcast<j>(Frow[j]);
+            T ajj = dpp_row_bcast<j>(Frow[j]);
             info = (info == 0 && !(ajj > 0)) ? j + 1 : info;
-            ajj = sqrtf(ajj);
-            const float q = Frow[j] / ajj;
+            ajj = vsqrt(ajj);
+            const T q = Frow[j] / ajj;
             Frow[j] = (r == j) ? ajj : q;                          // rows above the diagonal carry values nobody reads
             static_for<NMAX>([&](auto JJ) {
                 constexpr int jj = JJ.value;
                 if constexpr (jj > j && jj < N) {
-                    const float ljj = dpp_row_bcast<jj>(Frow[j]);  // F[jj][j]
-                    Frow[jj] = __builtin_fmaf(-Frow[j], ljj, Frow[jj]);
+                    const T ljj = dpp_row_bcast<jj>(Frow[j]);      // F[jj][j]
+                    Frow[jj] = __builtin_elementwise_fma(-Frow[j], ljj, Frow[jj]);
                     Fcol[jj] = (r == j) ? ljj : Fcol[jj];
                 }
             });
         }
     });
-    const float fd_r = MIRLSQ_ROW_PICK(Frow, r);                  // F[r][r]
+    const T fd_r = MIRLSQ_ROW_PICK(Frow, r);                      // F[r][r]
     // ?potrs. L y = v by columns: row r takes `t -= F[r][i] y[i]` at step i (ascending i, as in the oracle's row loop).
     // L^T z = y: row i needs t = y[i] - sum_{k > i} F[k][i] z[k] with k ascending, a chain that can only start when z[i + 1]
     // is known: lane i runs it on its column of the factor and the group's z[k].
-    auto potrs = [&](float v_r, float (&z)[NMAX]) {
+    auto potrs = [&](T v_r, T (&z)[NMAX]) {
         static_for<NMAX>([&](auto I) {
             constexpr int i = I.value;
             if constexpr (i < N) {
-                const float yi = dpp_row_bcast<i>(v_r / fd_r);
-                const float upd = __builtin_fmaf(-Frow[i], yi, v_r);
+                const T yi = dpp_row_bcast<i>(v_r / fd_r);
+                const T upd = __builtin_elementwise_fma(-Frow[i], yi, v_r);
                 v_r = (r == i) ? yi : (r > i ? upd : v_r);
             }
         });
 #pragma unroll
-        for (int i = 0; i < NMAX; ++i) z[i] = 0.0f;
+        for (int i = 0; i < NMAX; ++i) z[i] = T(0);
         static_for<NMAX>([&](auto II) {
             constexpr int i = NMAX - 1 - II.value;
             if constexpr (i < N) {
-                float t = v_r;
+                T t = v_r;
 #pragma unroll
-                for (int k = 0; k < NMAX; ++k) if (k > i && k < N) t = __builtin_fmaf(-Fcol[k], z[k], t);
+                for (int k = 0; k < NMAX; ++k) if (k > i && k < N) t = __builtin_elementwise_fma(-Fcol[k], z[k], t);
                 z[i] = dpp_row_bcast<i>(t / fd_r);
             }
         });
     };
     potrs(b_r, x);
     // ?porfs: the loop runs while any group refines; a group that has stopped keeps its solution
-    const float safe1 = (float)(N + 1) * safmin, safe2 = safe1 / eps;
-    float lstres = 3;
+    const T safe1 = (T)(N + 1) * safmin, safe2 = safe1 / eps;
+    T lstres = 3;
     bool active = true;
     for (int count = 1;; ++count) {
-        float ri = b_r, wi = fabsf(b_r);
+        T ri = b_r, wi = vabs(b_r);
 #pragma unroll
         for (int k = 0; k < NMAX; ++k) if (k < N) {
-            ri = __builtin_fmaf(-Arow[k], x[k], ri);
-            wi = __builtin_fmaf(fabsf(Arow[k]), fabsf(x[k]), wi);
+            ri = __builtin_elementwise_fma(-Arow[k], x[k], ri);
+            wi = __builtin_elementwise_fma(vabs(Arow[k]), vabs(x[k]), wi);
         }
         const bool big = wi > safe2;
-        const float q = (big ? fabsf(ri) : fabsf(ri) + safe1) / (big ? wi : wi + safe1);
-        const float berr = rows_max(live ? q : 0.0f);
+        const T q = (big ? vabs(ri) : vabs(ri) + safe1) / (big ? wi : wi + safe1);
+        const T berr = rows_max(live ? q : T(0));
         active = active && berr > eps && 2 * berr <= lstres && count <= 5;
         if (__builtin_amdgcn_ballot_w64(active) == 0) break;
-        float c[NMAX];
-        potrs(live ? ri : 0.0f, c);
+        T c[NMAX];
+        potrs(live ? ri : T(0), c);
 #pragma unroll
         for (int i = 0; i < NMAX; ++i) x[i] = active ? x[i] + c[i] : x[i];
         lstres = active ? berr : lstres;
@@ -298,21 +361,21 @@ __device__ inline int posvx_rows(const float (&Prow)[NMAX], float rhs_r, int r, 
 }
 
 // unit-test entry of posvx_rows: four systems a wave; P count x 64 (row-major, lower triangle read), rhs and x count x 8
-template <int N>
-__global__ __launch_bounds__(64) void k_posvx_rows(const float* __restrict__ P, const float* __restrict__ rhs, int count,
-                                                   float* __restrict__ x, int* __restrict__ info)
+template <int N, class T = float>
+__global__ __launch_bounds__(64) void k_posvx_rows(const T* __restrict__ P, const T* __restrict__ rhs, int count,
+                                                   T* __restrict__ x, int* __restrict__ info)
 {
     const int lane = threadIdx.x, r = lane & 7, g = lane >> 4;
     for (int p0 = 4 * blockIdx.x; p0 < count; p0 += 4 * gridDim.x) {
         const int p = p0 + g < count ? p0 + g : count - 1;            // a short last wave repeats the last system
-        float Prow[8], sol[8];
+        T Prow[8], sol[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) Prow[k] = (r < N && k < N) ? P[(size_t)p * 64 + (k <= r ? r * 8 + k : k * 8 + r)] : 0.0f;
-        const int rc = posvx_rows<N, 8>(Prow, r < N ? rhs[(size_t)p * 8 + r] : 0.0f, r, sol);
+        for (int k = 0; k < 8; ++k) Prow[k] = (r < N && k < N) ? P[(size_t)p * 64 + (k <= r ? r * 8 + k : k * 8 + r)] : T(0);
+        const int rc = posvx_rows<N, 8>(Prow, r < N ? rhs[(size_t)p * 8 + r] : T(0), r, sol);
         if ((lane & 15) == 0 && p0 + g < count) {
             info[p] = rc;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) x[(size_t)p * 8 + k] = (rc == 0 && k < N) ? sol[k] : 0.0f;
+            for (int k = 0; k < 8; ++k) x[(size_t)p * 8 + k] = (rc == 0 && k < N) ? sol[k] : T(0);
         }
     }
 }
@@ -328,13 +391,24 @@ __global__ __launch_bounds__(64) void k_posvx_rows(const float* __restrict__ P, 
 #define MIRLSQ_T1(k) ((void)0)
 #endif
 
+// waves per SIMD: float, what the LDS slices allow at m = 512; double, one -- which lets the compiler use the whole file of
+// 512 VGPRs + AGPRs (the f64 ladder, J^T J accumulators and vectors need about twice the fp32 kernel's registers: DESIGN
+// section 9). LDS bounds the f64 occupancy near there anyway: a problem at m = 512, n = 8 takes 40 KiB of a CU's 160.
+template <class Model> constexpr int batched_waves_per_simd()
+{
+    return std::is_same<batched_value_t<Model>, double>::value ? 1 : (Model::n <= 4 ? 4 : 2);
+}
+
 template <class Model>
-__global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(BatchedArgs a)   // waves per SIMD the LDS slices allow at m = 512
+__global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batched(BatchedArgs<batched_value_t<Model>> a)
 {
     // Nothing in this body is left to the compiler's choice of what to fuse: contraction is off and every multiply-add that is
-    // meant to be ONE rounding is a __builtin_fmaf. The arithmetic of a fit is then a fixed sequence of IEEE operations that
-    // oracle/lm_batched_fused.c repeats on the host (per-lane partial sums, the butterfly of wave_sum): bit-identical results.
+    // meant to be ONE rounding is a __builtin_elementwise_fma. The arithmetic of a fit is then a fixed sequence of IEEE operations that
+    // oracle/lm_batched_fused.c repeats on the host for float (per-lane partial sums, the butterfly of wave_sum): bit-identical
+    // results. T = double runs the same sequence in double.
 #pragma clang fp contract(off)
+    using T = batched_value_t<Model>;
+    static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "Model::value_type: float or double");
     constexpr int N = Model::n;
     constexpr int NMAX = kBatchedNMax;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
@@ -343,40 +417,40 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
     const int lane = threadIdx.x;
     const int prob = blockIdx.x;
     const int m = a.m;
-    float* Jl = reinterpret_cast<float*>(smem_b);                          // J: m x N row-major
-    float* yv = Jl + (size_t)N * m;
-    float* mB = yv + m;
-    const float* tp = a.t + (size_t)(a.t_stride ? prob : 0) * a.t_stride;
-    const float* dp = a.data + (size_t)prob * m;
+    T* Jl = reinterpret_cast<T*>(smem_b);                                  // J: m x N row-major
+    T* yv = Jl + (size_t)N * m;
+    T* mB = yv + m;
+    const T* tp = a.t + (size_t)(a.t_stride ? prob : 0) * a.t_stride;
+    const T* dp = a.data + (size_t)prob * m;
     constexpr int NB = Model::nb;
-    const float* bp = NB ? a.basis + (size_t)(a.t_stride ? prob : 0) * a.t_stride * NB : nullptr;
-    const LmSettingsDev<float>& S = a.set;
+    const T* bp = NB ? a.basis + (size_t)(a.t_stride ? prob : 0) * a.t_stride * NB : nullptr;
+    const LmSettingsDev<T>& S = a.set;
 
-    float x[NMAX], lo[NMAX], up[NMAX];
+    T x[NMAX], lo[NMAX], up[NMAX];
 #pragma unroll
     for (int j = 0; j < NMAX; ++j) {
-        x[j] = j < N ? a.x[(size_t)prob * N + j] : 0.0f;
-        lo[j] = j < N ? a.lower[j] : -Lim<float>::inf();
-        up[j] = j < N ? a.upper[j] : Lim<float>::inf();
+        x[j] = j < N ? a.x[(size_t)prob * N + j] : T(0);
+        lo[j] = j < N ? a.lower[j] : -Lim<T>::inf();
+        up[j] = j < N ? a.upper[j] : Lim<T>::inf();
     }
 #ifdef MIRLSQ_BATCHED_TIMING
     uint64_t tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const uint64_t tstart = __builtin_readcyclecounter();
 #endif
-    BatchedResult ret;
+    BatchedResult<T> ret;
     ret.status = -26;   // numericError, LS:132
     ret.iterations = 0; ret.fCalls = 0; ret.gCalls = 0;
-    ret.residual = Lim<float>::inf(); ret.lambda = 0;
+    ret.residual = Lim<T>::inf(); ret.lambda = 0;
 
     // The lane's rows (lane, lane + 64, ...) are taken in chunks of UNR: the loads of a chunk are issued together (index clamped
     // to the last row: always a valid address), then the rows are used in order, so a wave does not pay one memory latency a
     // row. The sum of squares is accumulated in the order of the plain loop.
-    auto feval = [&](const float (&p)[NMAX], float* dst) -> float {      // dst = f(p); returns ||f||^2
+    auto feval = [&](const T (&p)[NMAX], T* dst) -> T {                  // dst = f(p); returns ||f||^2
         constexpr int UNR = 8;
-        float ss = 0;
+        T ss = 0;
         for (int base = lane; base - lane < m; base += kWave * UNR) {
-            float tv[UNR], dv[UNR], rv[UNR];
-            BasisRow<NB> bv[UNR];
+            T tv[UNR], dv[UNR], rv[UNR];
+            BasisRow<NB, T> bv[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int i = min(base + kWave * u, m - 1);
@@ -389,7 +463,7 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
             for (int u = 0; u < UNR; ++u) {
                 const int i = base + kWave * u;
                 if (i < m) dst[i] = rv[u];
-                ss = i < m ? __builtin_fmaf(rv[u], rv[u], ss) : ss;
+                ss = i < m ? __builtin_elementwise_fma(rv[u], rv[u], ss) : ss;
             }
         }
         return wave_sum(ss);
@@ -399,7 +473,7 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
     bool finite = true, inb = true;
 #pragma unroll
     for (int j = 0; j < NMAX; ++j) if (j < N) {
-        if (!(-Lim<float>::inf() < x[j] && x[j] < Lim<float>::inf())) finite = false;
+        if (!(-Lim<T>::inf() < x[j] && x[j] < Lim<T>::inf())) finite = false;
         if (!(lo[j] <= x[j]) || !(x[j] <= up[j])) inb = false;
     }
     if (m == 0 || !finite) ret.status = -31;           // badGuess
@@ -415,21 +489,21 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
         uint32_t age = maxAge;
         // J^T J and J^T y live one ROW per lane (row r = lane & 7 in every group of eight lanes), as posvx_rows wants them
         const int r = lane & 7;
-        float dx[NMAX], JJrow[NMAX], Jy_r = 0;
+        T dx[NMAX], JJrow[NMAX], Jy_r = 0;
 #pragma unroll
         for (int j = 0; j < NMAX; ++j) { dx[j] = 0; JJrow[j] = 0; }
-        float lad_x[NMAX], lad_lam[4] = {0, 0, 0, 0};      // the ladder of solutions (group g of the wave: level g), see below
+        T lad_x[NMAX], lad_lam[4] = {0, 0, 0, 0};          // the ladder of solutions (group g of the wave: level g), see below
 #pragma unroll
         for (int j = 0; j < NMAX; ++j) lad_x[j] = 0;
         int lad_info = 0, lad_level = 0;
         bool lad_valid = false;
         const int lad_depth = (a.variant & kBatchedNoLadder) ? 1 : 4;
-        float dx_dot = 0, mu = 1, lambda = 0;
+        T dx_dot = 0, mu = 1, lambda = 0;
         ret.status = -1;                                                   // maxIterations, LS:971
         do {
             if (fConverged) { ret.status = 3; break; }                     // LS:974
             if (!(lambda <= S.maxLambda)) { ret.status = 0; break; }       // LS:979
-            if (mu > 16.0f && age) { needJacobian = true; age = maxAge; mu = 1; }   // LS:984
+            if (mu > T(16) && age) { needJacobian = true; age = maxAge; mu = 1; }   // LS:984
             {
                 bool nan = false;
 #pragma unroll
@@ -441,24 +515,24 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
                 MIRLSQ_T0();
                 if (age < maxAge) {                                        // Broyden LS:999-1007
                     age++;
-                    const float d = 1.0f / dx_dot;
+                    const T d = T(1) / dx_dot;
                     for (int i = lane; i < m; i += kWave) {
-                        float* Ji = Jl + (size_t)i * N;
-                        float dot = 0;
+                        T* Ji = Jl + (size_t)i * N;
+                        T dot = 0;
 #pragma unroll
-                        for (int j = 0; j < N; ++j) dot = __builtin_fmaf(Ji[j], dx[j], dot);
-                        const float t = (mB[i] - yv[i]) + dot;             // mB holds the previous residual
-                        const float u = -d * t;
+                        for (int j = 0; j < N; ++j) dot = __builtin_elementwise_fma(Ji[j], dx[j], dot);
+                        const T t = (mB[i] - yv[i]) + dot;                 // mB holds the previous residual
+                        const T u = -d * t;
 #pragma unroll
-                        for (int j = 0; j < N; ++j) Ji[j] = __builtin_fmaf(u, dx[j], Ji[j]);
+                        for (int j = 0; j < N; ++j) Ji[j] = __builtin_elementwise_fma(u, dx[j], Ji[j]);
                     }
                 } else if (use_g) {                                        // g(x, J), LS:1010-1014
                     age = 0;
                     if constexpr (HAS_GRAD) {
                         for (int i = lane; i < m; i += kWave) {
-                            BasisRow<NB> b;
+                            BasisRow<NB, T> b;
                             b.load(bp, i);
-                            float gi[NMAX];
+                            T gi[NMAX];
 #pragma unroll
                             for (int j = 0; j < NMAX; ++j) gi[j] = 0;
                             Model::grad(tp[i], b.v, x, gi);
@@ -470,30 +544,30 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
                 } else {                                                   // FD LS:1016-1050
                     age = 0;
                     // the n central differences of a row share its t, d and basis: rows outside, columns inside
-                    float xph[NMAX], xmh[NMAX], inv[NMAX];
+                    T xph[NMAX], xmh[NMAX], inv[NMAX];
 #pragma unroll
                     for (int j = 0; j < NMAX; ++j) {
-                        xmh[j] = fmaxf(x[j] - S.jacobianEpsilon, lo[j]);
-                        xph[j] = fminf(x[j] + S.jacobianEpsilon, up[j]);
-                        const float twh = xph[j] - xmh[j];
-                        inv[j] = twh != 0 ? 1.0f / twh : 0.0f;             // a zero-width interval: the column is zero, LS:1045
+                        xmh[j] = vmax(x[j] - S.jacobianEpsilon, lo[j]);
+                        xph[j] = vmin(x[j] + S.jacobianEpsilon, up[j]);
+                        const T twh = xph[j] - xmh[j];
+                        inv[j] = twh != 0 ? T(1) / twh : T(0);             // a zero-width interval: the column is zero, LS:1045
                     }
                     for (int i = lane; i < m; i += kWave) {
-                        BasisRow<NB> b;
+                        BasisRow<NB, T> b;
                         b.load(bp, i);
-                        const float ti = tp[i], di = dp[i];
-                        float p[NMAX];
+                        const T ti = tp[i], di = dp[i];
+                        T p[NMAX];
 #pragma unroll
                         for (int k = 0; k < NMAX; ++k) p[k] = x[k];
 #pragma unroll
                         for (int j = 0; j < N; ++j) {
                             p[j] = xph[j];
-                            const float fp = Model::eval(ti, b.v, p) - di;
+                            const T fp = Model::eval(ti, b.v, p) - di;
                             p[j] = xmh[j];
-                            const float fm = Model::eval(ti, b.v, p) - di;
+                            const T fm = Model::eval(ti, b.v, p) - di;
                             p[j] = x[j];
-                            const float v = fp - fm;
-                            Jl[(size_t)i * N + j] = inv[j] != 0 ? v * inv[j] : 0.0f;
+                            const T v = fp - fm;
+                            Jl[(size_t)i * N + j] = inv[j] != 0 ? v * inv[j] : T(0);
                         }
                     }
                     ret.fCalls += N;                                       // LS:1049 (quirk Q5)
@@ -503,31 +577,31 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
                 tacc[1] += t1_ - t0_;
 #endif
                 // Jy = J^T y (LS:1052) and JJ = J^T J lower (LS:1065) in one sweep over the lane's rows
-                float accJ[NMAX][NMAX], accy[NMAX];
+                T accJ[NMAX][NMAX], accy[NMAX];
 #pragma unroll
                 for (int j = 0; j < NMAX; ++j) { accy[j] = 0;
 #pragma unroll
                     for (int k = 0; k < NMAX; ++k) accJ[j][k] = 0; }
                 for (int i = lane; i < m; i += kWave) {
-                    const float* Ji = Jl + (size_t)i * N;
-                    const float yi = yv[i];
-                    float row[NMAX];
+                    const T* Ji = Jl + (size_t)i * N;
+                    const T yi = yv[i];
+                    T row[NMAX];
 #pragma unroll
-                    for (int j = 0; j < NMAX; ++j) row[j] = j < N ? Ji[j] : 0.0f;
+                    for (int j = 0; j < NMAX; ++j) row[j] = j < N ? Ji[j] : T(0);
 #pragma unroll
                     for (int j = 0; j < N; ++j) {
-                        accy[j] = __builtin_fmaf(row[j], yi, accy[j]);
+                        accy[j] = __builtin_elementwise_fma(row[j], yi, accy[j]);
 #pragma unroll
-                        for (int k = 0; k <= j; ++k) accJ[j][k] = __builtin_fmaf(row[j], row[k], accJ[j][k]);
+                        for (int k = 0; k <= j; ++k) accJ[j][k] = __builtin_elementwise_fma(row[j], row[k], accJ[j][k]);
                     }
                 }
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
-                    const float ty = wave_sum(accy[j]);
+                    const T ty = wave_sum(accy[j]);
                     Jy_r = (r == j) ? ty : Jy_r;
 #pragma unroll
                     for (int k = 0; k <= j; ++k) {
-                        const float t = wave_sum(accJ[j][k]);                  // element (j, k) and its mirror (k, j)
+                        const T t = wave_sum(accJ[j][k]);                      // element (j, k) and its mirror (k, j)
                         JJrow[k] = (r == j) ? t : JJrow[k];
                         if (k != j) JJrow[j] = (r == k) ? t : JJrow[j];
                     }
@@ -536,7 +610,7 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
 #ifdef MIRLSQ_BATCHED_TIMING
                 tacc[2] += __builtin_readcyclecounter() - t1_;
 #endif
-                const float gmax = lane_get(rows_max(fabsf(Jy_r)), 0);         // rows >= N hold zeros
+                const T gmax = lane_get(rows_max(vabs(Jy_r)), 0);              // rows >= N hold zeros
                 if (!(gmax > S.gradTolerance)) {                           // LS:1053-1062
                     if (age == 0) { ret.status = 2; break; }
                     age = maxAge;
@@ -545,9 +619,9 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
             }
             if (!(lambda >= S.minLambda)) {                                // LS:1067-1072
                 // the largest diagonal element (a sum of squares: its own absolute value; a NaN is skipped as by `>`)
-                const float best = lane_get(rows_max(r < N ? fabsf(MIRLSQ_ROW_PICK(JJrow, r)) : -1.0f), 0);
-                const float val = best < 0 ? 0.0f : best;
-                lambda = 0.001f * val;
+                const T best = lane_get(rows_max(r < N ? vabs(MIRLSQ_ROW_PICK(JJrow, r)) : T(-1)), 0);
+                const T val = best < 0 ? T(0) : best;
+                lambda = lit<T>(0.001f, 0.001) * val;
                 if (!(lambda >= S.minLambda)) lambda = 1;
             }
             // LS:1079-1080 (-> QP:194). The four 16-lane groups of the wave solve with lambda and with the three values the
@@ -555,14 +629,14 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
             // cost of one solve; a rejected step then finds its solution ready. A level is used only while J^T J is the one
             // the ladder was built on and lambda is bit for bit the ladder's value: the steps are those of the one-by-one loop.
             if (!(lad_valid && lad_level < lad_depth && lambda == lad_lam[lad_level])) {
-                float l = lambda, mm = mu;
+                T l = lambda, mm = mu;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) { lad_lam[g] = l; l *= S.lambdaIncrease * mm; mm *= 2; }
                 const int g = lane >> 4;
-                const float mine = g == 0 ? lad_lam[0] : (g == 1 ? lad_lam[1] : (g == 2 ? lad_lam[2] : lad_lam[3]));
-                float Prow[NMAX];
+                const T mine = g == 0 ? lad_lam[0] : (g == 1 ? lad_lam[1] : (g == 2 ? lad_lam[2] : lad_lam[3]));
+                T Prow[NMAX];
 #pragma unroll
-                for (int k = 0; k < NMAX; ++k) Prow[k] = JJrow[k] + ((k == r && r < N) ? mine : 0.0f);   // (Q1)
+                for (int k = 0; k < NMAX; ++k) Prow[k] = JJrow[k] + ((k == r && r < N) ? mine : T(0));   // (Q1)
                 MIRLSQ_T0();
                 lad_info = posvx_rows<N, NMAX>(Prow, -Jy_r, r, lad_x);
                 MIRLSQ_T1(3);
@@ -575,7 +649,7 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
 #ifdef MIRLSQ_BATCHED_TIMING
             const uint64_t t6_ = __builtin_readcyclecounter();
 #endif
-            float sol[NMAX];
+            T sol[NMAX];
             const int lad_lane = 16 * lad_level++;
             const int info = __builtin_amdgcn_readlane(lad_info, lad_lane);
 #pragma unroll
@@ -589,25 +663,25 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
             }
             if (nan) { ret.status = -26; break; }                          // LS:1087
             if (!feasible) { ret.status = kBatchedNeedsGeneral; break; }   // active-set loop: general solver
-            float trial[NMAX], ndd = 0;
+            T trial[NMAX], ndd = 0;
 #pragma unroll
             for (int j = 0; j < NMAX; ++j) {
-                float d = sol[j] + x[j];                                   // LS:1096-1097
+                T d = sol[j] + x[j];                                       // LS:1096-1097
                 d = d - x[j];
-                sol[j] = j < N ? d : 0.0f;
-                ndd = __builtin_fmaf(sol[j], sol[j], ndd);
-                trial[j] = fmaxf(fminf(sol[j] + x[j], up[j]), lo[j]);      // LS:1108-1110
+                sol[j] = j < N ? d : T(0);
+                ndd = __builtin_elementwise_fma(sol[j], sol[j], ndd);
+                trial[j] = vmax(vmin(sol[j] + x[j], up[j]), lo[j]);        // LS:1108-1110
             }
-            if (!(sqrtf(ndd) < S.maxStep)) { lambda *= S.lambdaIncrease * mu; mu *= 2; continue; }   // LS:1101-1106
+            if (!(vsqrt(ndd) < S.maxStep)) { lambda *= S.lambdaIncrease * mu; mu *= 2; continue; }   // LS:1101-1106
             ++ret.fCalls;                                                  // LS:1112-1115
 #ifdef MIRLSQ_BATCHED_TIMING
             tacc[6] += __builtin_readcyclecounter() - t6_;
 #endif
             // the trial residual goes to the buffer that is NOT the current y
-            float trialResidual;
+            T trialResidual;
             { MIRLSQ_T0(); trialResidual = feval(trial, mB); MIRLSQ_T1(0); }
-            if (!(trialResidual <= Lim<float>::inf())) { ret.status = -26; break; }   // LS:1117
-            const float improvement = ret.residual - trialResidual;
+            if (!(trialResidual <= Lim<T>::inf())) { ret.status = -26; break; }       // LS:1117
+            const T improvement = ret.residual - trialResidual;
 #ifdef MIRLSQ_BATCHED_TIMING
             const uint64_t t7_ = __builtin_readcyclecounter();
 #endif
@@ -617,31 +691,31 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
             ret.iterations++;
 #pragma unroll
             for (int j = 0; j < NMAX; ++j) { x[j] = trial[j]; dx[j] = sol[j]; }
-            { float* tmp = yv; yv = mB; mB = tmp; }                        // swap(mBuffer, y): mB = previous residual
+            { T* tmp = yv; yv = mB; mB = tmp; }                            // swap(mBuffer, y): mB = previous residual
             ret.residual = trialResidual;
             fConverged = ret.residual <= S.maxGoodResidual;
             dx_dot = ndd;
-            float pred = 0;                                                // LS:1141-1142 (undamped JJ)
+            T pred = 0;                                                    // LS:1141-1142 (undamped JJ)
             {
-                float tj = 0;                                              // row r of J^T J dx + 2 J^T y, then the dot with dx
+                T tj = 0;                                                  // row r of J^T J dx + 2 J^T y, then the dot with dx
 #pragma unroll
-                for (int k = 0; k < NMAX; ++k) tj = __builtin_fmaf(JJrow[k], dx[k], tj);
+                for (int k = 0; k < NMAX; ++k) tj = __builtin_elementwise_fma(JJrow[k], dx[k], tj);
                 tj = tj + 2 * Jy_r;
 #pragma unroll
-                for (int j = 0; j < NMAX; ++j) pred = __builtin_fmaf(lane_get(tj, j), dx[j], pred);
+                for (int j = 0; j < NMAX; ++j) pred = __builtin_elementwise_fma(lane_get(tj, j), dx[j], pred);
             }
             pred = -pred;
             if (!(pred > 0)) { ret.status = 0; break; }                    // LS:1144-1148
-            const float rho = pred / improvement;                          // LS:1150 (Q2)
+            const T rho = pred / improvement;                              // LS:1150 (Q2)
             if (rho < S.minStepQuality) { lambda *= S.lambdaIncrease * mu; mu *= 2; }
-            else if (rho >= S.goodStepQuality) lambda = fmaxf(S.lambdaDecrease * lambda * mu, S.minLambda);
-            float xn = 0;
+            else if (rho >= S.goodStepQuality) lambda = vmax(S.lambdaDecrease * lambda * mu, S.minLambda);
+            T xn = 0;
 #pragma unroll
-            for (int j = 0; j < NMAX; ++j) xn = __builtin_fmaf(x[j], x[j], xn);
+            for (int j = 0; j < NMAX; ++j) xn = __builtin_elementwise_fma(x[j], x[j], xn);
 #ifdef MIRLSQ_BATCHED_TIMING
             tacc[7] += __builtin_readcyclecounter() - t7_;
 #endif
-            if (!(sqrtf(dx_dot) > S.absTolerance && sqrtf(xn) > sqrtf(dx_dot) * S.relTolerance)) {   // LS:1164-1173 (Q6)
+            if (!(vsqrt(dx_dot) > S.absTolerance && vsqrt(xn) > vsqrt(dx_dot) * S.relTolerance)) {   // LS:1164-1173 (Q6)
                 if (age == 0) { ret.status = 1; break; }
                 age = maxAge;
                 continue;
@@ -662,16 +736,16 @@ __global__ __launch_bounds__(64, Model::n <= 4 ? 4 : 2) void k_lm_batched(Batche
 
 
 // residual of one problem as a DEVICE callback body (used when a batched problem falls back to the general solver)
-template <class Model>
-__global__ __launch_bounds__(256) void k_batched_model_eval(const float* __restrict__ t, const float* __restrict__ d,
-                                                            const float* __restrict__ x, float* __restrict__ y, int m)
+template <class Model, class T = batched_value_t<Model>>
+__global__ __launch_bounds__(256) void k_batched_model_eval(const T* __restrict__ t, const T* __restrict__ d,
+                                                            const T* __restrict__ x, T* __restrict__ y, int m)
 {
     constexpr int NB = Model::nb;
-    float p[kBatchedNMax];
+    T p[kBatchedNMax];
 #pragma unroll
-    for (int j = 0; j < kBatchedNMax; ++j) p[j] = j < Model::n ? x[j] : 0.0f;
+    for (int j = 0; j < kBatchedNMax; ++j) p[j] = j < Model::n ? x[j] : T(0);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
-        float b[NB > 0 ? NB : 1];
+        T b[NB > 0 ? NB : 1];
         Model::basis(t[i], b);
         y[i] = Model::eval(t[i], b, p) - d[i];
     }
