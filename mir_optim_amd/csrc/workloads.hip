@@ -372,6 +372,13 @@ void wl_tanh_linear_fbd_d(void* vctx, size_t m, size_t n, size_t p, const double
     auto* c = static_cast<wl_tanh_linear_ctx*>(vctx);
     launch_tanh_linear_batched_diff((const double*)c->A, (const double*)c->b, X, D, m, (int)n, (int)p, (hipStream_t)c->stream, c->read_a_once);
 }
+// the same panel with every product of the GEMM computed (n = 128: no forking off the base point's chain): for A/B runs and tests
+void wl_tanh_linear_fbd_dense_d(void* vctx, size_t m, size_t n, size_t p, const double* X, double* D)
+{
+    auto* c = static_cast<wl_tanh_linear_ctx*>(vctx);
+    launch_tanh_linear_batched_diff((const double*)c->A, (const double*)c->b, X, D, m, (int)n, (int)p, (hipStream_t)c->stream, c->read_a_once,
+                                    true);
+}
 void wl_tanh_linear_f_s(void* vctx, size_t m, size_t n, const float* x, float* y)
 {
     auto* c = static_cast<wl_tanh_linear_ctx*>(vctx);

@@ -138,39 +138,54 @@ template <int NK> struct TlbCfg {
     static constexpr int B_OFF = NS * STAGE_BYTES;
     static constexpr int LDS_BYTES = B_OFF + NSB * 256;
     static constexpr int THREADS = 64 * (COMPUTE_WAVES + LOADER_WAVES);
+    // prefix-forking difference panel (n = 128, tlb_fork_*): the base chain's accumulators P_2, P_4, ..., P_{NK-2} of both
+    // tiles of a stage, 16 doubles each in the D layout [fq][r], in a two-stage ring behind the b ring; then the vote word
+    static constexpr bool FORK = NK == 32;
+    static constexpr int NPRE = NK / 2 - 1;
+    static constexpr int PRE_STAGE = TILES * NPRE * 16 * 8;
+    static constexpr int PRE_OFF = LDS_BYTES;
+    static constexpr int VOTE_OFF = PRE_OFF + 2 * PRE_STAGE;
+    static constexpr int FORK_LDS_BYTES = VOTE_OFF + 16;
 };
+
+// loader LOADER's share of the DMA of flat stage f (f % S of this workgroup's stages) into ring slot f % NS; loader 1 also b
+template <int NK, int LOADER>
+__device__ __forceinline__ void tlb_issue(const double* __restrict__ A, const double* __restrict__ b, size_t m,
+                                          unsigned char* smem, int lane, size_t S, size_t f)
+{
+    using C = TlbCfg<NK>;
+    constexpr int MYI = C::IPS / 2;
+    const unsigned char* Ab = reinterpret_cast<const unsigned char*>(A);
+    const unsigned char* bb = reinterpret_cast<const unsigned char*>(b);
+    const size_t stage = blockIdx.x + (f % S) * (size_t)gridDim.x;
+    const size_t row0 = stage * C::ROWS;
+    unsigned char* slot = smem + (f % C::NS) * C::STAGE_BYTES;
+#pragma unroll
+    for (int k = 0; k < MYI; ++k) {
+        const int ins = LOADER + 2 * k;
+        const int g = ins * 64 + lane;                          // 16-byte piece of the stage image this lane fills
+        const int R = g / C::PPR, sp = g % C::PPR;              // LDS row within the stage = 16 tile + MFMA row
+        size_t row = row0 + (R & 16) + tlb_rho(R & 15);         // the memory row that feeds it
+        row = row < m ? row : m - 1;                            // rows past m: valid bytes, never stored
+        const int piece = sp ^ tlb_sigma(R & 15);
+        __builtin_amdgcn_global_load_lds((wl_gbl_ptr)(Ab + (row * C::N + 2 * piece) * 8),
+                                         (wl_lds_ptr)(slot + ins * 1024), 16, 0, 2 /* nt */);
+    }
+    if constexpr (LOADER == 1) {
+        size_t row = row0 + (lane >> 1);
+        row = row < m ? row : m - 1;
+        __builtin_amdgcn_global_load_lds((wl_gbl_ptr)(bb + row * 8 + (lane & 1) * 4),
+                                         (wl_lds_ptr)(smem + C::B_OFF + (f % C::NSB) * 256), 4, 0, 0);
+    }
+}
 
 template <int NK, int LOADER>
 __device__ __forceinline__ void tlb_loader(const double* __restrict__ A, const double* __restrict__ b, size_t m,
                                            unsigned char* smem, int lane, size_t S, size_t F)
 {
     using C = TlbCfg<NK>;
-    constexpr int MYI = C::IPS / 2;
-    constexpr int OPS = MYI + (LOADER == 1 ? 1 : 0);
-    const unsigned char* Ab = reinterpret_cast<const unsigned char*>(A);
-    const unsigned char* bb = reinterpret_cast<const unsigned char*>(b);
-    auto issue = [&](size_t f) {
-        const size_t stage = blockIdx.x + (f % S) * (size_t)gridDim.x;
-        const size_t row0 = stage * C::ROWS;
-        unsigned char* slot = smem + (f % C::NS) * C::STAGE_BYTES;
-#pragma unroll
-        for (int k = 0; k < MYI; ++k) {
-            const int ins = LOADER + 2 * k;
-            const int g = ins * 64 + lane;                      // 16-byte piece of the stage image this lane fills
-            const int R = g / C::PPR, sp = g % C::PPR;          // LDS row within the stage = 16 tile + MFMA row
-            size_t row = row0 + (R & 16) + tlb_rho(R & 15);     // the memory row that feeds it
-            row = row < m ? row : m - 1;                        // rows past m: valid bytes, never stored
-            const int piece = sp ^ tlb_sigma(R & 15);
-            __builtin_amdgcn_global_load_lds((wl_gbl_ptr)(Ab + (row * C::N + 2 * piece) * 8),
-                                             (wl_lds_ptr)(slot + ins * 1024), 16, 0, 2 /* nt */);
-        }
-        if constexpr (LOADER == 1) {
-            size_t row = row0 + (lane >> 1);
-            row = row < m ? row : m - 1;
-            __builtin_amdgcn_global_load_lds((wl_gbl_ptr)(bb + row * 8 + (lane & 1) * 4),
-                                             (wl_lds_ptr)(smem + C::B_OFF + (f % C::NSB) * 256), 4, 0, 0);
-        }
-    };
+    constexpr int OPS = C::IPS / 2 + (LOADER == 1 ? 1 : 0);
+    auto issue = [&](size_t f) { tlb_issue<NK, LOADER>(A, b, m, smem, lane, S, f); };
     const size_t pre = F < (size_t)C::D ? F : (size_t)C::D;
     for (size_t f = 0; f < pre; ++f) issue(f);
     for (size_t f = 0; f < F; ++f) {
@@ -543,12 +558,218 @@ __device__ __forceinline__ void tlb_compute_once(const double* __restrict__ X, d
     }
 }
 
+// ---- difference panel by PREFIX FORKING (n = 128, p = 2n finite-difference points, A read once). Points 2 j, 2 j + 1 are x except
+//      in coordinate j, and k-step s of the chain multiplies columns 8 (s >> 1) + 2 fq + (s & 1): the 16-point group g (coordinates
+//      8 g .. 8 g + 7) meets its own coordinates first at k-step 2 g. Before that every column of its MFMAs has the inputs of the
+//      chain of x itself (same A fragment, same B value, same accumulator), and an element of an MFMA result depends only on its
+//      own row, column and accumulator: the group's accumulator after 2 g steps IS the base chain's P_2g, bit for bit. So
+//        * the two loader waves also run the base chain (x in all 16 columns) of one tile each, one stage ahead of the compute
+//          waves, and publish P_2, P_4, ..., P_30 through LDS (16 doubles per prefix and tile: all columns of P_s are equal);
+//        * compute wave w owns the groups w ^ 2 and 15 - w, starts each from its prefix, then runs the group's own k-steps
+//          2 g .. NK - 1 in the order of tlb_compute: 302 instead of 512 MFMAs per tile. Balance: a group costs 32 - 2 g k-steps
+//          per tile, and the loader waves 8, 9 share the SIMDs of waves 0, 4 and 1, 5 (waves w and w + 4 share one). So those
+//          four waves get 30 k-steps per tile ({2, 15}, {3, 14}, {6, 11}, {7, 10}) and the other four 38 ({0, 13}, {1, 12},
+//          {4, 9}, {5, 8}): with a loader's base chain (15 per tile) 75 / 76 per SIMD and tile (groups {w, 15 - w}: 83 / 68);
+//        * a stage of A is DMA'd once for all 256 points; the epilogue is tlb_compute's.
+//      The structure is never assumed: tlb_fork_vote compares, as bit patterns, every X entry a forked chain takes from the base
+//      chain with the base value, and the workgroup runs the dense tlb_compute unless all of them agree.
+//      Barriers: the loaders pass B_f once stage f is in LDS, then DMA stage f + D and run the base chain of f; the compute waves
+//      compute stage f after B_{f + 1} (its prefixes are written by then). So a stage occupies a ring slot until B_{f + 2} and
+//      the DMA of f + D is issued after B_f, not before: D + 2 = NS slots.
+
+// every compute lane checks its two points over the k-steps their chains take from the base chain; true: all equal
+template <int NK>
+__device__ __forceinline__ bool tlb_fork_vote(const double* __restrict__ X, unsigned char* smem, int lane, int wave)
+{
+    using C = TlbCfg<NK>;
+    constexpr int N = C::N, P = 2 * N;
+    volatile int* vote = reinterpret_cast<volatile int*>(smem + C::VOTE_OFF);
+    if (threadIdx.x == 0) *vote = 0;
+    __syncthreads();
+    if (wave < C::COMPUTE_WAVES) {
+        const int fr = lane & 15, fq = lane >> 4;
+        const int s0 = 2 * (wave ^ 2), s1 = 2 * (2 * C::COMPUTE_WAVES - 1 - wave);   // its groups (tlb_fork_compute) fork at s0, s1
+        const unsigned long long* xr = reinterpret_cast<const unsigned long long*>(X);
+        const unsigned long long* x0 = xr + (size_t)(8 * s0 + fr) * N;         // point 16 g + fr
+        const unsigned long long* x1 = xr + (size_t)(8 * s1 + fr) * N;
+        bool bad = false;
+#pragma unroll
+        for (int s = 0; s < NK - 2; ++s) {
+            const int k = 8 * (s >> 1) + 2 * fq + (s & 1);
+            const unsigned long long xb = xr[(size_t)((2 * k + 2) % P) * N + k];  // the base value, as tlb_compute_once reads it
+            const unsigned long long a = x0[k], c = x1[k];
+            bad |= (s < s0) & (a != xb);
+            bad |= (s < s1) & (c != xb);
+        }
+        if (bad) *vote = 1;
+    }
+    __syncthreads();
+    return *vote == 0;
+}
+
+template <int NK, int LOADER>
+__device__ __forceinline__ void tlb_fork_loader(const double* __restrict__ A, const double* __restrict__ b,
+                                                const double* __restrict__ X, size_t m, unsigned char* smem, int lane, size_t S)
+{
+    using C = TlbCfg<NK>;
+    using Acc = __attribute__((ext_vector_type(4))) double;
+    constexpr int N = C::N, P = 2 * N;
+    constexpr int OPS = C::IPS / 2 + (LOADER == 1 ? 1 : 0);
+    const int fr = lane & 15, fq = lane >> 4;
+    const int v = fq ^ tlb_sigma(fr);
+    int laddr[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) laddr[k] = LOADER * 16 * N * 8 + fr * N * 8 + ((4 * k) ^ v) * 16;   // tile LOADER of a stage
+    double xb[2 * C::NPRE];
+#pragma unroll
+    for (int s = 0; s < 2 * C::NPRE; ++s) {
+        const int k = 8 * (s >> 1) + 2 * fq + (s & 1);
+        xb[s] = X[(size_t)((2 * k + 2) % P) * N + k];
+    }
+    auto issue = [&](size_t f) { tlb_issue<NK, LOADER>(A, b, m, smem, lane, S, f); };
+    for (size_t f = 0; f < S && f < (size_t)C::D; ++f) issue(f);
+    for (size_t f = 0; f < S; ++f) {
+        if (f + 1 < S) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");   // stage f + 1 may still be in flight
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                       // B_f: stage f is in LDS; stage f - 2 has no readers left
+        asm volatile("" ::: "memory");
+        if (f + C::D < S) issue(f + C::D);
+        // base chain of tile LOADER of stage f: after k-steps 2 j + 1, lanes of column 0 store P_{2 j + 2}
+        const unsigned char* slot = smem + (f % C::NS) * C::STAGE_BYTES;
+        double* pre = reinterpret_cast<double*>(smem + C::PRE_OFF + (f & 1) * C::PRE_STAGE) + LOADER * C::NPRE * 16 + 4 * fq;
+        Acc acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < C::NPRE; ++j) {
+            const double2 a = *reinterpret_cast<const double2*>(slot + laddr[j & 3] + (j >> 2) * 256);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, xb[2 * j], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, xb[2 * j + 1], acc, 0, 0, 0);
+            if (fr == 0) {
+                *reinterpret_cast<double2*>(pre + 16 * j) = make_double2(acc[0], acc[1]);
+                *reinterpret_cast<double2*>(pre + 16 * j + 2) = make_double2(acc[2], acc[3]);
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the prefixes are in LDS before the next barrier
+    }
+    __builtin_amdgcn_s_barrier();                           // B_S: the prefixes of the last stage
+}
+
+template <int NK, int W>
+__device__ __forceinline__ void tlb_fork_compute(const double* __restrict__ X, double* __restrict__ D, size_t m,
+                                                 unsigned char* smem, int lane, size_t S)
+{
+    using C = TlbCfg<NK>;
+    using Acc = __attribute__((ext_vector_type(4))) double;
+    constexpr int N = C::N;
+    constexpr int GA = W ^ 2, GC = 2 * C::COMPUTE_WAVES - 1 - W;   // this wave's two groups (see the balance note above)
+    constexpr int SA = 2 * GA, SC = 2 * GC;                 // the k-step where each forks off the base chain
+    constexpr int GROUP = W < C::COMPUTE_WAVES / 2 ? 0 : 1; // waves w and w + 4 share a SIMD: run them out of phase
+    const int fr = lane & 15, fq = lane >> 4;
+    const int v = fq ^ tlb_sigma(fr);
+    int laddr[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) laddr[k] = fr * N * 8 + ((4 * k) ^ v) * 16;
+    const int pa = 16 * GA + fr, pc = 16 * GC + fr;
+    double xa[NK - SA], xc[NK - SC];
+#pragma unroll
+    for (int s = SA; s < NK; ++s) xa[s - SA] = X[(size_t)pa * N + 8 * (s >> 1) + 2 * fq + (s & 1)];
+#pragma unroll
+    for (int s = SC; s < NK; ++s) xc[s - SC] = X[(size_t)pc * N + 8 * (s >> 1) + 2 * fq + (s & 1)];
+    double* const da = D + (pa >> 1);
+    double* const dc = D + (pc >> 1);
+    constexpr size_t ldr = N;                               // D is m x n row-major
+
+    // acc[0], acc[1]: group GA, tiles 0 and 1; acc[2], acc[3]: group GC
+    auto mfma_stage = [&](size_t f, Acc (&acc)[4]) {
+        const unsigned char* slot = smem + (f % C::NS) * C::STAGE_BYTES;
+        const double* pre = reinterpret_cast<const double*>(smem + C::PRE_OFF + (f & 1) * C::PRE_STAGE) + 4 * fq;
+        auto prefix = [&](int t, int s) {                   // P_s of tile t, this lane's rows fq + 4 r
+            if (s == 0) return Acc{0.0, 0.0, 0.0, 0.0};
+            const double* p = pre + (t * C::NPRE + s / 2 - 1) * 16;
+            const double2 lo = *reinterpret_cast<const double2*>(p), hi = *reinterpret_cast<const double2*>(p + 2);
+            return Acc{lo.x, lo.y, hi.x, hi.y};
+        };
+        acc[0] = prefix(0, SA);
+        acc[1] = prefix(1, SA);
+        acc[2] = prefix(0, SC);
+        acc[3] = prefix(1, SC);
+        wl_static_for<NK / 2 - GA>([&](auto jj) {
+            constexpr int j = GA + decltype(jj)::value;
+            const int off = laddr[j & 3] + (j >> 2) * 256;
+            const double2 a0 = *reinterpret_cast<const double2*>(slot + off);
+            const double2 a1 = *reinterpret_cast<const double2*>(slot + off + 16 * N * 8);
+            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0.x, xa[2 * j - SA], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1.x, xa[2 * j - SA], acc[1], 0, 0, 0);
+            if constexpr (j >= GC) {
+                acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0.x, xc[2 * j - SC], acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1.x, xc[2 * j - SC], acc[3], 0, 0, 0);
+            }
+            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0.y, xa[2 * j + 1 - SA], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1.y, xa[2 * j + 1 - SA], acc[1], 0, 0, 0);
+            if constexpr (j >= GC) {
+                acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0.y, xc[2 * j + 1 - SC], acc[2], 0, 0, 0);
+                acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1.y, xc[2 * j + 1 - SC], acc[3], 0, 0, 0);
+            }
+        });
+    };
+    auto epilogue_tile = [&](const Acc& acc, size_t row0, const unsigned char* bslot, double* yp, bool full) {
+        const double2 b0 = *reinterpret_cast<const double2*>(bslot + 16 * fq);
+        const double2 b1 = *reinterpret_cast<const double2*>(bslot + 64 + 16 * fq);
+        const double y0 = dtanh(acc[0]) - b0.x, y1 = dtanh(acc[1]) - b0.y;
+        const double y2 = dtanh(acc[2]) - b1.x, y3 = dtanh(acc[3]) - b1.y;
+        const double d0 = y0 - lane_pair_swap(y0), d1 = y1 - lane_pair_swap(y1);         // f(x + h e_j) - f(x - h e_j), LS:1041 + 1045
+        const double d2 = y2 - lane_pair_swap(y2), d3 = y3 - lane_pair_swap(y3);
+        const size_t ra = row0 + 2 * fq, rb = row0 + 8 + 2 * fq;
+        if ((fr & 1) == 0) {
+            if (full || ra < m) yp[ra * ldr] = d0;
+            if (full || ra + 1 < m) yp[(ra + 1) * ldr] = d1;
+            if (full || rb < m) yp[rb * ldr] = d2;
+            if (full || rb + 1 < m) yp[(rb + 1) * ldr] = d3;
+        }
+    };
+    auto epilogue = [&](const Acc (&acc)[4], size_t f) {
+        const size_t row0 = (blockIdx.x + f * (size_t)gridDim.x) * C::ROWS;
+        const unsigned char* bs = smem + C::B_OFF + (f % C::NSB) * 256;
+        const bool full = f + 1 < S;                        // only the last stage of a workgroup can be partial
+        epilogue_tile(acc[0], row0, bs, da, full);
+        __builtin_amdgcn_sched_barrier(0);                  // one tile at a time: bounds the live tanh temporaries
+        epilogue_tile(acc[1], row0 + 16, bs + 128, da, full);
+        __builtin_amdgcn_sched_barrier(0);
+        epilogue_tile(acc[2], row0, bs, dc, full);
+        __builtin_amdgcn_sched_barrier(0);
+        epilogue_tile(acc[3], row0 + 16, bs + 128, dc, full);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto barrier = [] {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+    Acc acc[4];
+    barrier();                                              // B_0
+    if constexpr (GROUP == 0) {
+        for (size_t f = 0; f < S; ++f) {
+            barrier();                                      // B_{f + 1}: stage f and its prefixes are in LDS
+            mfma_stage(f, acc);
+            epilogue(acc, f);
+        }
+    } else {
+        barrier();
+        mfma_stage(0, acc);
+        for (size_t f = 1; f < S; ++f) {
+            barrier();
+            epilogue(acc, f - 1);
+            mfma_stage(f, acc);
+        }
+        epilogue(acc, S - 1);
+    }
+}
+
 template <int NK, bool RM = false, bool DIFF = false>
 __global__ __launch_bounds__(TlbCfg<NK>::THREADS) void k_tanh_linear_batched_dma(const double* __restrict__ A,
                                                                                   const double* __restrict__ b,
                                                                                   const double* __restrict__ X,
                                                                                   double* __restrict__ Y, size_t m, int P,
-                                                                                  int read_a_once)
+                                                                                  int mode)
 {
     using C = TlbCfg<NK>;
     extern __shared__ __attribute__((aligned(16))) unsigned char tlb_smem[];
@@ -560,9 +781,21 @@ __global__ __launch_bounds__(TlbCfg<NK>::THREADS) void k_tanh_linear_batched_dma
     // the finite-difference points of fbRowMajorDiff, on request: A is read once (2.1 instead of 3.1 GB per call at n = 128,
     // and 3 % SLOWER: the kernel is MFMA-bound and the operand selects are extra VALU work -- not the default)
     // (n = 256: six chunks of per-chunk state next to 128 VGPRs of fragments spill -- measured 2x slower; not offered there)
-    const bool once = DIFF && read_a_once && NK <= 32 && P == 2 * C::N;
+    // mode: 0 = the chunked sweep (tlb_compute), 1 = read A once (tlb_compute_once), 2 = prefix forking (n = 128) when X passes
+    // tlb_fork_vote, else the chunked sweep
+    const bool once = DIFF && mode == 1 && NK <= 32 && P == 2 * C::N;
     const size_t F = once ? S : S * (size_t)nchunks;            // flat (chunk, stage) sequence: the ring never drains
     if (S == 0) return;
+    if constexpr (DIFF && C::FORK) {
+        if (mode == 2 && P == 2 * C::N && tlb_fork_vote<NK>(X, tlb_smem, lane, wave)) {       // (workgroup-uniform)
+            if (wave == C::COMPUTE_WAVES) tlb_fork_loader<NK, 0>(A, b, X, m, tlb_smem, lane, S);
+            else if (wave == C::COMPUTE_WAVES + 1) tlb_fork_loader<NK, 1>(A, b, X, m, tlb_smem, lane, S);
+            else wl_static_for<C::COMPUTE_WAVES>([&](auto ww) {
+                if (wave == decltype(ww)::value) tlb_fork_compute<NK, decltype(ww)::value>(X, Y, m, tlb_smem, lane, S);
+            });
+            return;
+        }
+    }
     if (!C::SELF && wave == C::COMPUTE_WAVES) tlb_loader<NK, 0>(A, b, m, tlb_smem, lane, S, F);
     else if (!C::SELF && wave == C::COMPUTE_WAVES + 1) tlb_loader<NK, 1>(A, b, m, tlb_smem, lane, S, F);
     else if (DIFF && once) {
@@ -588,17 +821,18 @@ __global__ __launch_bounds__(TlbCfg<NK>::THREADS) void k_tanh_linear_batched_dma
 }
 
 template <int NK, bool RM = false, bool DIFF = false>
-bool launch_tlb_dma(const double* A, const double* b, const double* X, double* Y, size_t m, int P, hipStream_t s, int read_a_once = 0)
+bool launch_tlb_dma(const double* A, const double* b, const double* X, double* Y, size_t m, int P, hipStream_t s, int mode = 0)
 {
     using C = TlbCfg<NK>;
+    constexpr int lds = DIFF && C::FORK ? C::FORK_LDS_BYTES : C::LDS_BYTES;
     static bool attr_ok = [] {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(k_tanh_linear_batched_dma<NK, RM, DIFF>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) == hipSuccess;
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
     }();
     if (!attr_ok) return false;
     const size_t Stot = (m + C::ROWS - 1) / C::ROWS;
     const unsigned grid = (unsigned)(Stot < 256 ? Stot : 256);
-    hipLaunchKernelGGL((k_tanh_linear_batched_dma<NK, RM, DIFF>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, s, A, b, X, Y, m, P, read_a_once);
+    hipLaunchKernelGGL((k_tanh_linear_batched_dma<NK, RM, DIFF>), dim3(grid), dim3(C::THREADS), lds, s, A, b, X, Y, m, P, mode);
     return true;
 }
 
@@ -728,13 +962,14 @@ __global__ __launch_bounds__(256) void k_tanh_linear_batched_wide(const double* 
 }  // namespace
 
 void launch_tanh_linear_batched_diff(const double* A, const double* b, const double* X, double* D, size_t m, int n, int P,
-                                     hipStream_t s, int read_a_once)
+                                     hipStream_t s, int read_a_once, bool dense)
 {
     if (m >= 32 && P % 16 == 0) {                          // whole 16-point MFMA tiles: no clamped lanes, whose pairs would store zeros
-        if (n == 256 && launch_tlb_dma<64, true, true>(A, b, X, D, m, P, s, read_a_once)) return;
-        if (n == 128 && launch_tlb_dma<32, true, true>(A, b, X, D, m, P, s, read_a_once)) return;
-        if (n == 64 && launch_tlb_dma<16, true, true>(A, b, X, D, m, P, s, read_a_once)) return;
-        if (n == 32 && launch_tlb_dma<8, true, true>(A, b, X, D, m, P, s, read_a_once)) return;
+        const int mode = read_a_once ? 1 : dense ? 0 : 2;
+        if (n == 256 && launch_tlb_dma<64, true, true>(A, b, X, D, m, P, s, mode)) return;
+        if (n == 128 && launch_tlb_dma<32, true, true>(A, b, X, D, m, P, s, mode)) return;
+        if (n == 64 && launch_tlb_dma<16, true, true>(A, b, X, D, m, P, s, mode)) return;
+        if (n == 32 && launch_tlb_dma<8, true, true>(A, b, X, D, m, P, s, mode)) return;
     }
     if (n > 256 && n % 8 == 0 && P % 2 == 0 && m > 0) {
         const size_t nt = (m + 63) / 64;
