@@ -400,7 +400,8 @@ int mir_optimize_least_squares_batched_s(const mir_least_squares_settings_s* set
  * `count` records in place; enqueued on options->stream, no synchronisation -- see mir_lsq_batched_options.basis for the one
  * exception): what bench.py --config cfg5 times. Problems whose step reaches a finite bound come back with status -100
  * (MIR_LSQ_BATCHED_NEEDS_GENERAL): the host entry above completes those with the general solver, this one leaves that to
- * the caller. Returns 0 when the launch succeeded.
+ * the caller. Returns 0 when the launch succeeded. The kernel entry (_s and _d alike) checks its arguments (-1: model id and
+ * options, then the pointers and t_stride) before it looks for a device (-2).
  * A caller with a residual model of its own -- the reference takes an arbitrary f, least_squares.d:73-80 -- compiles the
  * same kernel for it from include/mir_optim_amd_batched.hpp (launch_batched<Model>); the three built-in models are
  * instances of that template. */
@@ -414,8 +415,7 @@ int mir_lsq_batched_kernel_s(const mir_least_squares_settings_s* settings, size_
  * formulas, evaluated in double), contract and return codes as their _s twins; every array is double, the records are the _d
  * ones (32 bytes, written in place by the kernel entry), and a basis table passed in the options holds doubles. A problem
  * needs (n + 2) m doubles of LDS: m <= 2041 at n = 8, 4083 at n = 3. Problems whose step reaches a finite bound are completed
- * by mir_optimize_least_squares_gpu_d in the host entry, and come back with status -100 from the kernel entry. The kernel entry
- * checks its arguments (-1) before it looks for a device. */
+ * by mir_optimize_least_squares_gpu_d in the host entry, and come back with status -100 from the kernel entry. */
 int mir_optimize_least_squares_batched_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
                                          double* x, const double* lower, const double* upper,
                                          const double* t, size_t t_stride, const double* data,

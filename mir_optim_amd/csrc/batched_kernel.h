@@ -118,12 +118,6 @@ struct ModelExpDecayPad8 {
         return __builtin_fmaf(x[7], t, v);
     }
 };
-// the compiled-in models of mir_optimize_least_squares_batched_s by their MIR_LSQ_MODEL_* id
-template <int ID> struct BuiltinModel;
-template <> struct BuiltinModel<kModelExpDecay> { using type = ModelExpDecay; };
-template <> struct BuiltinModel<kModelExp3Affine> { using type = ModelExp3Affine; };
-template <> struct BuiltinModel<kModelExpDecayPad8> { using type = ModelExpDecayPad8; };
-
 // ---- the same three models in DOUBLE (mir_optimize_least_squares_batched_d: same ids, same formulas). Device exp / sin / cos
 // of the type; no host twin reproduces their bits, and none is needed: the f64 path is compared with the f64 oracle to tolerance.
 struct ModelExpDecayD {
@@ -153,6 +147,14 @@ struct ModelExpDecayPad8D {     // the basis table holds doubles
         return x[0] * exp(-t * x[1]) + x[2] + x[3] * b[0] + x[4] * b[1] + x[5] * b[2] + x[6] * b[3] + x[7] * t;
     }
 };
+// the compiled-in models of mir_optimize_least_squares_batched_s / _d by their MIR_LSQ_MODEL_* id and value type
+template <int ID, class T> struct BuiltinModel;
+template <> struct BuiltinModel<kModelExpDecay, float> { using type = ModelExpDecay; };
+template <> struct BuiltinModel<kModelExp3Affine, float> { using type = ModelExp3Affine; };
+template <> struct BuiltinModel<kModelExpDecayPad8, float> { using type = ModelExpDecayPad8; };
+template <> struct BuiltinModel<kModelExpDecay, double> { using type = ModelExpDecayD; };
+template <> struct BuiltinModel<kModelExp3Affine, double> { using type = ModelExp3AffineD; };
+template <> struct BuiltinModel<kModelExpDecayPad8, double> { using type = ModelExpDecayPad8D; };
 
 // T = float: the layout of mir_least_squares_result_s (24 bytes); T = double: of mir_least_squares_result_d (32 bytes)
 template <class T> struct BatchedResult { int32_t status; uint32_t iterations, fCalls, gCalls; T residual, lambda; };

@@ -12,7 +12,8 @@
 //   solver_jacobian.hip  Jacobian refresh: finite differences (device / host callbacks, LS:1018-1049), analytic g,
 //                        Broyden passes, J^T J / J^T y (LS:999-1065)
 //   launch_*.hip         the translation units that instantiate the kernels (jtj_plan.h, broyden_launch.h, solve_launch.h)
-//   batched.hip          one-wavefront-per-problem batched fits;  comm.hip  row-shard communicators;  unit_entries.hip
+//   batched.hip, batched_d.hip   one-wavefront-per-problem batched fits in float / double: the two instances of batched_host.h
+//   comm.hip             row-shard communicators;  unit_entries.hip
 //
 // There is NO CPU fallback: without a usable HIP device the solve entry points print a diagnostic and return
 // status = numericError.
@@ -82,6 +83,19 @@ template <> struct Abi<float> {
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// settings validation of LS:934-943 (after badGuess / badBounds there): the mir_ls_bad* code of the first check that fails, or 0
+template <typename Settings>
+int bad_settings(const Settings* S)
+{
+    using T = decltype(Settings::minStepQuality);
+    if (!(0 <= S->minStepQuality && S->minStepQuality < 1)) return mir_ls_badMinStepQuality;
+    if (!(0 <= S->goodStepQuality && S->goodStepQuality <= 1)) return mir_ls_badGoodStepQuality;
+    if (!(S->minStepQuality < S->goodStepQuality)) return mir_ls_badStepQuality;
+    if (!(1 <= S->lambdaIncrease && S->lambdaIncrease <= std::sqrt(Lim<T>::max))) return mir_ls_badLambdaParams;
+    if (!(std::sqrt(Lim<T>::min_normal) <= S->lambdaDecrease && S->lambdaDecrease <= 1)) return mir_ls_badLambdaParams;
+    return 0;
+}
 
 // polite busy-wait step: the architecture's spin hint where there is one
 inline void cpu_relax()

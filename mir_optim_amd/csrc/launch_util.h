@@ -37,5 +37,4 @@ inline hipError_t ensure_dyn_lds(const void* fn, size_t bytes, std::atomic<uint6
     namespace mirlsq { void preload_##name() { hipLaunchKernelGGL(k_preload_##name, dim3(1), dim3(1), 0, nullptr); } }
 namespace mirlsq {
 void preload_jtj(); void preload_broyden(); void preload_solve_d(); void preload_solve_s(); void preload_loop(); void preload_jacobian();
-void preload_batched();
 }

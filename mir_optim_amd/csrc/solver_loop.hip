@@ -442,11 +442,7 @@ typename Solver<T>::Result Solver<T>::run()
         for (uint32_t i = 0; i < n; ++i) if (!(-Lim<T>::inf() < xh[i] && xh[i] < Lim<T>::inf())) finite = false;
         if (m == 0 || n == 0 || !finite) { ret.status = mir_ls_badGuess; return ret; }
         for (uint32_t i = 0; i < n; ++i) if (!(lh[i] <= xh[i]) || !(xh[i] <= uh[i])) { ret.status = mir_ls_badBounds; return ret; }
-        if (!(0 <= S->minStepQuality && S->minStepQuality < 1)) { ret.status = mir_ls_badMinStepQuality; return ret; }
-        if (!(0 <= S->goodStepQuality && S->goodStepQuality <= 1)) { ret.status = mir_ls_badGoodStepQuality; return ret; }
-        if (!(S->minStepQuality < S->goodStepQuality)) { ret.status = mir_ls_badStepQuality; return ret; }
-        if (!(1 <= S->lambdaIncrease && S->lambdaIncrease <= std::sqrt(Lim<T>::max))) { ret.status = mir_ls_badLambdaParams; return ret; }
-        if (!(std::sqrt(Lim<T>::min_normal) <= S->lambdaDecrease && S->lambdaDecrease <= 1)) { ret.status = mir_ls_badLambdaParams; return ret; }
+        if (const int bad = bad_settings(S)) { ret.status = bad; return ret; }
     }
     if (!device_available()) return ret;
     if (!setup()) { teardown(); return ret; }

@@ -101,7 +101,7 @@ static Result run(long iters, bool null_stream, int mode, size_t table_bytes)
     return Result{iters, h[0], h[1], seen.size()};
 }
 
-// mode 3: the host entry's exact sequence in round 4 (batched.hip + launch_batched): hipMalloc(inputs) -> blocking H2D copies ->
+// mode 3: the host entry's exact sequence in round 4 (batched_host.h + launch_batched): hipMalloc(inputs) -> blocking H2D copies ->
 // hipMallocAsync(table, null stream) -> table kernel -> long consumer reading BOTH -> hipFreeAsync -> hipDeviceSynchronize ->
 // D2H copy -> hipFree(inputs); count = 256 problems of m = 512: 1 MB of inputs, a 2 MB table.
 static Result run_library_sequence(long iters)

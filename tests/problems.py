@@ -21,6 +21,13 @@ def splitmix64_uniform(seed, count, offset=0):
     return (z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
 
 
+# one bad value for each of the five settings checks of least_squares.d:934-943, in their order, with the status the
+# reference answers: every entry that takes a settings record (general and batched, float and double) reports the same code
+BAD_SETTINGS = [({"minStepQuality": 1.0}, "badMinStepQuality"), ({"goodStepQuality": 1.5}, "badGoodStepQuality"),
+                ({"minStepQuality": 0.5, "goodStepQuality": 0.5}, "badStepQuality"),
+                ({"lambdaIncrease": 0.5}, "badLambdaParams"), ({"lambdaDecrease": 2.0}, "badLambdaParams")]
+
+
 # ---------------------------------------------------------------- reference unittests (inputs only)
 def t1():  # LS:218-245
     def f(x, y):

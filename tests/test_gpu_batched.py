@@ -151,6 +151,26 @@ def test_batched_validation_codes():
     assert all(r.status == M.LeastSquaresStatus.badMinStepQuality for r in res)
 
 
+@pytest.mark.parametrize("fields, code", P.BAD_SETTINGS)
+def test_settings_validation_codes_agree_across_the_general_and_batched_entries(fields, code):
+    """One bad value for each of the five settings checks (least_squares.d:934-943): mir_optimize_least_squares_{s,d} and
+    mir_optimize_least_squares_batched_{s,d} answer the same code, the reference's, on every problem."""
+    t, data, truth, x0 = make_exp_decay(4)
+
+    def f(x, y):
+        y[:] = x
+    codes = []
+    for dtype in (np.float32, np.float64):
+        s = M.LeastSquaresSettings(dtype)
+        for name, value in fields.items():
+            setattr(s, name, value)
+        res, _ = M.optimizeLeastSquares(f, 2, [0.5, 0.5], settings=s, dtype=dtype)
+        codes.append(int(res.status))
+        res, _ = M.optimizeLeastSquaresBatched(M.MODEL_EXP_DECAY, x0, t, data, settings=s, dtype=dtype)
+        codes += [int(r.status) for r in res]
+    assert codes == [int(M.LeastSquaresStatus[code])] * len(codes), codes
+
+
 def test_cfg5_pad8_all_4096_problems_match_the_float_oracle(oracle):
     """BASELINE cfg 5 as specified: 4096 independent fits, m = 512, n = 8, fp32, jacobianEpsilon = 2^-11, the
     well-conditioned exponential-decay family padded to n = 8, per-problem seed 100 + id. EVERY problem is compared with
