@@ -284,6 +284,8 @@ def lib():
         L.mir_lsq_batched_kernel_s.restype = C.c_int
         L.mir_lsq_batched_kernel_s.argtypes = [C.POINTER(_Ss), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, sz, C.c_void_p, C.c_void_p, C.POINTER(BatchedOptions)]
+        L.mir_lsq_jtj_plan.restype = C.c_int
+        L.mir_lsq_jtj_plan.argtypes = [sz, sz, sz, C.c_int, C.c_int, C.c_int, C.POINTER(sz * 10)]
         L.mir_lsq_selftest_reductions.restype = C.c_int
         L.mir_lsq_selftest_reductions.argtypes = [C.c_int, C.POINTER(C.c_int * 4)]
         L.mir_lsq_batched_posvx_s.restype = C.c_int
@@ -696,6 +698,22 @@ def jtj(J, y, y_old=None, dx=None, dtype=np.float64):
     for b in (dJ, dy, dyo, ddx, dJJ, dJy):
         b.free()
     return out
+
+
+JTJ_OPS = ("plain", "rewrite", "fd", "fd_diff")
+JTJ_FAMILIES = ("none", "stream", "fdp", "pc32", "ring8", "fdp8", "wide")
+
+
+def jtj_plan(elem_size, m, n, num_cu, op, aligned=True):
+    """The kernel the J^T J entries launch for a shape and an operation of JTJ_OPS (mir_lsq_jtj_plan; host code, no GPU).
+    Returns a dict: family (of JTJ_FAMILIES), ncb, flat, grid, jobs, lds, slabs, slab_len, reduce_ncb, workspace_slab_elems."""
+    out = (C.c_size_t * 10)()
+    rc = lib().mir_lsq_jtj_plan(elem_size, m, n, num_cu, JTJ_OPS.index(op), int(bool(aligned)), C.byref(out))
+    if rc != 0:
+        raise ValueError(f"mir_lsq_jtj_plan: {rc}")
+    d = dict(zip(("family", "ncb", "flat", "grid", "jobs", "lds", "slabs", "slab_len", "reduce_ncb", "workspace_slab_elems"), map(int, out)))
+    d["family"] = JTJ_FAMILIES[d["family"]]
+    return d
 
 
 def fd_jtj(Yrm, twh, y, diff=False):

@@ -1,17 +1,25 @@
-// jtj_plan.h -- host view of the J^T J kernels: their argument block, which kernel runs for a shape (JtjPlan) and the
-// launch entry points (defined in launch_jtj.hip, the only translation unit that instantiates the kernels).
+// jtj_plan.h -- host view of the J^T J kernels: their argument block, which kernel runs for a shape and an operation
+// (jtj_plan<T>(), the ONE place that decides it) and the launch entry point (defined in launch_jtj.hip, the only translation
+// unit that instantiates the kernels). LS = source/mir/optim/least_squares.d of the reference.
 //
-// Kernel by shape, LS = /root/reference/source/mir/optim/least_squares.d:
-//   f64, n <= 128               k_jtj_fdp<NCB, true>    finite-difference panel -> J, J^T J, J^T y   (LS:1041-1047, 1052, 1065)
-//   f64, n <= 128               k_jtj_fdp<NCB, false>   J^T J + J^T y of a given J (odd n: 8-byte loads) (LS:1052, 1065)
-//   f64, 128 < n <= 256 (any n, m)             k_jtj_fdp8   finite-difference panel -> J, J^T J, J^T y
-//   f64, 128 < n <= 256 (n % 16 == 0, m even)  k_jtj8   eight-wave LDS-DMA ring, J^T J of a given J
-//   f64, 128 < n <= 256, the other n and m     k_jtj_fdp8<., false, true>   J^T J of a given J (flat buffer loads)
-//   f32, n <= 128, n % 4 == 0   k_jtj_pc32
-//   everything else             k_jtj (n <= 128, register streaming) / k_jtj_wide (any n: 64-column tile pairs)
-// MIR_LSQ_VARIANT_BROYDEN_REWRITE runs the Broyden pass as the literal restatement of LS:1003-1006 (J rewritten):
-// k_jtj<., ., true>, k_jtj8 with its Broyden flag, k_broyden_wide / k_broyden_rows in front of the tile-pair jobs.
+// Operations (JtjOp): plain = J^T J + J^T y of a given J (LS:1052, 1065); rewrite = the same behind the Broyden update as the
+// literal restatement of LS:1003-1006, J rewritten (MIR_LSQ_VARIANT_BROYDEN_REWRITE); fd = finite-difference pair panel -> J,
+// J^T J, J^T y (LS:1041-1047 fused); fd_diff = the same from the difference panel. Kernel by shape and operation:
+//   shape                                      plain               rewrite               fd            fd_diff
+//   f64, n <= 128                              fdp <., false> (1)  stream <., ., true>   fdp <., true> fdp <., false, true> (1)
+//   f64, 128 < n <= 256, n % 16 == 0, m even   ring8               ring8, Broyden flag   fdp8          fdp8 <., true> (2)
+//   f64, 128 < n <= 256, the other n and m     fdp8 <., false, true>   wide (3)          fdp8          fdp8 <., true> (2)
+//   f32, n <= 128, n % 4 == 0                  pc32 (4)            stream <., ., true>   none          none
+//   f32, n <= 128, n % 4 != 0                  stream              stream <., ., true>   none          none
+//   n > 256; f32, n > 128                      wide                wide (3)              none          none
+// stream = k_jtj (register streaming), fdp = k_jtj_fdp, pc32 = k_jtj_pc32, ring8 = k_jtj8 (eight-wave LDS-DMA ring),
+// fdp8 = k_jtj_fdp8 (compiled for n rounded up to a multiple of 32), wide = k_jtj_wide (64-column tile-pair jobs, any n).
+// (1) the flat producer (8-byte aligned loads) for odd n, for the difference panel with n % 16 != 0 and -- decided at the launch,
+//     jtj_resolve -- for a J that is not 16-byte aligned.  (2) n % 64 == 0 only (n = 192, 256), else none.
+// (3) k_broyden_wide (n <= 256) / k_broyden_rows in front.  (4) a J that is not 16-byte aligned: stream_fallback (jtj_resolve).
 #pragma once
+
+#include <initializer_list>
 
 #include "../../include/mir_optim_amd.h"
 #include "common.h"
@@ -49,8 +57,12 @@ __host__ __device__ constexpr int jtj_roles_rt(int ncb, int regs_per_block)
 // tile-pair jobs (jtj_wide.h)
 constexpr int kWideTile = 4;                                             // blocks per tile side
 constexpr int kWideSlabLen = (kWideTile * kWideTile * 4 + kWideTile) * kWave;   // 16 blocks x 4 regs + 4 jy regs, x 64 lanes
-// dynamic LDS of k_jtj8<NCB> (jtj_ring8.h: four 16-row stages + the y / y_old rings; launch_jtj.hip asserts the match)
-constexpr size_t jtj8_lds_bytes(int ncb) { return (size_t)4 * 16 * 16 * ncb * 8 + 2 * 4 * 1024; }
+// dynamic LDS of the kernels that size it at compile time (launch_jtj.hip asserts the match with the kernels' Cfg structs)
+constexpr size_t jtj8_lds_bytes(int ncb) { return (size_t)4 * 16 * 16 * ncb * 8 + 2 * 4 * 1024; }   // four 16-row stages + the y / y_old rings
+constexpr size_t jtj_fdp_lds_bytes(int ncb, bool fd) { return (size_t)2 * (fd && ncb % 4 ? 16 : 32) * (16 * ncb + 1) * 8; }   // two stages of 16 / 32 rows + y
+constexpr size_t jtj_fdp_flat_bytes(int ncb) { return (size_t)16 * ncb * 8; }                       // + the 1 / twh table of the flat producer
+constexpr size_t jtj_fdp8_lds_bytes(int ncb) { return (size_t)2 * 16 * (16 * ncb + 17) * 8; }
+constexpr size_t jtj_pc32_lds_bytes(int ncb) { return (size_t)2 * 64 * (16 * ncb + 17) * 4; }
 
 // Where the slab reduction may put its result besides `packed`: the full symmetric J^T J and J^T y (the work of
 // k_unpack_grad; max |J^T y| is taken by the solve kernel), when no all-reduce of `packed` sits in between. All null: `packed` only.
@@ -59,126 +71,125 @@ struct JtjUnpack {
     T* JJ = nullptr; T* Jy = nullptr;
 };
 
-struct JtjPlan {
-    int ncb = 0;
-    int nblk = 0;
+enum class JtjKernel { none, stream, fdp, pc32, ring8, fdp8, wide };   // none: the shape is not covered for this operation
+enum class JtjOp { plain, rewrite, fd, fd_diff };
+struct JtjLaunch {
+    JtjKernel kernel = JtjKernel::none;
+    int ncb = 0;        // 16-column blocks the kernel is compiled for = the layout of its slabs (fdp8: even, >= ceil(n / 16)); wide: ceil(n / 16)
+    int nblk = 0;       // grid.x = slabs per job
+    int njobs = 1;      // grid.y (wide: tile pairs)
     int slab_len = 0;
-    size_t lds = 0;
-    bool wide = false;      // n > 128 and not ring8: 64-column tile-pair jobs (jtj_wide.h), any n
-    bool ring8 = false;     // 128 < n <= 256, f64, n % 16 == 0, m even: eight-wave LDS-DMA ring (jtj_ring8.h)
-    bool fdp = false;       // f64, n <= 128, any m: producer / consumer kernel (jtj_fdp.h) for the finite-difference J^T J
-    bool fdp_plain = false; // ... and for the plain J^T J / the difference panel (odd n: the element-wise producer)
-    bool fdp8 = false;      // f64, 128 < n <= 256, any n and m: eight producer + consumer waves (jtj_fdp8.h), FD J^T J only
-    int fdp8_nblk = 0, fdp8_slab_len = 0, fdp8_ncb = 0;     // fdp8_ncb: the even block count the kernel is compiled for (>= ncb)
-    bool pc32 = false;      // f32, n <= 128, n % 4 == 0, any m: producer / consumer kernel on v_mfma_f32_16x16x4 (jtj_pc32.h), plain J^T J
-    int pc32_nblk = 0;
-    int njobs = 1;
-    int stream_nblk = 0;    // n <= 128: grid and dynamic LDS of the register-streaming kernel k_jtj
-    size_t stream_lds = 0;
+    size_t lds = 0;     // dynamic LDS
+    bool flat = false;  // fdp: the flat producer
+};
+struct JtjPlan {
+    JtjLaunch plain, rewrite, fd, fd_diff;
+    JtjLaunch stream_fallback;      // what `plain` becomes when J is not 16-byte aligned (pc32 only; else none)
+    const JtjLaunch& of(JtjOp op) const { return op == JtjOp::plain ? plain : (op == JtjOp::rewrite ? rewrite : (op == JtjOp::fd ? fd : fd_diff)); }
 };
 
 template <typename T>
 JtjPlan jtj_plan(size_t m, int n, int num_cu)
 {
+    constexpr bool f64 = sizeof(T) == 8;
+    using K = JtjKernel;
+    const int ncb = (n + 15) / 16;
+    auto slab_len = [](int c) { return (c * (c + 1) / 2 * 4 + c) * kWave; };
+    // grid: about 8 (`per`) units of `unit` rows a workgroup, at least one workgroup, at most `cap`
+    auto grid = [m](size_t unit, size_t per, size_t cap) {
+        const size_t want = ((m + unit - 1) / unit + per - 1) / per;
+        return (int)(want < cap ? (want ? want : 1) : cap);
+    };
+    auto wide = [&] {           // any n: 64-column tile pairs; at least ~8 four-row groups per wave, four workgroups per CU over all jobs
+        const int nt = (ncb + kWideTile - 1) / kWideTile, njobs = nt * (nt + 1) / 2;
+        const size_t cap = (size_t)num_cu * 4 / njobs;
+        return JtjLaunch{K::wide, ncb, grid(4, 4 * 8, cap < 1 ? 1 : cap), njobs, kWideSlabLen, (size_t)2 * kWideSlabLen * sizeof(T)};
+    };
     JtjPlan p;
-    p.ncb = (n + 15) / 16;
-    const int nacc = p.ncb * (p.ncb + 1) / 2;
-    p.slab_len = (nacc * 4 + p.ncb) * kWave;
-    if (sizeof(T) == 8 && n > 128 && n <= 256) {
-        // any n: the kernel is compiled for n rounded up to a multiple of 32 (an even number of 16-column blocks)
-        p.fdp8 = true;
-        p.fdp8_ncb = 2 * ((n + 31) / 32);
-        const size_t stot = (m + 15) / 16;
-        const size_t want = (stot + 7) / 8;                    // at least ~8 stages per workgroup
-        p.fdp8_nblk = (int)(want < (size_t)num_cu ? (want ? want : 1) : (size_t)num_cu);   // one workgroup per CU
-        p.fdp8_slab_len = (p.fdp8_ncb * (p.fdp8_ncb + 1) / 2 * 4 + p.fdp8_ncb) * kWave;
-    }
-    if (sizeof(T) == 8 && n > 128 && n <= 256 && n % 16 == 0 && m % 2 == 0) {
-        p.ring8 = true;
-        p.lds = jtj8_lds_bytes(p.ncb);
-        const size_t stot = (m + 15) / 16;
-        size_t want = (stot + 7) / 8;                          // at least ~8 stages per workgroup
-        p.nblk = (int)(want < (size_t)num_cu ? (want ? want : 1) : (size_t)num_cu);   // one workgroup per CU
+    if (n > 256 || (!f64 && n > 128)) {
+        p.plain = p.rewrite = wide();
         return p;
     }
     if (n > 128) {
-        p.wide = true;
-        const int nt = (p.ncb + kWideTile - 1) / kWideTile;
-        p.njobs = nt * (nt + 1) / 2;
-        p.slab_len = kWideSlabLen;
-        p.lds = (size_t)2 * kWideSlabLen * sizeof(T);
-        const size_t G = (m + 3) / 4;
-        size_t want = (G + 4 * 8 - 1) / (4 * 8);
-        size_t cap = (size_t)num_cu * 4 / p.njobs;
-        if (cap < 1) cap = 1;
-        p.nblk = (int)(want < cap ? (want ? want : 1) : cap);
+        // fdp8, any n: compiled for an even number of blocks; ring8 and fdp8: 16-row stages, at least ~8 a workgroup, one workgroup per CU
+        const int ncb8 = 2 * ((n + 31) / 32), nblk = grid(16, 8, (size_t)num_cu);
+        p.fd = {K::fdp8, ncb8, nblk, 1, slab_len(ncb8), jtj_fdp8_lds_bytes(ncb8)};
+        if (n % 64 == 0) p.fd_diff = p.fd;      // two columns per 16-byte load: whole loads per row
+        if (n % 16 == 0 && m % 2 == 0) p.plain = p.rewrite = {K::ring8, ncb, nblk, 1, slab_len(ncb), jtj8_lds_bytes(ncb)};
+        else { p.plain = p.fd; p.rewrite = wide(); }
         return p;
     }
-    if (sizeof(T) == 4 && n <= 128 && n % 4 == 0) {
-        p.pc32 = true;
-        const size_t stot = (m + 63) / 64;                     // 64-row stages
-        const size_t want = (stot + 3) / 4;                    // at least ~4 stages per workgroup
-        const size_t cap = (size_t)num_cu * 2;
-        p.pc32_nblk = (int)(want < cap ? (want ? want : 1) : cap);
-    }
-    p.fdp = sizeof(T) == 8 && n <= 128;
-    p.fdp_plain = p.fdp;                // any n: odd n (rows not on 16-byte boundaries) takes the element-wise producer
-    // the register-streaming kernel k_jtj: f64 with odd n, f32 with n % 4 != 0, and every Broyden REWRITE at n <= 128
     {
-        const int rpb = 4 * (int)(sizeof(T) / 4);
-        const int roles = jtj_roles_rt(p.ncb, rpb);
-        p.stream_lds = (size_t)(roles == 4 ? 0 : (roles == 2 ? 1 : 2)) * p.slab_len * sizeof(T);
+        const int rpb = 4 * (int)(sizeof(T) / 4), nacc = ncb * (ncb + 1) / 2;
+        const int roles = jtj_roles_rt(ncb, rpb);
+        const size_t lds = (size_t)(roles == 4 ? 0 : (roles == 2 ? 1 : 2)) * slab_len(ncb) * sizeof(T);
         // workgroups per CU: LDS- and register-limited (one workgroup = one wave per SIMD)
-        int per_cu = p.stream_lds ? (int)((160 * 1024) / p.stream_lds) : 8;
+        int per_cu = lds ? (int)((160 * 1024) / lds) : 8;
         const int reg_waves = (nacc * rpb / roles > 40) ? 2 : 4;   // matches jtj_min_waves
         if (per_cu > reg_waves) per_cu = reg_waves;
         if (per_cu < 1) per_cu = 1;
-        const size_t G = (m + 3) / 4;
-        const size_t slots_per_blk = kJtjWaves / roles;
-        size_t want = (G + slots_per_blk * 8 - 1) / (slots_per_blk * 8);     // at least ~8 row groups per wave
-        size_t cap = (size_t)num_cu * per_cu;
-        p.stream_nblk = (int)(want < cap ? (want ? want : 1) : cap);
+        // at least ~8 four-row groups per wave
+        p.rewrite = {K::stream, ncb, grid(4, (size_t)(kJtjWaves / roles) * 8, (size_t)num_cu * per_cu), 1, slab_len(ncb), lds};
     }
-    p.nblk = p.stream_nblk;         // k_jtj_fdp runs on the same grid, except:
-    if (sizeof(T) == 8 && n % 16 == 0 && n <= 128 && m % 2 == 0) {
-        // the shapes k_jtj_fdp was tuned on: two workgroups per CU, at least ~8 blocks of rs rows each (the partition of the
-        // retired LDS-DMA ring kernel; kept: it fixes the summation order of the slabs)
-        const int rs = p.ncb <= 4 ? 32 : (p.ncb == 5 ? 24 : (p.ncb == 6 ? 20 : 16));
-        const size_t stot = (m + rs - 1) / rs;
-        size_t want = (stot + 7) / 8;
-        const size_t cap = (size_t)num_cu * 2;
-        p.nblk = (int)(want < cap ? (want ? want : 1) : cap);
+    if (f64) {
+        p.fd = {K::fdp, ncb, p.rewrite.nblk, 1, slab_len(ncb), jtj_fdp_lds_bytes(ncb, true)};   // on k_jtj's grid, except:
+        if (n % 16 == 0 && m % 2 == 0) {
+            // the shapes k_jtj_fdp was tuned on: two workgroups per CU, at least ~8 blocks of rs rows each (the partition of the
+            // retired LDS-DMA ring kernel; kept: it fixes the summation order of the slabs)
+            const int rs = ncb <= 4 ? 32 : (ncb == 5 ? 24 : (ncb == 6 ? 20 : 16));
+            p.fd.nblk = grid(rs, 8, (size_t)num_cu * 2);
+        }
+        p.plain = p.fd;
+        p.plain.lds = jtj_fdp_lds_bytes(ncb, false);
+        p.fd_diff = p.plain;
+        // rows not on 16-byte boundaries; the difference panel also when a row of J does not start on a 128-byte boundary: the
+        // flat producer writes J back in memory order instead of the consumers' row segments. (On the 128-byte grid the consumers'
+        // write-back is the faster one: 0.428 against 0.448 ms at m = 1e6, n = 128; 0.189 against 0.196 at n = 64.)
+        p.plain.flat = n % 2 != 0;
+        p.fd_diff.flat = n % 16 != 0;
+        for (JtjLaunch* l : {&p.plain, &p.fd_diff}) if (l->flat) l->lds += jtj_fdp_flat_bytes(ncb);
+    } else if (n % 4 == 0) {
+        // 64-row stages, at least ~4 a workgroup, two workgroups per CU
+        p.plain = {K::pc32, ncb, grid(64, 4, (size_t)num_cu * 2), 1, slab_len(ncb), jtj_pc32_lds_bytes(ncb)};
+        p.stream_fallback = p.rewrite;
+    } else {
+        p.plain = p.rewrite;
     }
     return p;
 }
 
-// slab elements the J^T J kernels of a plan may write
-inline size_t jtj_slab_elems(const JtjPlan& a)
+// The two choices that depend on the POINTER, made at the launch: k_jtj_pc32 reads J with 16-byte loads of four floats and
+// k_jtj_fdp's strided producer with 16-byte loads of two doubles; a J that is not 16-byte aligned (an offset view handed to a
+// unit entry) takes the register-streaming kernel / the flat producer (the pair panel of `fd` is the library's own buffer).
+inline JtjLaunch jtj_resolve(const JtjPlan& p, JtjOp op, bool aligned16)
 {
-    size_t e = (size_t)a.nblk * a.njobs * a.slab_len;
-    const size_t ec = (size_t)a.fdp8_nblk * a.fdp8_slab_len, ed = (size_t)a.pc32_nblk * a.slab_len;
-    const size_t ef = (size_t)a.stream_nblk * a.slab_len;
-    e = e > ec ? e : ec;
-    e = e > ed ? e : ed;
-    return e > ef ? e : ef;
+    JtjLaunch l = p.of(op);
+    if (aligned16) return l;
+    if (l.kernel == JtjKernel::pc32) return p.stream_fallback;
+    if (l.kernel == JtjKernel::fdp && op != JtjOp::fd && !l.flat) { l.flat = true; l.lds += jtj_fdp_flat_bytes(l.ncb); }
+    return l;
 }
 
-// does jtj_run honour a JtjUnpack for this plan? (the tile-pair jobs have a reduction of their own; jtj_run_fd* always do)
-inline bool jtj_plain_unpacks(const JtjPlan& p, bool broyden = false) { return !p.wide || (p.fdp8 && !broyden); }
-// can the m x n DIFFERENCE panel be consumed for this shape? (f64; n <= 128: fdp_plain; n = 192, 256: k_jtj_fdp8)
-inline bool jtj_fd_diff_ok(const JtjPlan& p, int n) { return p.fdp_plain || (p.fdp8 && n % 64 == 0); }
+// slab elements the J^T J kernels of a plan may write
+inline size_t jtj_slab_elems(const JtjPlan& p)
+{
+    size_t e = 0;
+    for (const JtjLaunch* l : {&p.plain, &p.rewrite, &p.fd, &p.fd_diff, &p.stream_fallback}) {
+        const size_t el = (size_t)l->nblk * l->njobs * l->slab_len;
+        e = e > el ? e : el;
+    }
+    return e;
+}
+
+// does jtj_run honour a JtjUnpack for this operation? (the tile-pair jobs have a reduction of their own)
+inline bool jtj_unpacks(const JtjPlan& p, JtjOp op) { return p.of(op).kernel != JtjKernel::wide; }
 
 // ---- launch entry points (launch_jtj.hip; instantiated for double and float). Every kernel they launch is counted in
 //      tl_launches. `packed` receives [J^T J lower | J^T y]; `u` additionally the unpacked form (see JtjUnpack).
-// [Broyden rewrite, MIR_LSQ_VARIANT_BROYDEN_REWRITE] + J^T J + J^T y of the J in a.J
+// the operation `op` on a.J -- plain / rewrite: J; fd: the m x 2n row-major pair panel, fd_diff: the m x n difference panel
+// D_ij = f(x + h e_j)_i - f(x - h e_j)_i (both with a.twh; a.Jout receives J). hipErrorInvalidValue: the shape is not covered.
 template <typename T>
-hipError_t jtj_run(const JtjPlan& p, const JtjArgs<T>& a, bool broyden, T* packed, hipStream_t s, const JtjUnpack<T>& u = {});
-// finite-difference pair panel (a.J: m x 2n row-major, a.twh) -> a.Jout, packed
-template <typename T>
-hipError_t jtj_run_fd(const JtjPlan& p, const JtjArgs<T>& a, T* packed, hipStream_t s, const JtjUnpack<T>& u = {});
-// finite-difference DIFFERENCE panel (a.J: m x n row-major, D_ij = f(x + h e_j)_i - f(x - h e_j)_i; a.twh) -> a.Jout, packed
-template <typename T>
-hipError_t jtj_run_fd_diff(const JtjPlan& p, const JtjArgs<T>& a, T* packed, hipStream_t s, const JtjUnpack<T>& u = {});
+hipError_t jtj_run(const JtjPlan& p, JtjOp op, const JtjArgs<T>& a, T* packed, hipStream_t s, const JtjUnpack<T>& u = {});
 // packed [J^T J lower | J^T y] -> full symmetric JJ, Jy, st->jy_inf (behind a communicator's all-reduce)
 template <typename T> struct LmState;
 template <typename T>

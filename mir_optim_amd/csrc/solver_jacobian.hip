@@ -53,9 +53,9 @@ bool Solver<T>::plain_products(const T* y_vec)
     JtjArgs<T> a{};
     a.J = B.J; a.Jout = B.J; a.y = y_vec; a.y_old = y_vec; a.dx = B.dx_acc; a.dx_dot = &B.st->dx_dot;
     a.slabs = B.slabs; a.m = m; a.n = (int)n;
-    const bool direct = unpack_in_reduce(false);
+    const bool direct = unpack_in_reduce(JtjOp::plain);
     ev_begin(0);
-    if (!ok(jtj_run<T>(plan, a, false, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "jtj kernel")) return false;
+    if (!ok(jtj_run<T>(plan, JtjOp::plain, a, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "jtj kernel")) return false;
     ev_end();
     return finish_products(direct);
 }
@@ -81,19 +81,19 @@ bool Solver<T>::jacobian_products(bool broyden, const T* y_dev, const T* yold_de
     if (!broyden && fd_fused) {
         // the row-major FD panel is still in ws->ypanel: one kernel forms the Jacobian rows (LS:1041-1047), writes
         // them to J and accumulates J^T J / J^T y from the same registers
-        const bool diff = fd_fused == 2;
+        const JtjOp op = fd_fused == 2 ? JtjOp::fd_diff : JtjOp::fd;
         fd_fused = 0;
         a.J = static_cast<const T*>(ws->ypanel); a.twh = B.twh;
-        const bool direct = unpack_in_reduce(true);
-        const JtjUnpack<T> u = direct ? unpack_target() : JtjUnpack<T>{};
+        const bool direct = unpack_in_reduce(op);
         ev_begin(3);
-        if (!ok(diff ? jtj_run_fd_diff<T>(plan, a, B.packed, stream, u) : jtj_run_fd<T>(plan, a, B.packed, stream, u), "fd + jtj kernel")) return false;
+        if (!ok(jtj_run<T>(plan, op, a, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "fd + jtj kernel")) return false;
         ev_end();
         return finish_products(direct);
     }
-    const bool direct = unpack_in_reduce(false, broyden);
+    const JtjOp op = broyden ? JtjOp::rewrite : JtjOp::plain;
+    const bool direct = unpack_in_reduce(op);
     ev_begin(broyden ? 1 : 0);
-    if (!ok(jtj_run<T>(plan, a, broyden, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "jtj kernel")) return false;
+    if (!ok(jtj_run<T>(plan, op, a, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "jtj kernel")) return false;
     ev_end();
     return finish_products(direct);
 }
@@ -131,7 +131,7 @@ bool Solver<T>::fd_device()
     if (pb < 1) pb = 1;
     if (fb && fd_batch && fd_batch / 2 < pb) pb = fd_batch / 2 ? fd_batch / 2 : 1;
     const bool no_fuse = (variant & MIR_LSQ_VARIANT_FD_SEPARATE_FILL) != 0;
-    const bool use_diff = fbd && jtj_fd_diff_ok(plan, (int)n) && pb == n && sizeof(T) == 8 && !no_fuse;   // m x n difference panel
+    const bool use_diff = fbd && plan.fd_diff.kernel != JtjKernel::none && pb == n && !no_fuse;   // m x n difference panel
     const size_t need = (use_diff ? 1 : 2) * pb * m * sizeof(T);
     if (ws->ypanel_bytes < need) {
         if (ws->ypanel) (void)hipFree(ws->ypanel);
@@ -151,7 +151,7 @@ bool Solver<T>::fd_device()
         ret.fCalls += n;
         return ok(hipGetLastError(), "fd batched callback");
     }
-    if (fbr && (plan.fdp || plan.fdp8) && pb == n && sizeof(T) == 8 && !no_fuse) {
+    if (fbr && plan.fd.kernel != JtjKernel::none && pb == n && !no_fuse) {
         // all 2n points in one sweep, Y[i][2j], Y[i][2j+1] = f(x + h e_j)_i, f(x - h e_j)_i; k_jtj_fdp<., true>
         // (jacobian_products) turns the pairs into Jacobian rows on its way to J^T J -- no k_fd_fill pass
         ev_begin(4);

@@ -1,6 +1,6 @@
 // unit_entries.hip -- unit-level access to the kernels of the path (parity tests, micro-benchmarks) and the standalone
 // BOXCQP entry: mir_solve_box_qp_gpu_* (boxcqp.d:85-102 is D-only), mir_lsq_jtj_*, mir_lsq_fd_jtj_d, mir_lsq_fd_diff_jtj_d,
-// mir_lsq_selftest_reductions. Each call owns its scratch and synchronises before it returns.
+// mir_lsq_selftest_reductions. Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
 #include "driver.h"
 #include "misc_kernels.h"
 
@@ -108,7 +108,7 @@ int jtj_entry(size_t m, size_t n, T* J, const T* y, const T* y_old, const T* dx,
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, stream);
-    if (jtj_run<T>(plan, a, broyden != 0, packed, stream) != hipSuccess) rc = -4;
+    if (jtj_run<T>(plan, broyden ? JtjOp::rewrite : JtjOp::plain, a, packed, stream) != hipSuccess) rc = -4;
     (void)hipEventRecord(e1, stream);
     (void)jtj_unpack<T>(packed, (int)n, JJ, Jy, st, stream);
     if (hipStreamSynchronize(stream) != hipSuccess) rc = -5;
@@ -124,7 +124,8 @@ int fd_jtj_entry(size_t m, size_t n, const double* Yrm, const double* twh, const
     if (n == 0 || m == 0) return -2;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const JtjPlan plan = jtj_plan<double>(m, (int)n, query_num_cu());
-    if (diff ? !jtj_fd_diff_ok(plan, (int)n) : (!plan.fdp && !plan.fdp8)) return -6;   // shape not covered by a fused kernel
+    const JtjOp op = diff ? JtjOp::fd_diff : JtjOp::fd;
+    if (plan.of(op).kernel == JtjKernel::none) return -6;   // shape not covered by a fused kernel
     const size_t packed_len = n * (n + 1) / 2 + n + 8;
     double *slabs = nullptr, *packed = nullptr;
     LmState<double>* st = nullptr;
@@ -139,7 +140,7 @@ int fd_jtj_entry(size_t m, size_t n, const double* Yrm, const double* twh, const
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, stream);
-    if ((diff ? jtj_run_fd_diff<double>(plan, a, packed, stream) : jtj_run_fd<double>(plan, a, packed, stream)) != hipSuccess) rc = -4;
+    if (jtj_run<double>(plan, op, a, packed, stream) != hipSuccess) rc = -4;
     (void)hipEventRecord(e1, stream);
     (void)jtj_unpack<double>(packed, (int)n, JJ, Jy, st, stream);
     if (hipStreamSynchronize(stream) != hipSuccess) rc = -5;
@@ -177,6 +178,17 @@ int mir_lsq_fd_diff_jtj_d(size_t m, size_t n, const double* Drm, const double* t
                           double* JJ, double* Jy, void* stream_, float* kernel_ms)
 {
     return fd_jtj_entry(m, n, Drm, twh, y, J, JJ, Jy, stream_, kernel_ms, true);
+}
+int mir_lsq_jtj_plan(size_t elem_size, size_t m, size_t n, int num_cu, int op, int aligned16, size_t out[10])
+{
+    if ((elem_size != 4 && elem_size != 8) || m == 0 || n == 0 || n > (size_t)1 << 20 || num_cu < 1 || op < 0 || op > 3 || !out) return -1;
+    const JtjPlan p = elem_size == 8 ? jtj_plan<double>(m, (int)n, num_cu) : jtj_plan<float>(m, (int)n, num_cu);
+    const JtjLaunch l = jtj_resolve(p, (JtjOp)op, aligned16 != 0);
+    const bool wide = l.kernel == JtjKernel::wide;
+    const size_t v[10] = {(size_t)l.kernel, (size_t)l.ncb, (size_t)l.flat, (size_t)l.nblk, (size_t)l.njobs, l.lds,
+                          (size_t)l.nblk * l.njobs, (size_t)l.slab_len, wide ? 0 : (size_t)l.ncb, jtj_slab_elems(p)};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return 0;
 }
 int mir_lsq_jtj_s(size_t m, size_t n, float* J, const float* y, const float* y_old, const float* dx, int broyden,
                   float* JJ, float* Jy, void* stream, float* kernel_ms)
