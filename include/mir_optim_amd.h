@@ -425,6 +425,70 @@ int mir_lsq_batched_kernel_d(const mir_least_squares_settings_d* settings, size_
                              const double* t, size_t t_stride, const double* data,
                              mir_least_squares_result_d* results, const mir_lsq_batched_options* options);
 
+/* Per-row WEIGHTS and the COVARIANCE of the fitted parameters on the batched path -- the `sigma` and `pcov` of a curve-fitting
+ * interface. The reference takes an arbitrary f (least_squares.d:73-80), so its caller writes (model - data) / sigma_i into f;
+ * here the residual is compiled in, and the weights travel in this struct through the _ex entries (mir_lsq_batched_options
+ * keeps its size). With weights the residual of row i is
+ *     w_i (eval(t_i, x) - data_i),    w_i = 1 / sigma_i for data with per-point uncertainties,
+ * everywhere the fit forms a residual or a Jacobian row (finite-difference points are weighted before they are differenced,
+ * as through a weighted f). A weight of exactly 0 REMOVES its row: problems of different lengths are padded to a common m and
+ * the padding rows given weight 0 (their data must still be finite). Non-finite weights are the caller's error: the
+ * host-pointer entry rejects them with -1, the device-pointer entries do not scan (a NaN residual takes the reference's
+ * numericError exits).
+ * covariance, per problem n x n values row-major, symmetric:
+ *     cov = s^2 (J^T J)^-1,  J the (weighted) Jacobian at the returned x, rebuilt as a refresh of the fit builds it,
+ *     s^2 = residual / (rows with a nonzero weight - n),  or 1 with MIR_LSQ_BATCHED_ABSOLUTE_SIGMA.
+ * Every entry is +inf when J^T J is not positive definite to working precision or the degrees of freedom are <= 0, and NaN
+ * when the problem's status is negative (including -100 from the kernel entry: finish the problem, then call
+ * mir_lsq_batched_covariance_s / _d). */
+enum { MIR_LSQ_BATCHED_ABSOLUTE_SIGMA = 1u };
+typedef struct mir_lsq_batched_extras {
+    uint32_t struct_size;     /* = sizeof(mir_lsq_batched_extras) */
+    uint32_t flags;           /* MIR_LSQ_BATCHED_ABSOLUTE_SIGMA */
+    const void* weights;      /* values of the entry's type: m (weight_stride 0) or count x m (weight_stride m); NULL = unweighted */
+    size_t weight_stride;     /* 0 or m */
+    void* covariance;         /* out: count x n x n values of the entry's type; NULL = not wanted */
+} mir_lsq_batched_extras;
+/* The two batched entries of each precision with a trailing extras pointer. extras == NULL behaves exactly as the entry
+ * without _ex. The pointers in the struct live where the entry's other pointers do (host for
+ * mir_optimize_least_squares_batched_ex_*, device for the other two). The argument checks keep their order: -1 for the model
+ * id, the options and the extras (struct_size, weight_stride; the host entry's scan for non-finite weights), then the pointers
+ * and t_stride, then -2 for the device. The host entry computes the covariance after the general solver has completed the
+ * bounded problems, at their final x; the kernel entry computes it on the same stream right after the fit. */
+int mir_optimize_least_squares_batched_ex_s(const mir_least_squares_settings_s* settings, size_t count, size_t m, int model,
+                                            float* x, const float* lower, const float* upper,
+                                            const float* t, size_t t_stride, const float* data,
+                                            mir_least_squares_result_s* results, const mir_lsq_batched_options* options,
+                                            const mir_lsq_batched_extras* extras);
+int mir_optimize_least_squares_batched_ex_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                                            double* x, const double* lower, const double* upper,
+                                            const double* t, size_t t_stride, const double* data,
+                                            mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
+                                            const mir_lsq_batched_extras* extras);
+int mir_lsq_batched_kernel_ex_s(const mir_least_squares_settings_s* settings, size_t count, size_t m, int model,
+                                float* x, const float* lower, const float* upper,
+                                const float* t, size_t t_stride, const float* data,
+                                mir_least_squares_result_s* results, const mir_lsq_batched_options* options,
+                                const mir_lsq_batched_extras* extras);
+int mir_lsq_batched_kernel_ex_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                                double* x, const double* lower, const double* upper,
+                                const double* t, size_t t_stride, const double* data,
+                                mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
+                                const mir_lsq_batched_extras* extras);
+/* The covariance kernel on its own (device pointers, enqueued on options->stream): for a caller of the kernel entry who has
+ * finished its -100 problems itself and written their x and result records back. x and results are read, extras->covariance
+ * (required) is written; options->variant selects the analytic Jacobian as in the fit. */
+int mir_lsq_batched_covariance_s(const mir_least_squares_settings_s* settings, size_t count, size_t m, int model,
+                                 const float* x, const float* lower, const float* upper,
+                                 const float* t, size_t t_stride, const float* data,
+                                 const mir_least_squares_result_s* results, const mir_lsq_batched_options* options,
+                                 const mir_lsq_batched_extras* extras);
+int mir_lsq_batched_covariance_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                                 const double* x, const double* lower, const double* upper,
+                                 const double* t, size_t t_stride, const double* data,
+                                 const mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
+                                 const mir_lsq_batched_extras* extras);
+
 /* Resident-J solver (include/mir_optim_amd_resident.hpp, launch_resident<Model>): the whole loop of least_squares.d:972-1175
  * in ONE cooperative launch for problems whose Jacobian, residuals and per-row data fit the LDS of the chip (BASELINE
  * cfg 2). The residual model is a compile-time type of the caller's, as on the batched path. Options and statistics of

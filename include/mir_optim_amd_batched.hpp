@@ -34,12 +34,26 @@
 // has the contract of mir_lsq_batched_kernel_s / _d (include/mir_optim_amd.h): every pointer a DEVICE pointer, enqueued on
 // options->stream, results in place, status -100 (MIR_LSQ_BATCHED_NEEDS_GENERAL) for a problem whose step reaches a finite
 // bound. tests/user_model/ holds a complete example that is compiled and compared with the float oracle.
+//
+// Weights and covariance (mir_lsq_batched_extras, the trailing argument of launch_batched; include/mir_optim_amd.h says the same
+// of the C entries). With extras->weights the residual of row i is  w_i (eval(t_i, basis_i, x) - data_i)  -- w_i = 1 / sigma_i
+// for data with per-point uncertainties -- in the residual, at both points of every central difference and as w_i grad_j on the
+// analytic path: the fit the reference makes of a weighted f. weight_stride 0: one vector of m weights for all problems; m:
+// count x m. A weight of exactly 0 removes its row; problems of different lengths are padded to a common m with zero-weight
+// rows (finite data there). The weighted kernel is an instance of its own (k_lm_batched<Model, true>): an unweighted launch
+// runs the code it always ran. With extras->covariance the launch is followed, on the same stream, by
+// launch_batched_covariance<Model>: per problem n x n values, cov = s^2 (J^T J)^-1 with J the weighted Jacobian at the final x
+// (grad or central differences, as the fit's options say) and s^2 = residual / (rows with nonzero weight - n), or s^2 = 1 with
+// MIR_LSQ_BATCHED_ABSOLUTE_SIGMA; +inf everywhere when J^T J is not positive definite or the degrees of freedom are <= 0, NaN
+// everywhere for a problem with a negative status (-100 included: finish it, then call launch_batched_covariance).
+// tests/user_model/user_model_weighted.hip is the example.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstddef>
+#include <cstring>
 #include <type_traits>
 
 #include "mir_optim_amd.h"
@@ -66,14 +80,89 @@ template <class Model> constexpr size_t batched_basis_floats(size_t count, size_
     return (size_t)Model::nb * (t_stride ? count : 1) * m;
 }
 
+namespace detail {
+// the extras as this build understands them (struct_size-versioned); false: implausible
+inline bool batched_extras(const mir_lsq_batched_extras* extras, size_t m, mir_lsq_batched_extras& e)
+{
+    e = mir_lsq_batched_extras{};
+    if (!extras) return true;
+    if (extras->struct_size < 8 || extras->struct_size > 1024) return false;
+    std::memcpy(&e, extras, extras->struct_size < sizeof e ? extras->struct_size : sizeof e);
+    e.struct_size = sizeof e;
+    return e.weight_stride == 0 || e.weight_stride == m;
+}
+
+// The per-row basis table of a launch: the caller's (options->basis) or one of this call's own.
+// No table from the caller: hipMalloc, and a stream synchronisation before hipFree in release(). (Until round 4 this was
+// hipMallocAsync / hipFreeAsync, and 2 of 300 calls with a 2 MB table returned wrong fits for a contiguous range of
+// problems. Root cause, reproduced WITHOUT any library code by scripts/probes/malloc_async_probe.hip on this ROCm
+// (HIP runtime 70226015): with the pool's default release threshold (0) a synchronisation hands the freed block back
+// to the OS, the next hipMallocAsync maps memory at the same address again, and kernels then read wrong words from
+// it -- 84 % of a table per iteration when ordinary hipMalloc / hipFree traffic runs beside it, still some without;
+// with hipMemPoolAttrReleaseThreshold = UINT64_MAX (the pool keeps its memory): none, in any configuration
+// (profiles/r05/malloc_async_probe_*.txt). The runtime's, not this library's; a caller who wants stream-ordered
+// allocation around these launches raises that threshold first. The table here stays in ordinary memory:
+// tests/test_gpu_batched.py::test_repeated_launches_with_a_large_basis_table_agree.)
+template <class Model> struct BasisTable {
+    using T = batched_value_t<Model>;
+    T* table = nullptr;
+    bool owned = false;
+    // 0, or -1 (the caller's table is too small) / -4 (allocation)
+    int acquire(const mir_lsq_batched_options* opt, const T* t, size_t count, size_t m, size_t t_stride, hipStream_t stream)
+    {
+        if constexpr (Model::nb > 0) {
+            const size_t rows = (size_t)(t_stride ? count : 1) * m, bytes = rows * Model::nb * sizeof(T);
+            if (opt && opt->basis) {
+                if (opt->basis_bytes < bytes) return -1;
+                table = reinterpret_cast<T*>(opt->basis);          // the caller's table (doubles for a double model): no allocation here
+            } else {
+                owned = true;
+                if (hipMalloc((void**)&table, bytes) != hipSuccess) return -4;
+            }
+            const unsigned bb = (unsigned)std::min<size_t>((rows + 255) / 256, 4096);
+            hipLaunchKernelGGL(mirlsq::k_batched_basis<Model>, dim3(bb), dim3(256), 0, stream, t, table, rows);
+        }
+        return 0;
+    }
+    hipError_t release(hipStream_t stream, hipError_t e)
+    {
+        if (owned) {
+            const hipError_t f = hipStreamSynchronize(stream);     // the kernels read the table: wait before freeing it
+            (void)hipFree(table);
+            if (e == hipSuccess) e = f;
+        }
+        return e;
+    }
+};
+
+template <class Model>
+void enqueue_covariance(const batched_settings_t<Model>* S, size_t count, size_t m, const batched_value_t<Model>* x,
+                        const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
+                        size_t t_stride, const batched_value_t<Model>* data, const batched_result_t<Model>* results,
+                        const batched_value_t<Model>* table, uint32_t variant, const mir_lsq_batched_extras& e, hipStream_t stream)
+{
+    using T = batched_value_t<Model>;
+    mirlsq::BatchedCovArgs<T> c{};
+    c.jacobianEpsilon = S->jacobianEpsilon;
+    c.count = (int)count; c.m = (int)m; c.t = t; c.t_stride = (int)t_stride; c.data = data; c.x = x; c.lower = lower; c.upper = upper;
+    c.results = reinterpret_cast<const mirlsq::BatchedResult<T>*>(results);
+    c.basis = table;
+    c.weights = static_cast<const T*>(e.weights); c.w_stride = (int)e.weight_stride;
+    c.variant = variant; c.flags = e.flags;
+    c.cov = static_cast<T*>(e.covariance);
+    hipLaunchKernelGGL(mirlsq::k_batched_covariance<Model>, dim3((unsigned)count), dim3(64), 0, stream, c);
+}
+}  // namespace detail
+
 // Returns 0, or: -1 bad arguments, -3 a problem does not fit its workgroup's LDS, -4 allocation of the basis table failed,
 // -5 the launch failed. Does not synchronise (except in the documented hipMalloc fallback of the basis table).
 // A float model takes the _s records and float arrays, a double model the _d records and double arrays.
+// extras (optional): per-row weights and / or the covariance of the fitted parameters, DEVICE pointers (see the top of this file).
 template <class Model>
 int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
                    const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
                    size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
-                   const mir_lsq_batched_options* opt = nullptr)
+                   const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
 {
     using namespace mirlsq;
     using T = batched_value_t<Model>;
@@ -84,6 +173,8 @@ int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, b
     static_assert(sizeof(BatchedResult<T>) == sizeof(batched_result_t<Model>), "the kernel writes the C result records in place");
     static_assert(offsetof(BatchedResult<T>, residual) == offsetof(batched_result_t<Model>, residual)
                   && offsetof(BatchedResult<T>, lambda) == offsetof(batched_result_t<Model>, lambda), "same layout as the C record");
+    mir_lsq_batched_extras e;
+    if (!detail::batched_extras(extras, m, e)) return -1;
     if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
     if (count == 0) return 0;
     const size_t lds = batched_lds_bytes<Model>(m);
@@ -102,53 +193,56 @@ int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, b
     a.timing = opt ? opt->timing : nullptr;
     a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
     a.results = reinterpret_cast<BatchedResult<T>*>(results);
-    auto kern = k_lm_batched<Model>;
+    a.weights = static_cast<const T*>(e.weights); a.w_stride = (int)e.weight_stride;
+    auto kern = e.weights ? k_lm_batched<Model, true> : k_lm_batched<Model, false>;     // the host picks the instance
     if (lds > 48 * 1024
         && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return -5;
-    T* table = nullptr;
-    bool owned = false;
-    if constexpr (Model::nb > 0) {
-        const size_t rows = (size_t)(t_stride ? count : 1) * m, bytes = rows * Model::nb * sizeof(T);
-        if (opt && opt->basis) {
-            if (opt->basis_bytes < bytes) return -1;
-            table = reinterpret_cast<T*>(opt->basis);          // the caller's table (doubles for a double model): no allocation here
-        } else {
-            // No table from the caller: hipMalloc, and a stream synchronisation before hipFree below. (Until round 4 this was
-            // hipMallocAsync / hipFreeAsync, and 2 of 300 calls with a 2 MB table returned wrong fits for a contiguous range of
-            // problems. Root cause, reproduced WITHOUT any library code by scripts/probes/malloc_async_probe.hip on this ROCm
-            // (HIP runtime 70226015): with the pool's default release threshold (0) a synchronisation hands the freed block back
-            // to the OS, the next hipMallocAsync maps memory at the same address again, and kernels then read wrong words from
-            // it -- 84 % of a table per iteration when ordinary hipMalloc / hipFree traffic runs beside it, still some without;
-            // with hipMemPoolAttrReleaseThreshold = UINT64_MAX (the pool keeps its memory): none, in any configuration
-            // (profiles/r05/malloc_async_probe_*.txt). The runtime's, not this library's; a caller who wants stream-ordered
-            // allocation around these launches raises that threshold first. The table here stays in ordinary memory:
-            // tests/test_gpu_batched.py::test_repeated_launches_with_a_large_basis_table_agree.)
-            owned = true;
-            if (hipMalloc((void**)&table, bytes) != hipSuccess) return -4;
-        }
-        const unsigned bb = (unsigned)std::min<size_t>((rows + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_batched_basis<Model>, dim3(bb), dim3(256), 0, stream, t, table, rows);
-        a.basis = table;
-    }
+    detail::BasisTable<Model> basis;
+    if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
+    a.basis = basis.table;
     hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64), lds, stream, a);
-    hipError_t e = hipGetLastError();
-    if (owned) {
-        const hipError_t f = hipStreamSynchronize(stream);     // the kernel reads the table: wait before freeing it
-        (void)hipFree(table);
-        if (e == hipSuccess) e = f;
-    }
-    return e == hipSuccess ? 0 : -5;
+    if (e.covariance)
+        detail::enqueue_covariance<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, a.variant, e, stream);
+    const hipError_t err = basis.release(stream, hipGetLastError());
+    return err == hipSuccess ? 0 : -5;
 }
 
-// the residual vector of ONE problem, y_i = eval(t_i, basis_i, x) - data_i, as a kernel launch on device pointers: what a
-// caller hands to the general solver as its device callback when a batched problem comes back with status -100 (float or
-// double, as the model is: mir_optimize_least_squares_gpu_s / _d)
+// The covariance of the fitted parameters on its own: x (count x n) and results (the fit's records: status and residual are
+// read) as a launch_batched left them -- or as the caller completed them for the -100 problems -- give extras->covariance
+// (required; count x n x n values). Device pointers, enqueued on options->stream; the same return codes as launch_batched.
+template <class Model>
+int launch_batched_covariance(const batched_settings_t<Model>* S, size_t count, size_t m, const batched_value_t<Model>* x,
+                              const batched_value_t<Model>* lower, const batched_value_t<Model>* upper,
+                              const batched_value_t<Model>* t, size_t t_stride, const batched_value_t<Model>* data,
+                              const batched_result_t<Model>* results, const mir_lsq_batched_options* opt,
+                              const mir_lsq_batched_extras* extras)
+{
+    using namespace mirlsq;
+    static_assert(Model::n >= 1 && Model::n <= kBatchedNMax, "1 <= n <= 8: one matrix row per lane of a group of eight");
+    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
+    mir_lsq_batched_extras e;
+    if (!extras || !detail::batched_extras(extras, m, e) || !e.covariance) return -1;
+    if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
+    if (count == 0) return 0;
+    if (m == 0) return -3;
+    hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
+    detail::BasisTable<Model> basis;
+    if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
+    detail::enqueue_covariance<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, opt ? opt->variant : 0, e, stream);
+    const hipError_t err = basis.release(stream, hipGetLastError());
+    return err == hipSuccess ? 0 : -5;
+}
+
+// the residual vector of ONE problem, y_i = eval(t_i, basis_i, x) - data_i -- times w_i when `weights` (the problem's m values)
+// is given -- as a kernel launch on device pointers: what a caller hands to the general solver as its device callback when a
+// batched problem comes back with status -100 (float or double, as the model is: mir_optimize_least_squares_gpu_s / _d)
 template <class Model>
 void launch_model_residual(const batched_value_t<Model>* t, const batched_value_t<Model>* data, const batched_value_t<Model>* x,
-                           batched_value_t<Model>* y, size_t m, hipStream_t stream)
+                           batched_value_t<Model>* y, size_t m, hipStream_t stream, const batched_value_t<Model>* weights = nullptr)
 {
-    hipLaunchKernelGGL(mirlsq::k_batched_model_eval<Model>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, t, data, x, y, (int)m);
+    hipLaunchKernelGGL(mirlsq::k_batched_model_eval<Model>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, t, data, x, y, (int)m,
+                       weights);
 }
 
 }  // namespace mir_optim_amd

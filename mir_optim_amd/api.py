@@ -34,7 +34,7 @@ __all__ = [
     "fit_spline_residuals", "variant_lr_cap",
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
     "VARIANT_SOLVE_BOUNDED", "VARIANT_DEBUG_SOLVE", "VARIANT_HOST_PROFILE", "VARIANT_SOLVE_GENERIC", "VARIANT_SOLVE_ONE_WORKGROUP", "VARIANT_DEBUG_HELPERS_ABSENT", "VARIANT_FD_HOST_COLUMNS",
-    "VARIANT_NO_PIPELINE", "BatchedOptions",
+    "VARIANT_NO_PIPELINE", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA",
 ]
 
 MODEL_EXP_DECAY = 0      # n = 3: p0 exp(-t p1) + p2
@@ -212,6 +212,16 @@ class BatchedOptions(C.Structure):
         self.struct_size = C.sizeof(BatchedOptions)
 
 
+class BatchedExtras(C.Structure):
+    """mir_lsq_batched_extras: per-row weights and the covariance output of the batched _ex entries."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("weights", C.c_void_p), ("weight_stride", C.c_size_t),
+                ("covariance", C.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = C.sizeof(BatchedExtras)
+
+
 TASK_FN = C.CFUNCTYPE(None, _Task, C.c_uint32, C.c_uint32, C.c_uint32)
 TM_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, _Task, TASK_FN)
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -298,6 +308,12 @@ def lib():
                                                C.c_void_p, sz, C.c_void_p, C.c_void_p, C.POINTER(BatchedOptions)]
         L.mir_lsq_batched_posvx_d.restype = C.c_int
         L.mir_lsq_batched_posvx_d.argtypes = [sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for suf, S in (("s", _Ss), ("d", _Sd)):
+            for name in ("mir_optimize_least_squares_batched_ex_", "mir_lsq_batched_kernel_ex_", "mir_lsq_batched_covariance_"):
+                fn = getattr(L, name + suf)
+                fn.restype = C.c_int
+                fn.argtypes = [C.POINTER(S), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
+                               C.c_void_p, C.POINTER(BatchedOptions), C.POINTER(BatchedExtras)]
         L.mir_lsq_comm_describe.restype = C.c_int
         L.mir_lsq_comm_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         L.mir_lsq_workspace_create.restype = C.c_void_p
@@ -603,10 +619,16 @@ def _batched_suffix(dtype):
     raise ValueError(f"the batched entries exist in float32 and float64, not {np.dtype(dtype)}")
 
 
-def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None, variant=0, dtype=np.float32):
+def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None, variant=0, dtype=np.float32, weights=None,
+                                covariance=False, absolute_sigma=False):
     """Many independent small fits, one wavefront per problem (mir_optimize_least_squares_batched_s, fp32, or with
     dtype=np.float64 mir_optimize_least_squares_batched_d). x: count x n starts (a copy is updated and returned), t: m
-    (shared) or count x m, data: count x m. variant: BATCHED_* bits (per call). Returns (list of LeastSquaresResult, x)."""
+    (shared) or count x m, data: count x m. variant: BATCHED_* bits (per call). Returns (list of LeastSquaresResult, x).
+    weights: m (shared) or count x m values w_i = 1 / sigma_i; the residual of row i becomes w_i (model - data_i), a weight of 0
+    removes the row. covariance=True: returns (results, x, cov), cov count x n x n = s^2 inv(J^T J) at the returned x with
+    s^2 = residual / (rows with nonzero weight - n), or s^2 = 1 with absolute_sigma=True; +inf for a singular J^T J or no
+    degrees of freedom, NaN for a problem with a negative status. Any of the three goes through the _ex entry
+    (mir_optimize_least_squares_batched_ex_s / _d); a call without them is the call it always was."""
     suf = _batched_suffix(dtype)
     dtype = np.float32 if suf == "s" else np.float64
     L = lib()
@@ -621,15 +643,34 @@ def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None
     if settings is None:
         settings = LeastSquaresSettings(dtype)
     raw = ((_Rs if suf == "s" else _Rd) * count)()
-    fn = getattr(L, "mir_optimize_least_squares_batched_" + suf)
+    if weights is None and not covariance and not absolute_sigma:
+        fn = getattr(L, "mir_optimize_least_squares_batched_" + suf)
+        rc = fn(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data, up.ctypes.data, t.ctypes.data, t_stride,
+                data.ctypes.data, raw, C.byref(BatchedOptions(variant=variant)))
+        if rc != 0:
+            raise RuntimeError(f"mir_optimize_least_squares_batched_{suf} failed: {rc}")
+        return [LeastSquaresResult(r) for r in raw], x
+    ex = BatchedExtras(flags=BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0)
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=dtype)
+        if weights.shape not in ((m,), (count, m)):
+            raise ValueError(f"weights: {m} values or {count} x {m}, not {weights.shape}")
+        ex.weights = weights.ctypes.data
+        ex.weight_stride = 0 if weights.ndim == 1 else m
+    cov = np.empty((count, n, n), dtype=dtype) if covariance else None
+    if covariance:
+        ex.covariance = cov.ctypes.data
+    fn = getattr(L, "mir_optimize_least_squares_batched_ex_" + suf)
     rc = fn(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data, up.ctypes.data, t.ctypes.data, t_stride,
-            data.ctypes.data, raw, C.byref(BatchedOptions(variant=variant)))
+            data.ctypes.data, raw, C.byref(BatchedOptions(variant=variant)), C.byref(ex))
     if rc != 0:
-        raise RuntimeError(f"mir_optimize_least_squares_batched_{suf} failed: {rc}")
-    return [LeastSquaresResult(r) for r in raw], x
+        raise RuntimeError(f"mir_optimize_least_squares_batched_ex_{suf} failed: {rc}")
+    res = [LeastSquaresResult(r) for r in raw]
+    return (res, x, cov) if covariance else (res, x)
 
 
 BATCHED_NO_LADDER = 1
+BATCHED_ABSOLUTE_SIGMA = 1      # mir_lsq_batched_extras.flags
 
 
 def batchedPosvx(P, rhs, dtype=np.float32):

@@ -99,7 +99,8 @@ if __name__ == "__main__":
 def build_user_model_example(force=False, verbose=False):
     """tests/user_model/: a caller's own residual models compiled against include/mir_optim_amd_batched.hpp and
     include/mir_optim_amd_resident.hpp (the device headers of the batched fit and of the resident-J path) into a library of its own -- what a user of that header does. Built here so that it travels prebuilt.
-    The double model of user_model_f64.hip goes into a library of its own next to it (user_model_f64_lib())."""
+    The double model of user_model_f64.hip goes into a library of its own next to it (user_model_f64_lib()), and so does the
+    weighted fit with covariance of user_model_weighted.hip (user_model_weighted_lib())."""
     root = os.path.dirname(HERE)
     src = os.path.join(root, "tests", "user_model", "user_model.hip")
     out = os.path.join(root, "tests", "user_model", "libuser_model.so")
@@ -112,6 +113,9 @@ def build_user_model_example(force=False, verbose=False):
     src64, out64 = user_model_f64_paths()
     if force or _stale(out64, [src64] + deps[1:6]):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out64, src64], verbose)
+    srcw, outw = user_model_weighted_paths()
+    if force or _stale(outw, [srcw] + deps[1:6]):
+        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", outw, srcw], verbose)
     return out
 
 
@@ -125,3 +129,15 @@ def user_model_f64_lib(force=False, verbose=False):
     """Builds (when stale) and returns the path of tests/user_model/libuser_model_f64.so."""
     build_user_model_example(force=force, verbose=verbose)
     return user_model_f64_paths()[1]
+
+
+def user_model_weighted_paths():
+    """(source, library) of the caller's weighted fit with covariance (tests/user_model/user_model_weighted.hip)"""
+    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
+    return os.path.join(d, "user_model_weighted.hip"), os.path.join(d, "libuser_model_weighted.so")
+
+
+def user_model_weighted_lib(force=False, verbose=False):
+    """Builds (when stale) and returns the path of tests/user_model/libuser_model_weighted.so."""
+    build_user_model_example(force=force, verbose=verbose)
+    return user_model_weighted_paths()[1]

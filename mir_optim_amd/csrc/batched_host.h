@@ -1,7 +1,8 @@
 // batched_host.h -- host layer of the batched path (BASELINE cfg 5: many small independent fits, one wavefront per problem,
 // batched_kernel.h), written once in the value type T. The launch itself is the public device-header template
 // launch_batched<Model> (include/mir_optim_amd_batched.hpp); this header adds, for the three compiled-in models of T,
-//   batched_kernel_entry<T>   the device-pointer entry (mir_lsq_batched_kernel_s / _d),
+//   batched_kernel_entry<T>   the device-pointer entry (mir_lsq_batched_kernel_s / _d and, with extras, _ex_s / _ex_d),
+//   batched_covariance_entry<T>  the covariance kernel on its own (mir_lsq_batched_covariance_s / _d),
 //   batched_posvx_entry<T>    the ?posvx unit entry (mir_lsq_batched_posvx_s / _d),
 //   batched_host_entry<T>     the host-pointer entry (mir_optimize_least_squares_batched_s / _d), which completes problems whose
 //                             step reaches a finite bound with the general solver (BOXCQP on the device, boxcqp.d:234-376).
@@ -42,18 +43,41 @@ inline bool batched_options_plausible(const mir_lsq_batched_options* opt)
     return !opt || (opt->struct_size >= 8 && opt->struct_size <= 1024);
 }
 
-// Both precisions check in one order: model id and options, then pointers and t_stride (-1), then the device (-2).
+// the extras (weights, covariance) are plausible: a struct size, and a weight_stride of 0 or m. NULL = none.
+inline bool batched_extras_plausible(const mir_lsq_batched_extras* extras, size_t m)
+{
+    mir_lsq_batched_extras e;
+    return mir_optim_amd::detail::batched_extras(extras, m, e);
+}
+
+// Both precisions check in one order: model id, options and extras, then pointers and t_stride (-1), then the device (-2).
 template <class T>
 int batched_kernel_entry(const typename Abi<T>::Settings* S, size_t count, size_t m, int model, T* x, const T* lower, const T* upper,
                          const T* t, size_t t_stride, const T* data, typename Abi<T>::Result* results,
-                         const mir_lsq_batched_options* options)
+                         const mir_lsq_batched_options* options, const mir_lsq_batched_extras* extras = nullptr)
 {
     return with_builtin_model<T>(model, [&](auto mdl) {
-        if (!batched_options_plausible(options)) return -1;
+        if (!batched_options_plausible(options) || !batched_extras_plausible(extras, m)) return -1;
         if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
         if (count != 0 && !device_available()) return -2;
         const mir_lsq_batched_options o = batched_options(options);
-        return mir_optim_amd::launch_batched<decltype(mdl)>(S, count, m, x, lower, upper, t, t_stride, data, results, &o);
+        return mir_optim_amd::launch_batched<decltype(mdl)>(S, count, m, x, lower, upper, t, t_stride, data, results, &o, extras);
+    });
+}
+
+template <class T>
+int batched_covariance_entry(const typename Abi<T>::Settings* S, size_t count, size_t m, int model, const T* x, const T* lower,
+                             const T* upper, const T* t, size_t t_stride, const T* data, const typename Abi<T>::Result* results,
+                             const mir_lsq_batched_options* options, const mir_lsq_batched_extras* extras)
+{
+    return with_builtin_model<T>(model, [&](auto mdl) {
+        mir_lsq_batched_extras e;
+        if (!batched_options_plausible(options) || !extras || !mir_optim_amd::detail::batched_extras(extras, m, e) || !e.covariance)
+            return -1;
+        if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
+        if (count != 0 && !device_available()) return -2;
+        const mir_lsq_batched_options o = batched_options(options);
+        return mir_optim_amd::launch_batched_covariance<decltype(mdl)>(S, count, m, x, lower, upper, t, t_stride, data, results, &o, extras);
     });
 }
 
@@ -70,22 +94,29 @@ int batched_posvx_entry(size_t count, size_t n, const T* P, const T* rhs, T* x, 
 }
 
 // the general solver's device callback for ONE problem of the batch: its residual vector by the model's own kernel
-template <class T> struct BatchedFallbackCtx { const T* t; const T* d; hipStream_t stream; };
+template <class T> struct BatchedFallbackCtx { const T* t; const T* d; hipStream_t stream; const T* w; };   // w: the problem's weights or nullptr
 template <class Model>
 void batched_fallback(void* vctx, size_t m, size_t, const batched_value_t<Model>* x, batched_value_t<Model>* y)
 {
     auto* c = static_cast<BatchedFallbackCtx<batched_value_t<Model>>*>(vctx);
-    mir_optim_amd::launch_model_residual<Model>(c->t, c->d, x, y, m, c->stream);
+    mir_optim_amd::launch_model_residual<Model>(c->t, c->d, x, y, m, c->stream, c->w);
 }
 
 template <class Model, class T = batched_value_t<Model>>
 int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, size_t m, T* x, const T* lower, const T* upper,
                              const T* t, size_t t_stride, const T* data, typename Abi<T>::Result* results,
-                             const mir_lsq_batched_options* options)
+                             const mir_lsq_batched_options* options, const mir_lsq_batched_extras* extras)
 {
     using Result = typename Abi<T>::Result;
     constexpr size_t n = Model::n;
-    if (!S || !x || !lower || !upper || !t || !data || !results || !batched_options_plausible(options)) return -1;
+    mir_lsq_batched_extras e;                  // HOST pointers here
+    if (!batched_options_plausible(options) || !mir_optim_amd::detail::batched_extras(extras, m, e)) return -1;
+    const T* weights = static_cast<const T*>(e.weights);
+    T* cov = static_cast<T*>(e.covariance);
+    const size_t wn = weights ? (e.weight_stride ? count : 1) * m : 0;
+    for (size_t i = 0; i < wn; ++i)
+        if (!(-Lim<T>::inf() < weights[i] && weights[i] < Lim<T>::inf())) return -1;      // non-finite weights: the caller's error
+    if (!S || !x || !lower || !upper || !t || !data || !results) return -1;
     if (t_stride != 0 && t_stride != m) return -1;
     for (size_t i = 0; i < count; ++i) {       // defaults of LeastSquaresResult!T, LS:132-142
         results[i].status = mir_ls_numericError; results[i].iterations = results[i].fCalls = results[i].gCalls = 0;
@@ -107,8 +138,9 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
     char* base = nullptr;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o_ = off; off = align_up(off + bytes, 256); return o_; };
+    const size_t wb = wn * sizeof(T), cb = cov ? count * n * n * sizeof(T) : 0;
     const size_t ot = take(tb), od = take(db), ox = take(xb), ol = take(n * sizeof(T)), ou = take(n * sizeof(T)),
-                 orr = take(count * sizeof(Result)), obasis = take(basis_b);
+                 orr = take(count * sizeof(Result)), obasis = take(basis_b), ow = take(wb), oc = take(cb);
     if (hipMalloc((void**)&base, off) != hipSuccess) return -4;
     o.basis = basis_b ? (float*)(base + obasis) : nullptr;      // the C member is float*; it holds doubles for a double model
     o.basis_bytes = basis_b;
@@ -116,14 +148,19 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
         && hipMemcpy(base + od, data, db, hipMemcpyHostToDevice) == hipSuccess
         && hipMemcpy(base + ox, x, xb, hipMemcpyHostToDevice) == hipSuccess
         && hipMemcpy(base + ol, lower, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess
-        && hipMemcpy(base + ou, upper, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+        && hipMemcpy(base + ou, upper, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess
+        && (!wb || hipMemcpy(base + ow, weights, wb, hipMemcpyHostToDevice) == hipSuccess);
+    // the device twin of the extras: the weights for the fit; the covariance comes after the fallback solves, below
+    const T* dw = wb ? (const T*)(base + ow) : nullptr;
+    mir_lsq_batched_extras de{};
+    de.struct_size = sizeof de; de.flags = e.flags; de.weights = dw; de.weight_stride = e.weight_stride;
     const T* dt = (const T*)(base + ot); const T* ddata = (const T*)(base + od); T* dx = (T*)(base + ox);
     Result* dres = (Result*)(base + orr);      // the kernel writes the C records in place (launch_batched asserts the layout)
     std::vector<Result> res(count);
     std::vector<T> x0(x, x + count * n);       // starts, for the fallback problems
     if (good && !bad) {
         good = mir_optim_amd::launch_batched<Model>(S, count, m, dx, (const T*)(base + ol), (const T*)(base + ou), dt, t_stride, ddata,
-                                                    dres, &o) == 0;
+                                                    dres, &o, extras ? &de : nullptr) == 0;
         good = good && hipDeviceSynchronize() == hipSuccess
             && hipMemcpy(res.data(), dres, count * sizeof(Result), hipMemcpyDeviceToHost) == hipSuccess
             && hipMemcpy(x, dx, xb, hipMemcpyDeviceToHost) == hipSuccess;
@@ -137,7 +174,7 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
                 // solve_entry<T> is all there is to mir_optimize_least_squares_gpu_s / _d
                 hipStream_t st = nullptr;
                 if (hipStreamCreate(&st) != hipSuccess) { good = false; break; }
-                BatchedFallbackCtx<T> c{dt + (t_stride ? i * m : 0), ddata + i * m, st};
+                BatchedFallbackCtx<T> c{dt + (t_stride ? i * m : 0), ddata + i * m, st, dw ? dw + (e.weight_stride ? i * m : 0) : nullptr};
                 mir_lsq_gpu_options go{};
                 go.struct_size = sizeof go; go.flags = MIR_LSQ_DEVICE_CALLBACKS; go.stream = st;
                 std::memcpy(x + i * n, x0.data() + i * n, n * sizeof(T));
@@ -147,6 +184,18 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
             }
         }
     }
+    if (good && cov && bad) {
+        for (size_t i = 0; i < count * n * n; ++i) cov[i] = Lim<T>::inf() - Lim<T>::inf();     // negative status: NaN
+    } else if (good && cov) {
+        // the covariance at every problem's FINAL x: the records and x of the fallback problems go back to the device first
+        de.covariance = base + oc;
+        good = hipMemcpy(dres, results, count * sizeof(Result), hipMemcpyHostToDevice) == hipSuccess
+            && hipMemcpy(dx, x, xb, hipMemcpyHostToDevice) == hipSuccess
+            && mir_optim_amd::launch_batched_covariance<Model>(S, count, m, dx, (const T*)(base + ol), (const T*)(base + ou), dt,
+                                                               t_stride, ddata, dres, &o, &de) == 0
+            && hipDeviceSynchronize() == hipSuccess
+            && hipMemcpy(cov, base + oc, cb, hipMemcpyDeviceToHost) == hipSuccess;
+    }
     (void)hipFree(base);
     return good ? 0 : -5;
 }
@@ -154,10 +203,10 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
 template <class T>
 int batched_host_entry(const typename Abi<T>::Settings* S, size_t count, size_t m, int model, T* x, const T* lower, const T* upper,
                        const T* t, size_t t_stride, const T* data, typename Abi<T>::Result* results,
-                       const mir_lsq_batched_options* options)
+                       const mir_lsq_batched_options* options, const mir_lsq_batched_extras* extras = nullptr)
 {
     return with_builtin_model<T>(model, [&](auto mdl) {
-        return batched_host_model_entry<decltype(mdl)>(S, count, m, x, lower, upper, t, t_stride, data, results, options);
+        return batched_host_model_entry<decltype(mdl)>(S, count, m, x, lower, upper, t, t_stride, data, results, options, extras);
     });
 }
 

@@ -173,6 +173,8 @@ template <class T> struct BatchedArgs {
     const T* basis;        // (t_stride ? count : 1) x m x nb: the model's per-row basis (k_batched_basis), nullptr when nb == 0
     uint64_t* timing;      // profiling builds (MIRLSQ_BATCHED_TIMING): 10 x count cycle counters (mir_lsq_batched_options.timing), else unused
     uint32_t variant;      // kBatchedNoLadder: one damping value per solve (A/B and the test of the ladder against it)
+    int w_stride;          // 0 = one vector of m weights shared by all problems, m = count x m
+    const T* weights;      // the WEIGHTED instances only (k_lm_batched<Model, true>): the residual of row i is w_i (eval - data_i)
 };
 constexpr uint32_t kBatchedNoLadder = 1u;
 constexpr uint32_t kBatchedAnalytic = 2u;      // MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN: Model::grad instead of finite differences
@@ -401,7 +403,15 @@ template <class Model> constexpr int batched_waves_per_simd()
     return std::is_same<batched_value_t<Model>, double>::value ? 1 : (Model::n <= 4 ? 4 : 2);
 }
 
-template <class Model>
+// WEIGHTED (a compile-time parameter: the host picks the instance, launch_batched): the residual of row i is
+// w_i (eval(t_i, b_i, x) - data_i) -- ONE multiplication after the subtraction, wherever a residual or a Jacobian row is formed
+// (feval; the finite-difference points, each weighted before they are differenced, which is what the reference sees through a
+// weighted f; J_ij = w_i g_j on the analytic path). The weights are read from global memory next to t and data, in the same
+// chunked, clamped loads: no LDS, the m limits stay. A weight of exactly 0 removes its row (residual and Jacobian row are zero):
+// a batch of problems of different lengths is padded to a common m with zero-weight rows. Non-finite weights are the caller's
+// error: a NaN residual takes the reference's numericError exits. The unweighted instances do not read a.weights and are,
+// instruction for instruction, what they were before the parameter existed.
+template <class Model, bool WEIGHTED = false>
 __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batched(BatchedArgs<batched_value_t<Model>> a)
 {
     // Nothing in this body is left to the compiler's choice of what to fuse: contraction is off and every multiply-add that is
@@ -427,6 +437,8 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
     constexpr int NB = Model::nb;
     const T* bp = NB ? a.basis + (size_t)(a.t_stride ? prob : 0) * a.t_stride * NB : nullptr;
     const LmSettingsDev<T>& S = a.set;
+    const T* wp = nullptr;
+    if constexpr (WEIGHTED) wp = a.weights + (size_t)(a.w_stride ? prob : 0) * a.w_stride;
 
     T x[NMAX], lo[NMAX], up[NMAX];
 #pragma unroll
@@ -451,16 +463,20 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
         constexpr int UNR = 8;
         T ss = 0;
         for (int base = lane; base - lane < m; base += kWave * UNR) {
-            T tv[UNR], dv[UNR], rv[UNR];
+            T tv[UNR], dv[UNR], rv[UNR], wv[WEIGHTED ? UNR : 1];
             BasisRow<NB, T> bv[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int i = min(base + kWave * u, m - 1);
                 tv[u] = tp[i]; dv[u] = dp[i];
+                if constexpr (WEIGHTED) wv[u] = wp[i];
                 bv[u].load(bp, i);
             }
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) rv[u] = Model::eval(tv[u], bv[u].v, p) - dv[u];
+            for (int u = 0; u < UNR; ++u) {
+                rv[u] = Model::eval(tv[u], bv[u].v, p) - dv[u];
+                if constexpr (WEIGHTED) rv[u] = wv[u] * rv[u];
+            }
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int i = base + kWave * u;
@@ -538,6 +554,11 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
 #pragma unroll
                             for (int j = 0; j < NMAX; ++j) gi[j] = 0;
                             Model::grad(tp[i], b.v, x, gi);
+                            if constexpr (WEIGHTED) {
+                                const T wi = wp[i];
+#pragma unroll
+                                for (int j = 0; j < N; ++j) gi[j] = wi * gi[j];
+                            }
 #pragma unroll
                             for (int j = 0; j < N; ++j) Jl[(size_t)i * N + j] = gi[j];
                         }
@@ -558,15 +579,19 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
                         BasisRow<NB, T> b;
                         b.load(bp, i);
                         const T ti = tp[i], di = dp[i];
+                        T wi = 1;
+                        if constexpr (WEIGHTED) wi = wp[i];
                         T p[NMAX];
 #pragma unroll
                         for (int k = 0; k < NMAX; ++k) p[k] = x[k];
 #pragma unroll
                         for (int j = 0; j < N; ++j) {
                             p[j] = xph[j];
-                            const T fp = Model::eval(ti, b.v, p) - di;
+                            T fp = Model::eval(ti, b.v, p) - di;
+                            if constexpr (WEIGHTED) fp = wi * fp;
                             p[j] = xmh[j];
-                            const T fm = Model::eval(ti, b.v, p) - di;
+                            T fm = Model::eval(ti, b.v, p) - di;
+                            if constexpr (WEIGHTED) fm = wi * fm;
                             p[j] = x[j];
                             const T v = fp - fm;
                             Jl[(size_t)i * N + j] = inv[j] != 0 ? v * inv[j] : T(0);
@@ -737,10 +762,144 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
 }
 
 
-// residual of one problem as a DEVICE callback body (used when a batched problem falls back to the general solver)
+// ---- covariance of the fitted parameters, one wave per problem, no LDS, on the stream of the fit after it ---------------------
+//     cov = s^2 (J^T J)^-1,   s^2 = ||f(x)||^2 / (rows with a nonzero weight - n),   or s^2 = 1 with kBatchedAbsoluteSigma
+// (the pcov of a curve fit; with weights w_i = 1 / sigma_i and kBatchedAbsoluteSigma it is the covariance in the units of sigma).
+// J is rebuilt row by row at the final x exactly as a refresh of the fit kernel builds it (Model::grad with kBatchedAnalytic,
+// else central differences with jacobianEpsilon clipped to the bounds; weighted rows), J^T J is accumulated as there (per-lane
+// partial sums in the row order of the fit, then wave_sum) and inverted by posvx_rows on unit right-hand sides: the four 16-lane
+// groups take four columns a call. ||f(x)||^2 and the status are read from the fit's result record. The n x n values of a
+// problem are written row-major, symmetric (the mean of the two solves' mirror elements). Degenerate cases:
+//     status < 0 (also -100 from the kernel entry: that problem is not finished)   every entry NaN
+//     a non-positive minor in the factorization, or rows - n <= 0                   every entry +inf
+template <class T> struct BatchedCovArgs {
+    T jacobianEpsilon;
+    int count, m;
+    const T* t; int t_stride;
+    const T* data;
+    const T* x;            // count x n: the fitted parameters
+    const T* lower; const T* upper;
+    const BatchedResult<T>* results;
+    const T* basis;
+    const T* weights; int w_stride;      // nullptr = unweighted
+    uint32_t variant;      // kBatchedAnalytic
+    uint32_t flags;        // kBatchedAbsoluteSigma
+    T* cov;                // count x n x n
+};
+constexpr uint32_t kBatchedAbsoluteSigma = 1u;      // MIR_LSQ_BATCHED_ABSOLUTE_SIGMA
+
+template <class Model>
+__global__ __launch_bounds__(64) void k_batched_covariance(BatchedCovArgs<batched_value_t<Model>> a)
+{
+#pragma clang fp contract(off)
+    using T = batched_value_t<Model>;
+    constexpr int N = Model::n, NMAX = kBatchedNMax, NB = Model::nb;
+    const int lane = threadIdx.x, prob = blockIdx.x, m = a.m, r = lane & 7;
+    T* out = a.cov + (size_t)prob * N * N;
+    const int status = a.results[prob].status;
+    if (status < 0) {
+        if (lane < N * N) out[lane] = Lim<T>::inf() - Lim<T>::inf();       // NaN
+        return;
+    }
+    const T* tp = a.t + (size_t)(a.t_stride ? prob : 0) * a.t_stride;
+    const T* dp = a.data + (size_t)prob * m;
+    const T* bp = NB ? a.basis + (size_t)(a.t_stride ? prob : 0) * a.t_stride * NB : nullptr;
+    const T* wp = a.weights ? a.weights + (size_t)(a.w_stride ? prob : 0) * a.w_stride : nullptr;
+    T x[NMAX], xph[NMAX], xmh[NMAX], inv[NMAX];
+#pragma unroll
+    for (int j = 0; j < NMAX; ++j) {
+        x[j] = j < N ? a.x[(size_t)prob * N + j] : T(0);
+        const T lo = j < N ? a.lower[j] : -Lim<T>::inf(), up = j < N ? a.upper[j] : Lim<T>::inf();
+        xmh[j] = vmax(x[j] - a.jacobianEpsilon, lo);
+        xph[j] = vmin(x[j] + a.jacobianEpsilon, up);
+        const T twh = xph[j] - xmh[j];
+        inv[j] = twh != 0 ? T(1) / twh : T(0);
+    }
+    constexpr bool HAS_GRAD = batched_has_grad<Model>::value;
+    const bool use_g = HAS_GRAD && (a.variant & kBatchedAnalytic) != 0;
+    T accJ[NMAX][NMAX], rows = 0;
+#pragma unroll
+    for (int j = 0; j < NMAX; ++j)
+#pragma unroll
+        for (int k = 0; k < NMAX; ++k) accJ[j][k] = 0;
+    for (int i = lane; i < m; i += kWave) {
+        BasisRow<NB, T> b;
+        b.load(bp, i);
+        const T ti = tp[i], di = dp[i], wi = wp ? wp[i] : T(1);
+        rows += wi != 0 ? T(1) : T(0);
+        T row[NMAX];
+#pragma unroll
+        for (int j = 0; j < NMAX; ++j) row[j] = 0;
+        if (use_g) {
+            if constexpr (HAS_GRAD) {
+                Model::grad(ti, b.v, x, row);
+                if (wp) {
+#pragma unroll
+                    for (int j = 0; j < N; ++j) row[j] = wi * row[j];
+                }
+            }
+        } else {
+            T p[NMAX];
+#pragma unroll
+            for (int k = 0; k < NMAX; ++k) p[k] = x[k];
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                p[j] = xph[j];
+                T fp = Model::eval(ti, b.v, p) - di;
+                p[j] = xmh[j];
+                T fm = Model::eval(ti, b.v, p) - di;
+                p[j] = x[j];
+                if (wp) { fp = wi * fp; fm = wi * fm; }
+                const T v = fp - fm;
+                row[j] = inv[j] != 0 ? v * inv[j] : T(0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int k = 0; k <= j; ++k) accJ[j][k] = __builtin_elementwise_fma(row[j], row[k], accJ[j][k]);
+    }
+    T JJrow[NMAX];
+#pragma unroll
+    for (int j = 0; j < NMAX; ++j) JJrow[j] = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+        for (int k = 0; k <= j; ++k) {
+            const T s = wave_sum(accJ[j][k]);
+            JJrow[k] = (r == j) ? s : JJrow[k];
+            if (k != j) JJrow[j] = (r == k) ? s : JJrow[j];
+        }
+    const T dof = wave_sum(rows) - T(N);                 // row counts are small integers: exact in T
+    // column c = 4 call + g of the inverse by group g = lane >> 4: the right-hand side is the unit vector e_c
+    const int g = lane >> 4;
+    T sol[2][NMAX];
+    int info = posvx_rows<N, NMAX>(JJrow, (r == g && r < N) ? T(1) : T(0), r, sol[0]);
+    if constexpr (N > 4) info |= posvx_rows<N, NMAX>(JJrow, (r == 4 + g && r < N) ? T(1) : T(0), r, sol[1]);
+    info = __builtin_amdgcn_readlane(info, 0);            // the four groups factor the same matrix
+    const T s2 = (a.flags & kBatchedAbsoluteSigma) ? T(1) : a.results[prob].residual / dof;
+    const bool degenerate = info != 0 || !(dof > 0);
+    T mine = 0;                                           // lane i n + c takes element (i, c)
+    static_for<NMAX>([&](auto I) {
+        constexpr int i = I.value;
+        static_for<NMAX>([&](auto Cc) {
+            constexpr int c = Cc.value;
+            if constexpr (i < N && c < N) {
+                const T vic = lane_get(sol[c / 4][i], 16 * (c & 3)), vci = lane_get(sol[i / 4][c], 16 * (i & 3));
+                const T v = s2 * ((vic + vci) / 2);
+                mine = (lane == i * N + c) ? v : mine;
+            }
+        });
+    });
+    if (lane < N * N) out[lane] = degenerate ? Lim<T>::inf() : mine;
+}
+
+// residual of one problem as a DEVICE callback body (used when a batched problem falls back to the general solver); w: the
+// problem's m weights, or nullptr
 template <class Model, class T = batched_value_t<Model>>
 __global__ __launch_bounds__(256) void k_batched_model_eval(const T* __restrict__ t, const T* __restrict__ d,
-                                                            const T* __restrict__ x, T* __restrict__ y, int m)
+                                                            const T* __restrict__ x, T* __restrict__ y, int m,
+                                                            const T* __restrict__ w)
 {
     constexpr int NB = Model::nb;
     T p[kBatchedNMax];
@@ -749,7 +908,8 @@ __global__ __launch_bounds__(256) void k_batched_model_eval(const T* __restrict_
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
         T b[NB > 0 ? NB : 1];
         Model::basis(t[i], b);
-        y[i] = Model::eval(t[i], b, p) - d[i];
+        const T v = Model::eval(t[i], b, p) - d[i];
+        y[i] = w ? w[i] * v : v;
     }
 }
 
