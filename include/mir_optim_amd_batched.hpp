@@ -181,12 +181,7 @@ int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, b
     if (m == 0 || lds > kBatchedLdsLimit) return -3;
     hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
     BatchedArgs<T> a{};
-    a.set.jacobianEpsilon = S->jacobianEpsilon; a.set.absTolerance = S->absTolerance; a.set.relTolerance = S->relTolerance;
-    a.set.gradTolerance = S->gradTolerance; a.set.maxGoodResidual = S->maxGoodResidual; a.set.maxStep = S->maxStep;
-    a.set.maxLambda = S->maxLambda; a.set.minLambda = S->minLambda; a.set.minStepQuality = S->minStepQuality;
-    a.set.goodStepQuality = S->goodStepQuality; a.set.lambdaIncrease = S->lambdaIncrease; a.set.lambdaDecrease = S->lambdaDecrease;
-    a.set.qpRelTolerance = S->qpSettings.relTolerance; a.set.qpAbsTolerance = S->qpSettings.absTolerance;
-    a.set.qpMaxIterations = S->qpSettings.maxIterations;
+    a.set = lm_settings_dev(S);
     a.maxIterations = S->maxIterations; a.maxAge = S->maxAge;
     a.count = (int)count; a.m = (int)m; a.t_stride = (int)t_stride;
     a.variant = opt ? opt->variant : 0;

@@ -172,12 +172,7 @@ int launch_resident(const mir_least_squares_settings_d* S, size_t m, double* x, 
         owned = true;
     }
     ResidentArgs a{};
-    a.set.jacobianEpsilon = S->jacobianEpsilon; a.set.absTolerance = S->absTolerance; a.set.relTolerance = S->relTolerance;
-    a.set.gradTolerance = S->gradTolerance; a.set.maxGoodResidual = S->maxGoodResidual; a.set.maxStep = S->maxStep;
-    a.set.maxLambda = S->maxLambda; a.set.minLambda = S->minLambda; a.set.minStepQuality = S->minStepQuality;
-    a.set.goodStepQuality = S->goodStepQuality; a.set.lambdaIncrease = S->lambdaIncrease; a.set.lambdaDecrease = S->lambdaDecrease;
-    a.set.qpRelTolerance = S->qpSettings.relTolerance; a.set.qpAbsTolerance = S->qpSettings.absTolerance;
-    a.set.qpMaxIterations = S->qpSettings.maxIterations; a.set.pad = 0;
+    a.set = lm_settings_dev(S);
     a.maxIterations = S->maxIterations; a.maxAge = S->maxAge; a.variant = opt ? opt->variant : 0;
     a.m = (int)m; a.grid = plan.grid; a.rows = plan.rows; a.groups = plan.groups;
     a.rowdata = rowdata; a.x = x; a.lower = lower; a.upper = upper; a.result = result;

@@ -106,15 +106,16 @@ def build_user_model_example(force=False, verbose=False):
     out = os.path.join(root, "tests", "user_model", "libuser_model.so")
     deps = [src, os.path.join(root, "include", "mir_optim_amd_batched.hpp"), os.path.join(root, "include", "mir_optim_amd.h"),
             os.path.join(CSRC, "batched_kernel.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "solve_types.h"),
+            os.path.join(CSRC, "lm_rules.h"),
             os.path.join(root, "include", "mir_optim_amd_resident.hpp"), os.path.join(CSRC, "resident_kernel.h"),
             os.path.join(CSRC, "solve_wave16.h"), os.path.join(CSRC, "solve_kernel.h"), os.path.join(CSRC, "solve_lds.h")]
     if force or _stale(out, deps):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out, src], verbose)
     src64, out64 = user_model_f64_paths()
-    if force or _stale(out64, [src64] + deps[1:6]):
+    if force or _stale(out64, [src64] + deps[1:7]):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out64, src64], verbose)
     srcw, outw = user_model_weighted_paths()
-    if force or _stale(outw, [srcw] + deps[1:6]):
+    if force or _stale(outw, [srcw] + deps[1:7]):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", outw, srcw], verbose)
     return out
 

@@ -502,7 +502,7 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
         const uint32_t maxAge = a.maxAge ? a.maxAge : (use_g ? 3u : 2u * N);     // LS:945
         { MIRLSQ_T0(); ret.residual = feval(x, yv); MIRLSQ_T1(0); }       // LS:953-955
         ++ret.fCalls;
-        bool fConverged = ret.residual <= S.maxGoodResidual;
+        bool fConverged = LM_F_CONVERGED(ret.residual, S);
         bool needJacobian = true;
         uint32_t age = maxAge;
         // J^T J and J^T y live one ROW per lane (row r = lane & 7 in every group of eight lanes), as posvx_rows wants them
@@ -520,8 +520,8 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
         ret.status = -1;                                                   // maxIterations, LS:971
         do {
             if (fConverged) { ret.status = 3; break; }                     // LS:974
-            if (!(lambda <= S.maxLambda)) { ret.status = 0; break; }       // LS:979
-            if (mu > T(16) && age) { needJacobian = true; age = maxAge; mu = 1; }   // LS:984
+            if (!LM_LAMBDA_IN_RANGE(lambda, S)) { ret.status = 0; break; } // LS:979
+            if (mu > kSuspiciousMu && age) { needJacobian = true; age = maxAge; mu = 1; }   // LS:984
             {
                 bool nan = false;
 #pragma unroll
@@ -644,12 +644,10 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
                     continue;
                 }
             }
-            if (!(lambda >= S.minLambda)) {                                // LS:1067-1072
+            if (!LM_LAMBDA_SET(lambda, S)) {                               // LS:1067-1072
                 // the largest diagonal element (a sum of squares: its own absolute value; a NaN is skipped as by `>`)
                 const T best = lane_get(rows_max(r < N ? vabs(MIRLSQ_ROW_PICK(JJrow, r)) : T(-1)), 0);
-                const T val = best < 0 ? T(0) : best;
-                lambda = lit<T>(0.001f, 0.001) * val;
-                if (!(lambda >= S.minLambda)) lambda = 1;
+                LM_LAMBDA0(lambda, best < 0 ? T(0) : best, S);
             }
             // LS:1079-1080 (-> QP:194). The four 16-lane groups of the wave solve with lambda and with the three values the
             // rejection rule (LS:1101-1106, 1125-1130: lambda *= lambdaIncrease mu, mu *= 2) would make of it next, at the
@@ -658,7 +656,7 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
             if (!(lad_valid && lad_level < lad_depth && lambda == lad_lam[lad_level])) {
                 T l = lambda, mm = mu;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) { lad_lam[g] = l; l *= S.lambdaIncrease * mm; mm *= 2; }
+                for (int g = 0; g < 4; ++g) { lad_lam[g] = l; LM_REJECT(l, mm, S); }
                 const int g = lane >> 4;
                 const T mine = g == 0 ? lad_lam[0] : (g == 1 ? lad_lam[1] : (g == 2 ? lad_lam[2] : lad_lam[3]));
                 T Prow[NMAX];
@@ -699,7 +697,7 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
                 ndd = __builtin_elementwise_fma(sol[j], sol[j], ndd);
                 trial[j] = vmax(vmin(sol[j] + x[j], up[j]), lo[j]);        // LS:1108-1110
             }
-            if (!(vsqrt(ndd) < S.maxStep)) { lambda *= S.lambdaIncrease * mu; mu *= 2; continue; }   // LS:1101-1106
+            if (!LM_STEP_ALLOWED(vsqrt(ndd), S)) { LM_REJECT(lambda, mu, S); continue; }   // LS:1101-1106
             ++ret.fCalls;                                                  // LS:1112-1115
 #ifdef MIRLSQ_BATCHED_TIMING
             tacc[6] += __builtin_readcyclecounter() - t6_;
@@ -712,7 +710,7 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
 #ifdef MIRLSQ_BATCHED_TIMING
             const uint64_t t7_ = __builtin_readcyclecounter();
 #endif
-            if (!(improvement > 0)) { lambda *= S.lambdaIncrease * mu; mu *= 2; continue; }   // LS:1125-1130
+            if (!(improvement > 0)) { LM_REJECT(lambda, mu, S); continue; }   // LS:1125-1130
             needJacobian = true;                                           // LS:1132-1139
             mu = 1;
             ret.iterations++;
@@ -720,7 +718,7 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
             for (int j = 0; j < NMAX; ++j) { x[j] = trial[j]; dx[j] = sol[j]; }
             { T* tmp = yv; yv = mB; mB = tmp; }                            // swap(mBuffer, y): mB = previous residual
             ret.residual = trialResidual;
-            fConverged = ret.residual <= S.maxGoodResidual;
+            fConverged = LM_F_CONVERGED(ret.residual, S);
             dx_dot = ndd;
             T pred = 0;                                                    // LS:1141-1142 (undamped JJ)
             {
@@ -734,15 +732,14 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
             pred = -pred;
             if (!(pred > 0)) { ret.status = 0; break; }                    // LS:1144-1148
             const T rho = pred / improvement;                              // LS:1150 (Q2)
-            if (rho < S.minStepQuality) { lambda *= S.lambdaIncrease * mu; mu *= 2; }
-            else if (rho >= S.goodStepQuality) lambda = vmax(S.lambdaDecrease * lambda * mu, S.minLambda);
+            LM_RATE_STEP(rho, lambda, mu, S);                              // LS:1152-1161
             T xn = 0;
 #pragma unroll
             for (int j = 0; j < NMAX; ++j) xn = __builtin_elementwise_fma(x[j], x[j], xn);
 #ifdef MIRLSQ_BATCHED_TIMING
             tacc[7] += __builtin_readcyclecounter() - t7_;
 #endif
-            if (!(vsqrt(dx_dot) > S.absTolerance && vsqrt(xn) > vsqrt(dx_dot) * S.relTolerance)) {   // LS:1164-1173 (Q6)
+            if (!LM_X_MOVING(vsqrt(dx_dot), vsqrt(xn), S)) {               // LS:1164-1173 (Q6)
                 if (age == 0) { ret.status = 1; break; }
                 age = maxAge;
                 continue;

@@ -221,8 +221,7 @@ __device__ inline int decide_chain_body(const DecideArgs<T>& a, const DecidePre<
             s.qp_status = r.qp_status; s.qp_iterations = r.qp_iterations; s.flags = r.flags;
             if (r.qp_status != 0 || (r.flags & kFlagDxNaN)) { dec = kDecideNumericError; break; }   // LS:1080-1092
             if (r.flags & kFlagStepTooLong) {                                 // LS:1101-1106
-                s.lambda *= a.set.lambdaIncrease * s.mu;
-                s.mu *= 2;
+                LM_REJECT(s.lambda, s.mu, a.set);
                 ++guards;
                 continue;
             }
@@ -237,8 +236,7 @@ __device__ inline int decide_chain_body(const DecideArgs<T>& a, const DecidePre<
             const T improvement = s.residual - tr;                            // LS:1124
             s.improvement = improvement;
             if (!(improvement > 0)) {                                         // LS:1125-1130
-                s.lambda *= a.set.lambdaIncrease * s.mu;
-                s.mu *= 2;
+                LM_REJECT(s.lambda, s.mu, a.set);
                 ++rejects;
                 continue;
             }
@@ -253,12 +251,7 @@ __device__ inline int decide_chain_body(const DecideArgs<T>& a, const DecidePre<
             if (!(r.predicted > 0)) { dec = kDecideAcceptNoPrediction; break; }   // LS:1144-1148
             const T rho = r.predicted / improvement;                          // LS:1150 (quirk Q2)
             s.rho = rho;
-            if (rho < a.set.minStepQuality) {                                 // LS:1152-1156
-                s.lambda *= a.set.lambdaIncrease * s.mu;
-                s.mu *= 2;
-            } else if (rho >= a.set.goodStepQuality) {                        // LS:1158-1161
-                s.lambda = dfmax(a.set.lambdaDecrease * s.lambda * s.mu, a.set.minLambda);
-            }
+            LM_RATE_STEP(rho, s.lambda, s.mu, a.set);                         // LS:1152-1161
             dec = kDecideAccept;
             break;
         }
@@ -269,8 +262,8 @@ __device__ inline int decide_chain_body(const DecideArgs<T>& a, const DecidePre<
         // expression on the same record, says whether it ran in full).
         int spec = 0;
         if (a.spec_static && dec == kDecideAccept && acc == 0) {
-            spec = !(s.residual <= a.set.maxGoodResidual) && s.iterations < a.maxIterations && (s.lambda <= a.set.maxLambda)
-                && (s.lambda >= a.set.minLambda) && lr_spec_go(a.rec[0], a.set.absTolerance, a.set.relTolerance);
+            spec = LM_PASS_MAY_START(s.residual, s.lambda, s.iterations, a.maxIterations, a.set)
+                && LM_LAMBDA_SET(s.lambda, a.set) && lr_spec_go(a.rec[0], a.set.absTolerance, a.set.relTolerance);
         }
         s.spec_ok = spec;
         uint32_t rescued = 0;

@@ -593,7 +593,7 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
             if (phase == 0) {                                                  // LS:953-971
                 ++fCalls;
                 residual = ss_total;
-                fConverged = residual <= a.set.maxGoodResidual;
+                fConverged = LM_F_CONVERGED(residual, a.set);
                 needJac = true; age = maxAge; lambda = 0; mu = 1; iterations = 0; dx_dot = 0;
                 next_pre |= kResPreAccept;                                     // the vector just evaluated IS y
                 // validation of x0 and the bounds, LS:930-932 (the settings were checked on the host)
@@ -618,8 +618,8 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
                 if (where == kTop) {
                     ++n_passes;
                     if (fConverged) { status = mir_ls_fConverged; where = kDone; break; }                           // LS:974
-                    if (!(lambda <= a.set.maxLambda)) { status = mir_ls_furtherImprovement; where = kDone; break; } // LS:979
-                    if (mu > 16.0 && age) { needJac = true; age = maxAge; mu = 1; }                                 // LS:984
+                    if (!LM_LAMBDA_IN_RANGE(lambda, a.set)) { status = mir_ls_furtherImprovement; where = kDone; break; } // LS:979
+                    if (mu > kSuspiciousMu && age) { needJac = true; age = maxAge; mu = 1; }                        // LS:984
                     if (x_nan) { status = mir_ls_numericError; where = kDone; break; }                              // LS:990
                     newJac = false;
                     if (needJac) {                                             // LS:996
@@ -680,20 +680,19 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
                             ? fmax(8.0 * sqrt(j2) / (0x1p-54 * xm), 1e-6 * dg) : Lim<double>::inf();
                         null_lambda_for = 2;
                     }
-                    if (!newJac && lambda > null_lambda && lambda >= a.set.minLambda && !(a.variant & kResVariantNoNullSkip)) {
+                    if (!newJac && lambda > null_lambda && LM_LAMBDA_SET(lambda, a.set) && !(a.variant & kResVariantNoNullSkip)) {
                         ++fCalls;                                              // LS:1112
                         ++n_elided;
                         ++n_rej;
                         trace(2, iterations, lambda, residual, residual, 0.0);
-                        lambda *= a.set.lambdaIncrease * mu;
-                        mu *= 2;
+                        LM_REJECT(lambda, mu, a.set);
                         where = kCond;
                         continue;
                     }
                     // LS:1052-1110, 1141-1142 on this workgroup: gradient test, lambda_0, solveBoxQP, rounding, trial, prediction
                     long long ts0 = 0;
                     if (clk) ts0 = wall_clock64();
-                    const bool from_state = !(lambda >= a.set.minLambda);
+                    const bool from_state = !LM_LAMBDA_SET(lambda, a.set);
                     ChainRec<double> rec{};
                     if constexpr (WAVE) {
                         // a pass after a rejection finds its step in the ladder the last solve made (same J^T J, J^T y, x; its
@@ -741,8 +740,7 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
                     if (rec.flags & kFlagStepTooLong) {                        // LS:1101-1106
                         trace(4, iterations, lambda, residual, 0, s_ndd);
                         ++n_guard;
-                        lambda *= a.set.lambdaIncrease * mu;
-                        mu *= 2;
+                        LM_REJECT(lambda, mu, a.set);
                         where = kCond;
                         continue;
                     }
@@ -753,8 +751,7 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
                         ++n_elided;
                         ++n_rej;
                         trace(2, iterations, lambda, residual, residual, s_ndd);
-                        lambda *= a.set.lambdaIncrease * mu;
-                        mu *= 2;
+                        LM_REJECT(lambda, mu, a.set);
                         where = kCond;
                         continue;
                     }
@@ -803,8 +800,7 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
                                 trace(2, iterations, s_lam_used, residual, ahead, s_ndd);
                                 ++n_rej;
                                 ++n_look;
-                                lambda *= a.set.lambdaIncrease * mu;
-                                mu *= 2;
+                                LM_REJECT(lambda, mu, a.set);
                                 where = kCond;
                                 continue;
                             }
@@ -825,8 +821,7 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
                         trace(2, iterations, s_lam_used, residual, trialResidual, s_ndd);
                         ++n_rej;
                         x_nan = false;
-                        lambda *= a.set.lambdaIncrease * mu;
-                        mu *= 2;
+                        LM_REJECT(lambda, mu, a.set);
                         where = kCond;
                         continue;
                     }
@@ -839,15 +834,14 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
                     __syncthreads();
                     next_pre |= kResPreAccept;
                     residual = trialResidual;
-                    fConverged = residual <= a.set.maxGoodResidual;
+                    fConverged = LM_F_CONVERGED(residual, a.set);
                     dx_dot = s_ndd;
                     trace(3, iterations, s_lam_used, residual, trialResidual, s_ndd);
                     if (!(s_pred > 0)) { status = mir_ls_furtherImprovement; where = kDone; break; }             // LS:1144-1148
                     const double rho = s_pred / improvement;                   // LS:1150 (quirk Q2)
-                    if (rho < a.set.minStepQuality) { lambda *= a.set.lambdaIncrease * mu; mu *= 2; }
-                    else if (rho >= a.set.goodStepQuality) lambda = fmax(a.set.lambdaDecrease * lambda * mu, a.set.minLambda);
+                    LM_RATE_STEP(rho, lambda, mu, a.set);                      // LS:1152-1161
                     const double dxn = sqrt(dx_dot);                           // LS:1164-1173 (quirk Q6)
-                    if (!(dxn > a.set.absTolerance && s_xnorm > dxn * a.set.relTolerance)) {
+                    if (!LM_X_MOVING(dxn, s_xnorm, a.set)) {
                         if (age == 0) { status = mir_ls_xConverged; where = kDone; break; }
                         age = maxAge;
                     }
@@ -880,7 +874,7 @@ __global__ __launch_bounds__(res_threads(Model::n)) void k_lm_resident(ResidentA
                         for (int l = lad_level + 1; l < 4 && nl < kResLookMax; ++l) {
                             if (lreci[4 * l + 3] == 0 || lreci[4 * l] != 0) break;
                             if (lreci[4 * l + 2] & (kFlagDxNaN | kFlagStepTooLong | kFlagNullStep | kFlagGradSmall | kFlagXNaN)) break;
-                            if (!(lrec[8 * l] <= a.set.maxLambda)) break;
+                            if (!LM_LAMBDA_IN_RANGE(lrec[8 * l], a.set)) break;
                             ++nl;
                         }
                     }

@@ -756,7 +756,7 @@ __device__ __forceinline__ void lm_solve_big_main(const LmSolveArgs<T>& a, int k
     }
     // lambda_0, LS:1067-1072: the FIRST diagonal entry of maximum modulus, as i?amax picks it
     T lambda = (kc == 0 && (a.lambda_from_state || a.lambda_from_device)) ? a.st->lambda : a.lam[kc];
-    if (kc == 0 && a.lambda_from_state && !(lambda >= a.set.minLambda)) {
+    if (kc == 0 && a.lambda_from_state && !LM_LAMBDA_SET(lambda, a.set)) {
         T best = -1;
         int where = 0x7fffffff;
         for (int i = tid; i < n; i += kBigThreads) {
@@ -772,8 +772,7 @@ __device__ __forceinline__ void lm_solve_big_main(const LmSolveArgs<T>& a, int k
         __syncthreads();
         int first = sm.ired[0];
         for (int wv = 1; wv < kBigWaves; ++wv) first = sm.ired[wv] < first ? sm.ired[wv] : first;
-        lambda = T(0.001) * a.JJ[(size_t)first * n + first];
-        if (!(lambda >= a.set.minLambda)) lambda = 1;
+        LM_LAMBDA0(lambda, a.JJ[(size_t)first * n + first], a.set);
         __syncthreads();
     }
     // step bounds LS:1074-1077; Pm = A = JJ + lambda I, LS:1078-1079
@@ -879,7 +878,7 @@ __device__ __forceinline__ void lm_solve_big_main(const LmSolveArgs<T>& a, int k
         if (amax > 0)
             for (int i = tid; i < n; i += kBigThreads) { const T v = trial_out[i] / amax; sc2 += v * v; }
         xn = amax > 0 ? amax * dsqrt(big_sum(sc2, sm.red)) : T(0);
-        if (!(dsqrt(ndd) < a.set.maxStep)) flags |= kFlagStepTooLong; // LS:1101
+        if (!LM_STEP_ALLOWED(dsqrt(ndd), a.set)) flags |= kFlagStepTooLong;   // LS:1101
     }
     MIRLSQ_STAMP(sc.dbg, 8);
     if (sc.dbg && threadIdx.x == 0) sc.dbg[10] = clock64();

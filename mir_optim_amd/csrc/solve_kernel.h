@@ -760,7 +760,7 @@ __device__ __forceinline__ void lm_solve_body(const LmSolveArgs<T>& a, const int
 
     // lambda_0, LS:1067-1072 (first element of maximum |diag|, as i?amax picks it)
     T lambda = (kc == 0 && (a.lambda_from_state || a.lambda_from_device)) ? a.st->lambda : a.lam[kc];
-    if (kc == 0 && a.lambda_from_state && !(lambda >= a.set.minLambda)) {
+    if (kc == 0 && a.lambda_from_state && !LM_LAMBDA_SET(lambda, a.set)) {
         const T dg = tid < n ? dabs(a.JJ[(size_t)tid * n + tid]) : T(-1);
         const T mx = block_max(dg, red);
         int cand = (tid < n && dg == mx) ? tid : 0x7fffffff;
@@ -771,8 +771,7 @@ __device__ __forceinline__ void lm_solve_body(const LmSolveArgs<T>& a, const int
         __syncthreads();
         int first = ired[4];
         for (int wv = 1; wv < kSolveThreads / kWave; ++wv) first = ired[4 + wv] < first ? ired[4 + wv] : first;
-        lambda = T(0.001) * a.JJ[(size_t)first * n + first];
-        if (!(lambda >= a.set.minLambda)) lambda = 1;
+        LM_LAMBDA0(lambda, a.JJ[(size_t)first * n + first], a.set);
     }
 
     // step bounds LS:1074-1077, P = JJ + lambda I LS:1078-1079 (JJ itself is never modified, so
@@ -949,7 +948,7 @@ __device__ __forceinline__ void lm_solve_body(const LmSolveArgs<T>& a, const int
             if (tid < n && amx > 0) { const T v = tr / amx; sc2 = v * v; }
             xn = amx > 0 ? amx * dsqrt(block_sum(sc2, red)) : T(0);
         }
-        if (!(dsqrt(ndd) < a.set.maxStep)) flags |= kFlagStepTooLong; // LS:1101
+        if (!LM_STEP_ALLOWED(dsqrt(ndd), a.set)) flags |= kFlagStepTooLong;   // LS:1101
     }
     MIRLSQ_STAMP(sc.dbg, 8);
     if (sc.dbg && threadIdx.x == 0) sc.dbg[10] = clock64();

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "common.h"
+#include "lm_rules.h"
 
 namespace mirlsq {
 
@@ -50,13 +51,6 @@ constexpr int32_t kQpCoopTimeout = 3;
 enum : int32_t {
     kDecideNone = 0, kDecideReject = 1, kDecideAccept = 2, kDecideAcceptNoPrediction = 3,
     kDecideNumericError = 4, kDecideGradSmall = 5
-};
-
-template <typename T>
-struct LmSettingsDev {   // the floating-point part of LeastSquaresSettings!T (LS:85-123)
-    T jacobianEpsilon, absTolerance, relTolerance, gradTolerance, maxGoodResidual, maxStep, maxLambda,
-      minLambda, minStepQuality, goodStepQuality, lambdaIncrease, lambdaDecrease, qpRelTolerance, qpAbsTolerance;
-    uint32_t qpMaxIterations, pad;
 };
 
 template <typename T>

@@ -161,21 +161,20 @@ __device__ __forceinline__ void wave16_lm_solve(const double (&JJrow)[kW16], dou
         const double jy_inf = row16_max(el ? fabs(Jy_r) : 0.0);
         if (!(jy_inf > set.gradTolerance)) { out.flags = kFlagGradSmall; return; }
     }
-    if (from_state && !(lambda >= set.minLambda)) {              // LS:1067-1072: the FIRST entry of maximum |diag|, as i?amax picks it
+    if (from_state && !LM_LAMBDA_SET(lambda, set)) {         // LS:1067-1072: the FIRST entry of maximum |diag|, as i?amax picks it
         const double ad = el ? fabs(djj) : -1.0;
         const double mx = row16_max(ad);
         const unsigned hit = group_bits(el && ad == mx, g);
         const int first = hit ? __builtin_ctz(hit) : 0;
         const double dfirst = __shfl(djj, 16 * g + first, 64);
-        lambda = 0.001 * dfirst;
-        if (!(lambda >= set.minLambda)) lambda = 1;
+        LM_LAMBDA0(lambda, dfirst, set);
     }
     // the ladder: group g solves with the damping g rejections from now would leave (LS:1103-1104, 1127-1128)
     double lam_g = lambda;
     {
         double l = lambda, mm = mu;
 #pragma unroll
-        for (int k = 1; k < 4; ++k) { l *= set.lambdaIncrease * mm; mm *= 2; lam_g = (g == k && !single) ? l : lam_g; }
+        for (int k = 1; k < 4; ++k) { LM_REJECT(l, mm, set); lam_g = (g == k && !single) ? l : lam_g; }
     }
     out.lambda = lam_g;
     const double qpl = lo_r - x_r, qpu = up_r - x_r;              // LS:1074-1077
@@ -293,7 +292,7 @@ __device__ __forceinline__ void wave16_lm_solve(const double (&JJrow)[kW16], dou
     double sc2 = 0;
     if (el && amx > 0) { const double v = tr / amx; sc2 = v * v; }
     const double xn = amx > 0 ? amx * sqrt(row16_sum(sc2)) : 0.0;
-    if (!(sqrt(ndd) < set.maxStep)) flags |= kFlagStepTooLong;                                // LS:1101
+    if (!LM_STEP_ALLOWED(sqrt(ndd), set)) flags |= kFlagStepTooLong;                          // LS:1101
     out.ndd = ndd; out.pred = pred; out.xnorm = xn; out.flags = flags;
     dx_out = d; trial_out = tr;
 }

@@ -70,12 +70,7 @@ bool Solver<T>::setup()
         if (!ok(hipStreamCreate(&stream), "hipStreamCreate")) return false;
         own_stream = true;
     }
-    sd.jacobianEpsilon = S->jacobianEpsilon; sd.absTolerance = S->absTolerance; sd.relTolerance = S->relTolerance;
-    sd.gradTolerance = S->gradTolerance; sd.maxGoodResidual = S->maxGoodResidual; sd.maxStep = S->maxStep;
-    sd.maxLambda = S->maxLambda; sd.minLambda = S->minLambda; sd.minStepQuality = S->minStepQuality;
-    sd.goodStepQuality = S->goodStepQuality; sd.lambdaIncrease = S->lambdaIncrease; sd.lambdaDecrease = S->lambdaDecrease;
-    sd.qpRelTolerance = S->qpSettings.relTolerance; sd.qpAbsTolerance = S->qpSettings.absTolerance;
-    sd.qpMaxIterations = S->qpSettings.maxIterations; sd.pad = 0;
+    sd = lm_settings_dev(S);
     dbg_solve = (variant & MIR_LSQ_VARIANT_DEBUG_SOLVE) != 0;
     no_speculation = (variant & MIR_LSQ_VARIANT_NO_SPECULATION) != 0;
     lowrank = (variant & MIR_LSQ_VARIANT_BROYDEN_REWRITE) == 0;
@@ -464,7 +459,7 @@ typename Solver<T>::Result Solver<T>::run()
     if (fail) { teardown(); ret.status = mir_ls_numericError; return ret; }
 
     ret.residual = st_h->residual;
-    bool fConverged = ret.residual <= S->maxGoodResidual;                // LS:956
+    bool fConverged = LM_F_CONVERGED(ret.residual, sd);                  // LS:956
     bool needJacobian = true;                                            // LS:959
     bool last_rejected = false;
     bool spec_live = false;            // the Jacobian side and the solve of the round at the top of the loop have run already (fused round)
@@ -473,15 +468,14 @@ typename Solver<T>::Result Solver<T>::run()
     uint32_t age = maxAge;
     ret.lambda = 0;
     T mu = 1;
-    const T suspiciousMu = 16;
     ret.status = mir_ls_maxIterations;                                   // LS:971
 
     do {
         close_round();
         if (stats) stats->passes++;
         if (fConverged) { ret.status = mir_ls_fConverged; break; }       // LS:974-978
-        if (!(ret.lambda <= S->maxLambda)) { ret.status = mir_ls_furtherImprovement; break; }   // LS:979-983
-        if (mu > suspiciousMu && age) {                                  // LS:984-989
+        if (!LM_LAMBDA_IN_RANGE(ret.lambda, sd)) { ret.status = mir_ls_furtherImprovement; break; }   // LS:979-983
+        if (mu > kSuspiciousMu && age) {                                 // LS:984-989
             needJacobian = true;
             age = maxAge;
             mu = 1;
@@ -551,16 +545,15 @@ typename Solver<T>::Result Solver<T>::run()
         // first accepted one are discarded, so results, counters and callback-visible semantics of accepted
         // points are unchanged. The ladder stops where the reference's top-of-loop checks would intervene
         // (lambda > maxLambda LS:979, forced refresh LS:984).
-        lambda_from_state = !solve_enqueued && !(ret.lambda >= S->minLambda);   // first pass: lambda_0 rule inside the kernel
+        lambda_from_state = !solve_enqueued && !LM_LAMBDA_SET(ret.lambda, sd);   // first pass: lambda_0 rule inside the kernel
         T lam[kChainMax];
         lam[0] = ret.lambda;
         if (speculate && !newJacobian && !lambda_from_state && last_rejected) {
             T l2 = ret.lambda, m2 = mu;
             while (ks < kChainMax) {
-                l2 *= S->lambdaIncrease * m2;
-                m2 *= 2;
-                if (!(l2 <= S->maxLambda)) break;                         // LS:979 would exit there
-                if (m2 > suspiciousMu && age) break;                      // LS:984 would force a refresh there
+                LM_REJECT(l2, m2, sd);                                    // LS:1103-1104, 1127-1128
+                if (!LM_LAMBDA_IN_RANGE(l2, sd)) break;                   // LS:979 would exit there
+                if (m2 > kSuspiciousMu && age) break;                     // LS:984 would force a refresh there
                 lam[ks++] = l2;
             }
         }
@@ -652,13 +645,13 @@ typename Solver<T>::Result Solver<T>::run()
         }
         { T* t = mB; mB = y; y = fr; fr = t; }                           // swap(mBuffer, y) of LS:1136 as a rotation of three
         ret.residual = st_h->residual;
-        fConverged = ret.residual <= S->maxGoodResidual;
+        fConverged = LM_F_CONVERGED(ret.residual, sd);
         if (stats) stats->accepted++;
 
         if (dec == kDecideAcceptNoPrediction) { ret.status = mir_ls_furtherImprovement; break; }   // LS:1144-1148
 
         const T dxn = std::sqrt(st_h->dx_dot);                           // LS:1164-1173 (quirk Q6)
-        if (!(dxn > S->absTolerance && st_h->trial_xnorm > dxn * S->relTolerance)) {
+        if (!LM_X_MOVING(dxn, st_h->trial_xnorm, sd)) {
             if (age == 0) { ret.status = mir_ls_xConverged; break; }
             age = maxAge;
             continue;

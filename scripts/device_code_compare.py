@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Per-kernel comparison of the gfx950 device code of two trees (profiles/r08, r09: device_code_compare.txt).
+
+    python scripts/device_code_compare.py PARENT_TREE BRANCH_TREE OUT_DIR
+
+Compiles every unit that carries kernels in both trees with build.py's flags and `--offload-device-only -S` into
+OUT_DIR/{parent,branch}/<unit>.s, then compares per kernel the function body (label to .Lfunc_end) and the .amdhsa_kernel
+block as text after local labels are normalised, and prints VGPR / AGPR / scratch / static LDS from the kernels' metadata; for
+a kernel that differs also whether the instruction counts per opcode agree."""
+import collections
+import os
+import re
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only", "-S"]
+UNITS = ["solver_loop", "launch_solve_d", "launch_solve_s", "unit_entries", "batched", "batched_d", "workloads_resident", "workloads",
+         "workloads_gemm", "solver_jacobian", "launch_jtj", "launch_broyden", "comm"]
+USER = ["user_model", "user_model_f64", "user_model_weighted"]
+
+
+def compile_tree(tree, out):
+    os.makedirs(out, exist_ok=True)
+    cmds = [["hipcc"] + FLAGS + (["-fopenmp"] if u.startswith("workloads") else []) + ["mir_optim_amd/csrc/%s.hip" % u, "-o", "%s/%s.s" % (out, u)]
+            for u in UNITS]
+    cmds += [["hipcc"] + FLAGS + ["-I", "include", "tests/user_model/%s.hip" % u, "-o", "%s/%s.s" % (out, u)] for u in USER]
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        list(ex.map(lambda c: subprocess.check_call(c, cwd=tree, stderr=subprocess.DEVNULL), cmds))
+
+
+def norm(t):
+    t = re.sub(r"BB[0-9]+_", "BB_", t)
+    t = re.sub(r"Lfunc_(end|begin)[0-9]+", r"Lfunc_\1", t)
+    return re.sub(r"[ \t]+", " ", t)
+
+
+def kernels(path):
+    s = open(path).read()
+    code = {}
+    for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", s, re.M | re.S):
+        body = re.search(r"^" + re.escape(m.group(1)) + r":.*?^\.Lfunc_end[0-9]+:", s, re.M | re.S).group(0)
+        code[m.group(1)] = (norm(body), norm(m.group(2)))
+    res = {}
+    for m in re.finditer(r"- \.agpr_count:\s+(\d+).*?\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?"
+                         r"\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)", s, re.S):
+        res[m.group(3)] = (int(m.group(5)), int(m.group(1)), int(m.group(4)), int(m.group(2)))
+    return code, res
+
+
+def opcounts(body):
+    c = collections.Counter()
+    for line in body.splitlines():
+        line = line.strip()
+        if line and not line.startswith((".", ";")) and not line.endswith(":"):
+            c[line.split()[0]] += 1
+    return c
+
+
+def demangle(names):
+    p = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True)
+    return dict(zip(names, p.stdout.splitlines()))
+
+
+def main(parent, branch, out):
+    pd, bd = os.path.join(out, "parent"), os.path.join(out, "branch")
+    compile_tree(parent, pd)
+    compile_tree(branch, bd)
+    tot = same = 0
+    for u in UNITS + USER:
+        pk, pr = kernels("%s/%s.s" % (pd, u))
+        bk, br = kernels("%s/%s.s" % (bd, u))
+        dm = demangle(sorted(set(pk) | set(bk)))
+        print("== %s: %d kernels in the parent, %d in the branch" % (u, len(pk), len(bk)))
+        for k in pk:
+            print("  " + dm[k])
+            if k not in bk:
+                print("      only in the parent")
+                continue
+            tot += 1
+            ident = pk[k] == bk[k]
+            same += ident
+            extra = ""
+            if not ident:
+                extra = "   [instruction counts per opcode: %s; .amdhsa_kernel block: %s]" % (
+                    "equal" if opcounts(pk[k][0]) == opcounts(bk[k][0]) else "differ", "equal" if pk[k][1] == bk[k][1] else "differs")
+            print("      body + .amdhsa_kernel block identical: %s   VGPR %d/%d  AGPR %d/%d  scratch %d/%d  static LDS %d/%d  (parent/branch)%s"
+                  % (("yes" if ident else "NO",) + tuple(v for pair in zip(pr[k], br[k]) for v in pair) + (extra,)))
+        for k in bk:
+            if k not in pk:
+                print("  " + dm[k] + "\n      only in the branch")
+    print("== total: %d kernels present in both trees, %d text-identical" % (tot, same))
+    return 0 if tot == same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3])))
