@@ -566,6 +566,47 @@ int mir_lsq_fd_diff_jtj_d(size_t m, size_t n, const double* Drm, const double* t
  * the slab reduction is given (0: the tile pairs' own reduction), slab elements a workspace holds }. Returns 0, or -1 (arguments). */
 int mir_lsq_jtj_plan(size_t elem_size, size_t m, size_t n, int num_cu, int op, int aligned16, size_t out[10]);
 
+/* Covariance of the fitted parameters of the general solver: cov = s^2 inv(J^T J) at x (usually the x a solve returned), from
+ * ONE full Jacobian refresh made exactly as a refresh of the solve makes it (g if given, else finite differences through the
+ * same callbacks, options->fb / fbRowMajor / fbRowMajorDiff, fd_batch and clipping of x +- jacobianEpsilon to [l, u]), the J^T J
+ * kernel of the solve (all-reduced over options->comm) and an SPD inverse on the device; nothing of the LM loop runs and x is not
+ * written. s^2 = ||f(x)||^2 / (M - n_free): M the rows of all ranks, n_free the parameters with l_j < u_j; with
+ * MIR_LSQ_COVARIANCE_ABSOLUTE_SIGMA s^2 = 1; with M - n_free <= 0 every free entry is +inf. A parameter with l_j == u_j is
+ * fixed: its row and column are 0. A parameter ON a bound with l_j < u_j is not fixed (its difference is one-sided or narrower).
+ * options->workspace, stream, comm, stats (the refresh and callbacks are counted in the existing fields) are honoured, trace is
+ * ignored; the n x n scratch comes from the workspace, a workspace stays usable by later solves.
+ * cov: HOST, n x n row-major. Returns 0 (cov written; *info as the inverse's: nonzero -> +inf at the free entries),
+ * mir_ls_badGuess (-31: x NULL or not finite, m == 0, n == 0), mir_ls_badBounds (-32), the status of a bad setting, -1 (settings,
+ * l, u, cov or f NULL), or mir_ls_numericError (-26) when no device is usable or a launch failed. These are answered before a
+ * device is touched, except the last. residual_out (optional): ||f(x)||^2; info (optional). n <= 20480 (double), 40960 (float). */
+enum { MIR_LSQ_COVARIANCE_ABSOLUTE_SIGMA = 1u };
+int mir_lsq_covariance_gpu_d(const mir_least_squares_settings_d* settings, size_t m, size_t n,
+    const double* x, const double* l, const double* u, const mir_lsq_gpu_options* options,
+    void* fContext, mir_least_squares_function_d f, void* gContext, mir_least_squares_jacobian_d g,
+    void* tmContext, mir_least_squares_thread_manager tm,
+    uint32_t flags, double* cov, double* residual_out, int* info);
+int mir_lsq_covariance_gpu_s(const mir_least_squares_settings_s* settings, size_t m, size_t n,
+    const float* x, const float* l, const float* u, const mir_lsq_gpu_options* options,
+    void* fContext, mir_least_squares_function_s f, void* gContext, mir_least_squares_jacobian_s g,
+    void* tmContext, mir_least_squares_thread_manager tm,
+    uint32_t flags, float* cov, float* residual_out, int* info);
+/* Unit-level access to the inverse (csrc/spd_inverse.h): X = inv(P), equilibrated as ?posvx('E') and factored by a lower
+ * Cholesky. DEVICE pointers; P n x n row-major (lower triangle read); fixed: n bytes or NULL -- a nonzero byte takes that index
+ * out of the system (its row and column of P are not read and are 0 in X); X n x n, symmetric to the bit; info: device int, 0 or
+ * the 1-based order, among the free indices, of the first leading minor that is not positive (a NaN included): every free entry
+ * of X is then +inf. Deterministic. The call allocates its scratch, enqueues on `stream` (NULL = default stream) and
+ * synchronises that stream before it returns, as mir_lsq_jtj_*. Returns 0, -1 (n == 0, n too large, NULL pointer), -2 (no
+ * device), -3 (allocation), -4 (launch), -5 (synchronisation). */
+int mir_lsq_spd_inverse_d(size_t n, const double* P, const unsigned char* fixed, double* X, int* info, void* stream);
+int mir_lsq_spd_inverse_s(size_t n, const float*  P, const unsigned char* fixed, float*  X, int* info, void* stream);
+/* The same with caller-owned DEVICE scratch of mir_lsq_spd_inverse_work_bytes(n, element size) bytes: two launches enqueued
+ * on `stream`, no allocation and no synchronisation (what a caller times, or runs behind its own kernels). */
+size_t mir_lsq_spd_inverse_work_bytes(size_t n, size_t elem_size);
+int mir_lsq_spd_inverse_work_d(size_t n, const double* P, const unsigned char* fixed, double* X, int* info, void* work,
+                               size_t work_bytes, void* stream);
+int mir_lsq_spd_inverse_work_s(size_t n, const float* P, const unsigned char* fixed, float* X, int* info, void* work,
+                               size_t work_bytes, void* stream);
+
 /* Workspace: device buffers for one (m, n, element size) problem, reusable across calls. */
 mir_lsq_workspace* mir_lsq_workspace_create(size_t m, size_t n, size_t elem_size);
 void mir_lsq_workspace_destroy(mir_lsq_workspace* ws);

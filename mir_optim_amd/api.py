@@ -35,6 +35,7 @@ __all__ = [
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
     "VARIANT_SOLVE_BOUNDED", "VARIANT_DEBUG_SOLVE", "VARIANT_HOST_PROFILE", "VARIANT_SOLVE_GENERIC", "VARIANT_SOLVE_ONE_WORKGROUP", "VARIANT_DEBUG_HELPERS_ABSENT", "VARIANT_FD_HOST_COLUMNS",
     "VARIANT_NO_PIPELINE", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA",
+    "covariance", "spdInverse", "COVARIANCE_ABSOLUTE_SIGMA",
 ]
 
 MODEL_EXP_DECAY = 0      # n = 3: p0 exp(-t p1) + p2
@@ -280,6 +281,19 @@ def lib():
             fn.restype = C.c_int
             fn.argtypes = [sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.POINTER(C.c_float)]
+            fn = getattr(L, "mir_lsq_covariance_gpu_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [C.POINTER(S), sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GpuOptions),
+                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+            fn = getattr(L, "mir_lsq_spd_inverse_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            fn = getattr(L, "mir_lsq_spd_inverse_work_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p]
+        L.mir_lsq_spd_inverse_work_bytes.restype = sz
+        L.mir_lsq_spd_inverse_work_bytes.argtypes = [sz, sz]
         L.mir_lsq_comm_create_local_group.restype = C.c_int
         L.mir_lsq_comm_create_local_group.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.mir_lsq_fd_diff_jtj_d.restype = C.c_int
@@ -505,24 +519,10 @@ def _as_fnptr(cb, ftype, wrap, keep):
     return C.c_void_p(int(cb))
 
 
-def optimizeLeastSquares(f, m, x, l=None, u=None, g=None, tm=None, settings=None, dtype=np.float64,
-                         fContext=None, gContext=None, options=None, gpu_entry=None):
-    """High level nothrow API (LS:459-519). `x` is updated in place (numpy array) and returned with the result.
-
-    f, g : python callables f(x, y) / g(x, J) working on numpy views of HOST memory (y and J are
-           zero-filled before the call like the template tier does, LS:469, LS:482), or integer
-           addresses of native callbacks (then fContext / gContext are passed through).
-    tm   : optional python thread manager tm(count, task) where task(totalThreads, threadId, i)
-           must be called for every i in [0, count) (LS:575-578).
-    options : GpuOptions for the additive entry point (device callbacks, comm, stats, ...)."""
-    L = lib()
-    dbl = dtype == np.float64
-    x = np.ascontiguousarray(x, dtype=dtype)
-    n = x.size
-    lo = np.full(n, -np.inf, dtype=dtype) if l is None else np.ascontiguousarray(l, dtype=dtype)
-    up = np.full(n, np.inf, dtype=dtype) if u is None else np.ascontiguousarray(u, dtype=dtype)
-    if settings is None:
-        settings = LeastSquaresSettings(dtype)
+def _wrap_callbacks(f, g, tm, dtype):
+    """The C function pointers of f, g and tm for a call (python callables are wrapped, integer addresses passed through).
+    Returns (fptr, gptr, tmptr, keep, errors): `keep` holds the ctypes thunks alive for the duration of the call, `errors`
+    collects what the python callbacks raised."""
     ft = _ftype(dtype)
     keep = []
     errors = []      # exceptions raised inside Python callbacks: ctypes would print and swallow them and the solve would go
@@ -565,6 +565,28 @@ def optimizeLeastSquares(f, m, x, l=None, u=None, g=None, tm=None, settings=None
         tmc = TM_FN(tm_cb)
         keep.append(tmc)
         tmptr = C.cast(tmc, C.c_void_p)
+    return fptr, gptr, tmptr, keep, errors
+
+
+def optimizeLeastSquares(f, m, x, l=None, u=None, g=None, tm=None, settings=None, dtype=np.float64,
+                         fContext=None, gContext=None, options=None, gpu_entry=None):
+    """High level nothrow API (LS:459-519). `x` is updated in place (numpy array) and returned with the result.
+
+    f, g : python callables f(x, y) / g(x, J) working on numpy views of HOST memory (y and J are
+           zero-filled before the call like the template tier does, LS:469, LS:482), or integer
+           addresses of native callbacks (then fContext / gContext are passed through).
+    tm   : optional python thread manager tm(count, task) where task(totalThreads, threadId, i)
+           must be called for every i in [0, count) (LS:575-578).
+    options : GpuOptions for the additive entry point (device callbacks, comm, stats, ...)."""
+    L = lib()
+    dbl = dtype == np.float64
+    x = np.ascontiguousarray(x, dtype=dtype)
+    n = x.size
+    lo = np.full(n, -np.inf, dtype=dtype) if l is None else np.ascontiguousarray(l, dtype=dtype)
+    up = np.full(n, np.inf, dtype=dtype) if u is None else np.ascontiguousarray(u, dtype=dtype)
+    if settings is None:
+        settings = LeastSquaresSettings(dtype)
+    fptr, gptr, tmptr, keep, errors = _wrap_callbacks(f, g, tm, dtype)
     use_gpu_entry = gpu_entry if gpu_entry is not None else (options is not None)
     suf = "d" if dbl else "s"
     if use_gpu_entry:
@@ -696,6 +718,73 @@ def batchedPosvx(P, rhs, dtype=np.float32):
     for b in (dP, db, dx, di):
         b.free()
     return x, info
+
+
+COVARIANCE_ABSOLUTE_SIGMA = 1      # MIR_LSQ_COVARIANCE_ABSOLUTE_SIGMA
+
+
+def covariance(f, m, x, l=None, u=None, g=None, tm=None, settings=None, dtype=np.float64, absolute_sigma=False,
+               fContext=None, gContext=None, options=None):
+    """Covariance of the fitted parameters of the general solver at x (mir_lsq_covariance_gpu_*): cov = s^2 inv(J^T J) from one
+    full Jacobian refresh made as the solve makes it (g, or finite differences through f / the options' batched callbacks), with
+    s^2 = ||f(x)||^2 / (rows - free parameters), or 1 with absolute_sigma=True. f, g, tm, fContext, gContext and options as in
+    optimizeLeastSquares (device callbacks, workspace, communicator, stats). x is not modified. A parameter with l == u is
+    fixed: its row and column are 0. Returns (cov n x n, stderr = sqrt(diag(cov)), residual ||f(x)||^2, info); info != 0: J^T J
+    is not positive definite at that leading minor and the free entries are +inf. Raises LeastSquaresException for a negative
+    status (bad guess, bad bounds, bad settings, no device)."""
+    L = lib()
+    x = np.array(x, dtype=dtype, order="C")
+    n = x.size
+    lo = np.full(n, -np.inf, dtype=dtype) if l is None else np.ascontiguousarray(l, dtype=dtype)
+    up = np.full(n, np.inf, dtype=dtype) if u is None else np.ascontiguousarray(u, dtype=dtype)
+    if settings is None:
+        settings = LeastSquaresSettings(dtype)
+    fptr, gptr, tmptr, keep, errors = _wrap_callbacks(f, g, tm, dtype)
+    cov = np.empty((n, n), dtype=dtype)
+    res = np.zeros(1, dtype=dtype)
+    info = C.c_int(0)
+    fn = getattr(L, "mir_lsq_covariance_gpu_" + ("d" if dtype == np.float64 else "s"))
+    rc = fn(C.byref(settings), m, n, x.ctypes.data, lo.ctypes.data, up.ctypes.data,
+            C.byref(options) if options is not None else None, fContext, fptr, gContext, gptr, None, tmptr,
+            COVARIANCE_ABSOLUTE_SIGMA if absolute_sigma else 0, cov.ctypes.data, res.ctypes.data, C.byref(info))
+    del keep
+    if errors:
+        raise errors[0]
+    if rc == -1:
+        raise ValueError("mir_lsq_covariance_gpu: NULL argument")
+    if rc != 0:
+        raise LeastSquaresException(rc)
+    with np.errstate(invalid="ignore"):
+        stderr = np.sqrt(np.diag(cov))
+    return cov, stderr, res[0], info.value
+
+
+def spdInverse(P, fixed=None, dtype=np.float64):
+    """The inverse of a symmetric positive definite matrix on the device (mir_lsq_spd_inverse_*): P n x n (lower triangle
+    read), fixed: n flags or None -- a fixed index is taken out of the system and its row and column are 0. Returns (X, info);
+    info != 0: the leading minor of that order among the free indices is not positive, the free entries of X are +inf."""
+    suf = _batched_suffix(dtype)
+    dtype = np.float32 if suf == "s" else np.float64
+    L = lib()
+    P = np.ascontiguousarray(P, dtype=dtype)
+    n = P.shape[0]
+    dP = DeviceBuffer(P)
+    dX = DeviceBuffer(nbytes=n * n * P.itemsize, dtype=dtype, shape=(n, n))
+    di = DeviceBuffer(nbytes=4, dtype=np.int32, shape=(1,))
+    df = None
+    if fixed is not None:
+        fx = np.ascontiguousarray(np.asarray(fixed) != 0, dtype=np.uint8)
+        if fx.shape != (n,):
+            raise ValueError(f"fixed: {n} flags, not {fx.shape}")
+        df = DeviceBuffer(fx)
+    rc = getattr(L, "mir_lsq_spd_inverse_" + suf)(n, dP.ptr, df.ptr if df is not None else None, dX.ptr, di.ptr, None)
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_spd_inverse_{suf} failed: {rc}")
+    X, info = dX.download(), int(di.download()[0])
+    for b in (dP, dX, di, df):
+        if b is not None:
+            b.free()
+    return X, info
 
 
 def solveBoxQP(P, q, l, u, x=None, settings=None, dtype=np.float64, unconstrainedSolution=False):

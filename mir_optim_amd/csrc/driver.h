@@ -12,6 +12,7 @@
 //   solver_jacobian.hip  Jacobian refresh: finite differences (device / host callbacks, LS:1018-1049), analytic g,
 //                        Broyden passes, J^T J / J^T y (LS:999-1065)
 //   launch_*.hip         the translation units that instantiate the kernels (jtj_plan.h, broyden_launch.h, solve_launch.h)
+//   covariance.hip       Solver<T>::covariance(): one refresh at x, J^T J, its inverse (launch_spd_inverse.hip) -> covariance
 //   batched.hip, batched_d.hip   one-wavefront-per-problem batched fits in float / double: the two instances of batched_host.h
 //   comm.hip             row-shard communicators;  unit_entries.hip
 //
@@ -288,6 +289,7 @@ struct Solver {
     void commit_spec_round();
     void drop_spec_round();
     Result run();
+    void apply_options(const mir_lsq_gpu_options* opt);
 
     // ---- solver_jacobian.hip
     bool broyden_lowrank(const T* y_dev, const T* yold_dev);
@@ -302,6 +304,9 @@ struct Solver {
     bool fd_host_prepare_panel();
     bool fd_host();
     bool analytic_jacobian();
+
+    // ---- covariance.hip: cov = s^2 inv(J^T J) of ONE full refresh at x, nothing of the LM loop
+    int covariance(uint32_t flags, T* cov, T* residual_out, int* info_out);
 };
 
 // the one entry every solve goes through (solver_loop.hip; instantiated for double and float)
@@ -309,5 +314,10 @@ template <typename T>
 typename Abi<T>::Result solve_entry(const typename Abi<T>::Settings* settings, size_t m, size_t n, T* x, const T* l,
                                     const T* u, const mir_lsq_gpu_options* opt, void* fctx, typename Abi<T>::F f,
                                     void* gctx, typename Abi<T>::G g, void* tmctx, mir_least_squares_thread_manager tm);
+// mir_lsq_covariance_gpu_* (covariance.hip)
+template <typename T>
+int covariance_entry(const typename Abi<T>::Settings* settings, size_t m, size_t n, const T* x, const T* l, const T* u,
+                     const mir_lsq_gpu_options* opt, void* fctx, typename Abi<T>::F f, void* gctx, typename Abi<T>::G g,
+                     void* tmctx, mir_least_squares_thread_manager tm, uint32_t flags, T* cov, T* residual_out, int* info);
 
 }  // namespace mirlsq

@@ -665,6 +665,45 @@ typename Solver<T>::Result Solver<T>::run()
     return ret;
 }
 
+// mir_lsq_gpu_options -> the solver's members (struct_size says which members the caller's struct has); shared by the solve
+// and the covariance step (covariance.hip)
+template <typename T>
+void Solver<T>::apply_options(const mir_lsq_gpu_options* opt)
+{
+    Solver<T>& s = *this;
+    if (!opt) return;
+    s.device_cb = (opt->flags & MIR_LSQ_DEVICE_CALLBACKS) != 0;
+    s.time_kernels = (opt->flags & MIR_LSQ_TIME_KERNELS) != 0 && opt->stats;
+    s.stream = static_cast<hipStream_t>(opt->stream);
+    s.comm = opt->comm;
+    s.ws = opt->workspace;
+    s.fbctx = opt->fbContext;
+    s.fb = s.device_cb ? reinterpret_cast<typename Abi<T>::FB>(opt->fb) : nullptr;
+    s.fd_batch = opt->fd_batch;
+    s.variant = opt->variant;
+    if (opt->stats) {
+        // mir_lsq_stats is versioned by size (header: "Versioning of mir_lsq_stats"): work on a full local image, hand back
+        // only what the caller's struct holds
+        size_t bytes = opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajorDiff) + sizeof(void*)
+            ? offsetof(mir_lsq_stats, trial_callback_points) + sizeof(uint64_t)
+            : (opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajor) + sizeof(void*)
+                   ? offsetof(mir_lsq_stats, jtj_fd_launches) + sizeof(uint64_t)
+                   : offsetof(mir_lsq_stats, qp_active_set_passes) + sizeof(uint64_t));
+        if (opt->struct_size >= offsetof(mir_lsq_gpu_options, stats_size) + sizeof(uint32_t) && opt->stats_size)
+            bytes = opt->stats_size;
+        if (bytes > sizeof(mir_lsq_stats)) bytes = sizeof(mir_lsq_stats);
+        s.stats_user = opt->stats;
+        s.stats_bytes = bytes;
+        std::memcpy(&s.stats_local, opt->stats, bytes);          // the counters accumulate over calls
+        s.stats = &s.stats_local;
+    }
+    if (opt->struct_size >= offsetof(mir_lsq_gpu_options, trace) + sizeof(void*)) s.trace = opt->trace;
+    if (opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajor) + sizeof(void*) && s.device_cb)
+        s.fbr = reinterpret_cast<typename Abi<T>::FB>(opt->fbRowMajor);
+    if (opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajorDiff) + sizeof(void*) && s.device_cb)
+        s.fbd = reinterpret_cast<typename Abi<T>::FB>(opt->fbRowMajorDiff);
+}
+
 template <typename T>
 typename Abi<T>::Result solve_entry(const typename Abi<T>::Settings* settings, size_t m, size_t n, T* x, const T* l,
                                     const T* u, const mir_lsq_gpu_options* opt, void* fctx, typename Abi<T>::F f,
@@ -673,39 +712,8 @@ typename Abi<T>::Result solve_entry(const typename Abi<T>::Settings* settings, s
     Solver<T> s{};
     s.S = settings; s.m = m; s.n = (uint32_t)n; s.xh = x; s.lh = l; s.uh = u;
     s.fctx = fctx; s.f = f; s.gctx = gctx; s.g = g; s.tmctx = tmctx; s.tm = tm;
-    if (opt) {
-        s.device_cb = (opt->flags & MIR_LSQ_DEVICE_CALLBACKS) != 0;
-        s.time_kernels = (opt->flags & MIR_LSQ_TIME_KERNELS) != 0 && opt->stats;
-        s.stream = static_cast<hipStream_t>(opt->stream);
-        s.comm = opt->comm;
-        s.ws = opt->workspace;
-        s.fbctx = opt->fbContext;
-        s.fb = s.device_cb ? reinterpret_cast<typename Abi<T>::FB>(opt->fb) : nullptr;
-        s.fd_batch = opt->fd_batch;
-        s.variant = opt->variant;
-        if (opt->stats) {
-            // mir_lsq_stats is versioned by size (header: "Versioning of mir_lsq_stats"): work on a full local image, hand back
-            // only what the caller's struct holds
-            size_t bytes = opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajorDiff) + sizeof(void*)
-                ? offsetof(mir_lsq_stats, trial_callback_points) + sizeof(uint64_t)
-                : (opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajor) + sizeof(void*)
-                       ? offsetof(mir_lsq_stats, jtj_fd_launches) + sizeof(uint64_t)
-                       : offsetof(mir_lsq_stats, qp_active_set_passes) + sizeof(uint64_t));
-            if (opt->struct_size >= offsetof(mir_lsq_gpu_options, stats_size) + sizeof(uint32_t) && opt->stats_size)
-                bytes = opt->stats_size;
-            if (bytes > sizeof(mir_lsq_stats)) bytes = sizeof(mir_lsq_stats);
-            s.stats_user = opt->stats;
-            s.stats_bytes = bytes;
-            std::memcpy(&s.stats_local, opt->stats, bytes);          // the counters accumulate over calls
-            s.stats = &s.stats_local;
-        }
-        if (opt->struct_size >= offsetof(mir_lsq_gpu_options, trace) + sizeof(void*)) s.trace = opt->trace;
-        if (opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajor) + sizeof(void*) && s.device_cb)
-            s.fbr = reinterpret_cast<typename Abi<T>::FB>(opt->fbRowMajor);
-        if (opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajorDiff) + sizeof(void*) && s.device_cb)
-            s.fbd = reinterpret_cast<typename Abi<T>::FB>(opt->fbRowMajorDiff);
-        if (s.trace) s.trace->count = 0;
-    }
+    s.apply_options(opt);
+    if (s.trace) s.trace->count = 0;
     const typename Abi<T>::Result r = s.run();
     if (s.stats_user) std::memcpy(s.stats_user, &s.stats_local, s.stats_bytes);
     return r;

@@ -63,7 +63,8 @@ Buffers<T> carve(void* base, size_t m, size_t n, int num_cu)
         b.sc[k].A = (T*)take(n * n, sizeof(T));
         b.sc[k].Fg = (T*)take(n * (n | 1), sizeof(T));
         b.sc[k].vec = (T*)take(12 * n, sizeof(T));
-        b.sc[k].ivec = (int32_t*)take(2 * n, sizeof(int32_t));
+        b.sc[k].ivec = (int32_t*)take(2 * n, sizeof(int32_t));      // (covariance.hip keeps its n-byte mask and info in the last entry's:
+                                                                     //  Pm, A >= n x n, vec >= n, ivec >= n + 1 int32 must stay true)
         b.sc[k].dbg = nullptr;
         b.sc[k].coop = (unsigned long long*)take(n > (size_t)kSolveMaxN ? kCoopWords : 0, sizeof(unsigned long long));
         b.sc[k].cS = (T*)take(coop_scratch_elems((int)n), sizeof(T));
