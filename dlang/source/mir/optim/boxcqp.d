@@ -43,7 +43,19 @@ extern(C) @system nothrow @nogc pure
         const(double)* l, const(double)* u, double* x, int unconstrainedSolution, int* iterations);
     int mir_solve_box_qp_gpu_s(scope const BoxQPSettings!float* settings, size_t n, const(float)* P, const(float)* q,
         const(float)* l, const(float)* u, float* x, int unconstrainedSolution, int* iterations);
+
+    /// `count` problems of order n <= 8 in one launch, DEVICE pointers in the 8-wide layout (P count x 64, q / x count x 8,
+    /// l / u 8 values or count x 8 with bound_stride 0 / 8); enqueued on `stream`, no synchronisation. 0, -1 or -5.
+    int mir_lsq_batched_box_qp_d(scope const BoxQPSettings!double* settings, size_t count, size_t n, const(double)* P,
+        const(double)* q, const(double)* l, const(double)* u, size_t bound_stride, double* x, int* status, int* iterations,
+        uint flags, void* stream);
+    int mir_lsq_batched_box_qp_s(scope const BoxQPSettings!float* settings, size_t count, size_t n, const(float)* P,
+        const(float)* q, const(float)* l, const(float)* u, size_t bound_stride, float* x, int* status, int* iterations,
+        uint flags, void* stream);
 }
+
+/// flag of mir_lsq_batched_box_qp_*: x holds the unconstrained minimisers on entry
+enum uint MIR_LSQ_BOX_QP_UNCONSTRAINED_SOLUTION = 1;
 
 /++
 argmin_x (x'Px / 2 + q'x) subject to l <= x <= u, P positive definite with its LOWER triangle meaningful (row-major,

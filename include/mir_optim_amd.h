@@ -354,6 +354,28 @@ int mir_solve_box_qp_gpu_s(const mir_box_qp_settings_s* settings, size_t n, cons
                            const float* q, const float* l, const float* u, float* x,
                            int unconstrainedSolution, int* iterations);
 
+/* Batched BOXCQP on the device for small problems: `count` independent solveBoxQP calls (QP:122-379) of the same order
+ * n (1 .. 8) in ONE launch, four problems a wavefront (csrc/boxqp_rows.h), instead of a loop over mir_solve_box_qp_gpu_*.
+ * All pointers are DEVICE pointers, laid out as mir_lsq_batched_posvx_* takes them: P count x 64 values, problem p at
+ * P + 64 p, row-major with row stride 8, the LOWER triangle is read; q and x count x 8; l and u 8 values shared by all
+ * problems (bound_stride = 0) or count x 8 (bound_stride = 8). Components >= n are ignored on input and written as 0 in x.
+ * status[p]: BoxQPStatus (solved 0; numericError 1: a factorization failed; maxIterations 2, also the all-free exit of the
+ * active-set loop); iterations[p] (optional, may be NULL): active-set steps, 0 when the unconstrained minimiser is feasible.
+ * settings: relTolerance / absTolerance of the classification, maxIterations (0: 10 n + 100), common to all problems.
+ * flags: MIR_LSQ_BOX_QP_UNCONSTRAINED_SOLUTION -- x holds every problem's unconstrained minimiser on entry (the reference's
+ * unconstrainedSolution = true, QP:129, 168): the first solve is skipped.
+ * The call is enqueued on `stream` (NULL = default stream) and does not synchronise. Returns 0; -1 for bad arguments (a NULL
+ * pointer other than iterations, n outside 1 .. 8, bound_stride not 0 or 8, count above 2^30); -5 when the launch failed (no
+ * usable device included). count == 0 returns 0 and launches nothing. Callers discover the entry by its name: the version
+ * string stays "0.4". */
+#define MIR_LSQ_BOX_QP_UNCONSTRAINED_SOLUTION 1u
+int mir_lsq_batched_box_qp_s(const mir_box_qp_settings_s* settings, size_t count, size_t n, const float* P, const float* q,
+                             const float* l, const float* u, size_t bound_stride, float* x, int* status, int* iterations,
+                             unsigned flags, void* stream);
+int mir_lsq_batched_box_qp_d(const mir_box_qp_settings_d* settings, size_t count, size_t n, const double* P, const double* q,
+                             const double* l, const double* u, size_t bound_stride, double* x, int* status, int* iterations,
+                             unsigned flags, void* stream);
+
 /* Batched small fits, ONE WAVEFRONT PER PROBLEM (BASELINE cfg 5): `count` independent problems of the same shape
  * with a built-in residual model r_i = model(t_i; x) - data_i evaluated inside the kernel (no callback):
  *   MIR_LSQ_MODEL_EXP_DECAY   n = 3   p0 exp(-t p1) + p2

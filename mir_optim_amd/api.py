@@ -30,6 +30,7 @@ __all__ = [
     "mir_least_squares_work_length", "mir_least_squares_iwork_length", "mir_box_qp_work_length",
     "mir_box_qp_iwork_length", "GpuOptions", "Stats", "lib", "workloads_lib", "device_count",
     "DeviceBuffer", "Stream", "jtj", "fd_jtj", "DEVICE_CALLBACKS", "TIME_KERNELS", "optimizeLeastSquaresBatched", "batchedPosvx", "BATCHED_NO_LADDER",
+    "solveBoxQPBatched", "BOX_QP_UNCONSTRAINED_SOLUTION",
     "MODEL_EXP_DECAY", "MODEL_EXP3_AFFINE", "MODEL_EXP_DECAY_PAD8", "ResultS", "Trace", "TraceRecord", "Spline", "FitSplineResult", "fitSpline",
     "fit_spline_residuals", "variant_lr_cap",
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
@@ -328,6 +329,11 @@ def lib():
                 fn.restype = C.c_int
                 fn.argtypes = [C.POINTER(S), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
                                C.c_void_p, C.POINTER(BatchedOptions), C.POINTER(BatchedExtras)]
+        for suf in ("s", "d"):
+            fn = getattr(L, "mir_lsq_batched_box_qp_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [C.c_void_p, sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.c_uint, C.c_void_p]
         L.mir_lsq_comm_describe.restype = C.c_int
         L.mir_lsq_comm_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         L.mir_lsq_workspace_create.restype = C.c_void_p
@@ -804,6 +810,71 @@ def solveBoxQP(P, q, l, u, x=None, settings=None, dtype=np.float64, unconstraine
     st = fn(C.byref(settings), n, P.ctypes.data, q.ctypes.data, l.ctypes.data, u.ctypes.data, xo.ctypes.data,
             1 if unconstrainedSolution else 0, C.byref(it))
     return BoxQPStatus(st), xo, it.value
+
+
+BOX_QP_UNCONSTRAINED_SOLUTION = 1      # MIR_LSQ_BOX_QP_UNCONSTRAINED_SOLUTION
+
+
+def _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution):
+    """The 8-wide layout of mir_lsq_batched_box_qp_* from count x n x n / count x n arrays (host side, no device): returns
+    (count, n, P count x 8 x 8, q count x 8, l, u (8,) or count x 8, bound_stride, x count x 8). Raises ValueError."""
+    suf = _batched_suffix(dtype)
+    dtype = np.float32 if suf == "s" else np.float64
+    P = np.asarray(P, dtype=dtype)
+    if P.ndim != 3 or P.shape[1] != P.shape[2]:
+        raise ValueError(f"P: count x n x n, not {P.shape}")
+    count, n = P.shape[0], P.shape[1]
+    if not 1 <= n <= 8:
+        raise ValueError(f"solveBoxQPBatched: n = {n} is outside 1 .. 8")
+    q = np.asarray(q, dtype=dtype)
+    if q.shape != (count, n):
+        raise ValueError(f"q: {count} x {n}, not {q.shape}")
+    l, u = np.asarray(l, dtype=dtype), np.asarray(u, dtype=dtype)
+    if l.shape != u.shape or l.shape not in ((n,), (count, n)):
+        raise ValueError(f"l, u: both {n} values or both {count} x {n}, not {l.shape} and {u.shape}")
+    shared = l.ndim == 1
+    Pp = np.zeros((count, 8, 8), dtype=dtype); Pp[:, :n, :n] = P
+    qp = np.zeros((count, 8), dtype=dtype); qp[:, :n] = q
+    lp = np.zeros((8,) if shared else (count, 8), dtype=dtype); lp[..., :n] = l
+    up = np.zeros((8,) if shared else (count, 8), dtype=dtype); up[..., :n] = u
+    xp = np.zeros((count, 8), dtype=dtype)
+    if x is not None:
+        x = np.asarray(x, dtype=dtype)
+        if x.shape != (count, n):
+            raise ValueError(f"x: {count} x {n}, not {x.shape}")
+        xp[:, :n] = x
+    elif unconstrainedSolution:
+        raise ValueError("unconstrainedSolution=True needs x, the unconstrained minimisers")
+    return count, n, Pp, qp, lp, up, (0 if shared else 8), xp
+
+
+def solveBoxQPBatched(P, q, l, u, x=None, settings=None, dtype=np.float64, unconstrainedSolution=False):
+    """`count` solveBoxQP problems of order n <= 8 in one launch (mir_lsq_batched_box_qp_d / _s, four problems a wavefront):
+    argmin_x(1/2 xPx + qx) : l <= x <= u for every problem. P count x n x n (lower triangles read), q count x n, l and u
+    n values shared by all problems or count x n; x (only with unconstrainedSolution=True): the unconstrained minimisers,
+    count x n. Returns (status[count] of BoxQPStatus values, x[count, n], iterations[count])."""
+    count, n, Pp, qp, lp, up, bound_stride, xp = _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution)
+    dtype = Pp.dtype.type
+    suf = "s" if dtype == np.float32 else "d"
+    if settings is None:
+        settings = BoxQPSettings(dtype)
+    if count == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros((0, n), dtype=dtype), np.zeros(0, dtype=np.int32)
+    L = lib()
+    bufs = [DeviceBuffer(a) for a in (Pp, qp, lp, up, xp)]
+    dst = DeviceBuffer(nbytes=count * 4, dtype=np.int32, shape=(count,))
+    dit = DeviceBuffer(nbytes=count * 4, dtype=np.int32, shape=(count,))
+    st = Stream()
+    rc = getattr(L, "mir_lsq_batched_box_qp_" + suf)(C.addressof(settings), count, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr,
+                                                    bufs[3].ptr, bound_stride, bufs[4].ptr, dst.ptr, dit.ptr,
+                                                    BOX_QP_UNCONSTRAINED_SOLUTION if unconstrainedSolution else 0, st.handle)
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_batched_box_qp_{suf} failed: {rc}")
+    st.synchronize()
+    out = dst.download().copy(), bufs[4].download()[:, :n].copy(), dit.download().copy()
+    for b in bufs + [dst, dit]:
+        b.free()
+    return out
 
 
 def jtj(J, y, y_old=None, dx=None, dtype=np.float64):

@@ -265,12 +265,17 @@ template <class T> __device__ inline T rows_min(T v)
 // Prow: the full symmetric row r of this group's P; rhs_r: component r of its right-hand side. x: the group's solution in every
 // lane of the group. Returns the group's info in every lane of the group. There is no branch on a group's data: a group whose
 // factorization fails keeps computing on values nobody reads.
-template <int N, int NMAX, class T>
-__device__ inline int posvx_rows(const T (&Prow)[NMAX], T rhs_r, int r, T (&x)[NMAX])
+// MASKED (boxqp_rows.h: the reduced systems of the active-set loop, solved in place at full order as posvx_rows16 does): only
+// the rows with live_r belong to the group's system, `order` of them; the row and column of every other index are the
+// identity's and its right-hand side is 0, which leaves the arithmetic of the live part exactly that of the compact system in
+// the reference's order (every skipped term is an exact zero), and ?poequ, berr and safe1 look at the live rows only. The
+// unmasked instantiations ignore both arguments and are, operation for operation, what they were before the parameter existed.
+template <int N, int NMAX, class T, bool MASKED = false>
+__device__ inline int posvx_rows(const T (&Prow)[NMAX], T rhs_r, int r, T (&x)[NMAX], bool live_r = true, int order = N)
 {
     static_assert(NMAX == 8, "row r = lane & 7");
     const T eps = Lim<T>::eps / 2, safmin = Lim<T>::min_normal;
-    const bool live = r < N;
+    const bool live = MASKED ? (r < N && live_r) : r < N;
     const T d_r = MIRLSQ_ROW_PICK(Prow, r);
     // ?poequ
     const T smin = rows_min(live ? d_r : Lim<T>::inf());
@@ -286,7 +291,9 @@ __device__ inline int posvx_rows(const T (&Prow)[NMAX], T rhs_r, int r, T (&x)[N
         constexpr int k = K.value;
         s[k] = dpp_row_bcast<k>(s_r);
         const T v = Prow[k];
-        Arow[k] = (live && k < N) ? (rcequ ? s[k] * s_r * v : v) : (r == k ? T(1) : T(0));
+        bool lk = true;                                              // column k belongs to the system
+        if constexpr (MASKED) lk = dpp_row_bcast<k>(live ? 1 : 0) != 0;
+        Arow[k] = (live && k < N && lk) ? (rcequ ? s[k] * s_r * v : v) : (r == k ? T(1) : T(0));
         Frow[k] = Arow[k];
         Fcol[k] = T(0);
     });
@@ -338,7 +345,7 @@ __device__ inline int posvx_rows(const T (&Prow)[NMAX], T rhs_r, int r, T (&x)[N
     };
     potrs(b_r, x);
     // ?porfs: the loop runs while any group refines; a group that has stopped keeps its solution
-    const T safe1 = (T)(N + 1) * safmin, safe2 = safe1 / eps;
+    const T safe1 = (T)((MASKED ? order : N) + 1) * safmin, safe2 = safe1 / eps;
     T lstres = 3;
     bool active = true;
     for (int count = 1;; ++count) {

@@ -1,0 +1,172 @@
+"""Seeded families of small box-constrained QPs for the batched BOXCQP tests (tests/test_batched_boxqp_host.py on the CPU,
+tests/test_gpu_batched_boxqp.py on the device), and what the tests share: the oracle's answers, the margin screen, the KKT
+check. Nothing here needs a device.
+
+A problem: P = A^T A / m + delta I (A m x n standard normal, m = n + 4, delta = 0.05; redrawn until cond_2(P) <= 1e3), q
+standard normal scaled by 2, bounds l = c - w, u = c + w around a centre c ~ N(0, 1) of half-width w ~ U(0.05, 1.5), each
+side infinite with probability 0.1: about half the variables end on a bound. The float tests solve the problem ROUNDED to
+float (P, q, l, u cast to float32), and every reference computed in double takes those rounded numbers.
+
+MARGIN SCREEN (exact status / iteration / active-set comparisons only): at the f64 oracle's solution x, with g = P x + q,
+  * a variable on a bound (x_i == l_i or x_i == u_i) has its multiplier (g_i at a lower bound, -g_i at an upper one) at least
+    1e-3 (1 + (|P| |x| + |q|)_i) -- the size of the terms the multiplier is the sum of -- above zero;
+  * a free variable has both slacks x_i - l_i and u_i - x_i at least 1e-3 (1 + |bound|) above zero (an infinite bound passes).
+A problem that fails the screen is one where a rounding error may legitimately change the path of the active-set loop. The
+screened-out share of a family is capped at 10 % (asserted on the CPU from the oracle alone).
+"""
+import functools
+
+import numpy as np
+
+NS = (1, 2, 3, 5, 8)
+FAMILY_COUNT = 64
+COUNTS = (1, 3, 4, 5, 7, 257)
+MAX_SCREENED_OUT = 0.10
+DTYPES = (np.float32, np.float64)
+
+
+def cond2(P):
+    w = np.linalg.eigvalsh(np.asarray(P, dtype=np.float64))
+    return w[-1] / w[0]
+
+
+def random_problem(rng, n, width=1.0):
+    m = n + 4
+    while True:
+        A = rng.standard_normal((m, n))
+        P = A.T @ A / m + 0.05 * np.eye(n)
+        if cond2(P) <= 1e3:
+            break
+    q = 2.0 * rng.standard_normal(n)
+    c = rng.standard_normal(n)
+    w = width * rng.uniform(0.05, 1.5, n)
+    l, u = c - w, c + w
+    l[rng.random(n) < 0.1] = -np.inf
+    u[rng.random(n) < 0.1] = np.inf
+    return P, q, l, u
+
+
+@functools.lru_cache(maxsize=None)
+def family(n, dtype=np.float64, seed=20260, count=FAMILY_COUNT):
+    """count problems of order n as float64 arrays holding values representable in `dtype`: P count x n x n (full symmetric),
+    q, l, u count x n. The same (n, seed) gives the same problems; float32 rounds them."""
+    rng = np.random.default_rng([seed, n])
+    probs = [random_problem(rng, n) for _ in range(count)]
+    out = [np.stack([p[k] for p in probs]) for k in range(4)]
+    out = [a.astype(dtype).astype(np.float64) for a in out]
+    for a in out:
+        a.setflags(write=False)
+    return tuple(out)
+
+
+def qp_settings(oracle, dtype, relTolerance=None, absTolerance=None, maxIterations=None):
+    s = oracle.default_settings(dtype).qpSettings
+    if relTolerance is not None:
+        s.relTolerance = relTolerance
+    if absTolerance is not None:
+        s.absTolerance = absTolerance
+    if maxIterations is not None:
+        s.maxIterations = maxIterations
+    return s
+
+
+def oracle_solve(oracle, P, q, l, u, dtype, settings=None, x0=None):
+    """oracle.solve_box_qp over a batch: (status[count], x[count, n] as float64, iterations[count])."""
+    count, n = q.shape
+    st = np.zeros(count, dtype=np.int32); it = np.zeros(count, dtype=np.int32); x = np.zeros((count, n))
+    shared = np.ndim(l) == 1
+    for p in range(count):
+        lp, up = (l, u) if shared else (l[p], u[p])
+        if x0 is None:
+            st[p], xp, it[p] = oracle.solve_box_qp(np.tril(P[p]), q[p], lp, up, settings=settings, dtype=dtype)
+        else:
+            st[p], xp, it[p] = oracle.solve_box_qp(np.tril(P[p]), q[p], lp, up, settings=settings, dtype=dtype, x0=x0[p],
+                                                   unconstrained_solution=True)
+        x[p] = xp
+    return st, x, it
+
+
+_ORACLE = {}
+
+
+def oracle_family(oracle, n, dtype, data_dtype=None):
+    """The oracle's answers in `dtype` for family(n, data_dtype or dtype), computed once and shared (read-only)."""
+    data_dtype = data_dtype or dtype
+    key = (n, np.dtype(dtype).name, np.dtype(data_dtype).name)
+    if key not in _ORACLE:
+        res = oracle_solve(oracle, *family(n, data_dtype), dtype)
+        for a in res:
+            a.setflags(write=False)
+        _ORACLE[key] = res
+    return _ORACLE[key]
+
+
+def active_set(x, l, u):
+    """-1 on the lower bound, 1 on the upper bound, 0 free: a bound variable is set to its bound exactly (QP:246, 253)."""
+    x, l, u = np.broadcast_arrays(np.asarray(x, dtype=np.float64), l, u)
+    return np.where(x == l, -1, np.where(x == u, 1, 0))
+
+
+def margin_screened(P, q, l, u, x64):
+    """True when the problem passes the margin screen at the f64 oracle's solution x64 (module docstring)."""
+    g = P @ x64 + q
+    scale = np.abs(P) @ np.abs(x64) + np.abs(q)
+    fl = active_set(x64, l, u)
+    for i in range(q.size):
+        if fl[i] != 0:
+            mult = g[i] if fl[i] < 0 else -g[i]
+            if not mult >= 1e-3 * (1 + scale[i]):
+                return False
+        else:
+            for slack, b in ((x64[i] - l[i], l[i]), (u[i] - x64[i], u[i])):
+                if np.isfinite(b) and not slack >= 1e-3 * (1 + abs(b)):
+                    return False
+    return True
+
+
+def screen_family(oracle, n, dtype):
+    """Boolean mask over family(n, dtype): the margin screen at the f64 oracle's solution of the same (rounded) data."""
+    P, q, l, u = family(n, dtype)
+    st, x64, _ = oracle_family(oracle, n, np.float64, dtype)
+    return np.array([st[p] == 0 and margin_screened(P[p], q[p], l[p], u[p], x64[p]) for p in range(q.shape[0])])
+
+
+def kkt_factor(P, q, l, u, x, eps):
+    """The smallest factor f for which x passes the KKT check with tau_i = f eps (|P| |x| + |q|)_i, in numpy float64; inf when
+    x leaves [l, u]. The tests assert f <= KKT_FACTOR."""
+    x = np.asarray(x, dtype=np.float64)
+    if not (np.all(l <= x) and np.all(x <= u)):
+        return np.inf
+    g = P @ x + q
+    tau1 = eps * (np.abs(P) @ np.abs(x) + np.abs(q))
+    fl = active_set(x, l, u)
+    viol = np.where(fl < 0, -g, np.where(fl > 0, g, np.abs(g)))          # what must stay below tau
+    viol = np.where((l == u), 0.0, viol)                                 # a fixed variable carries any multiplier
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = np.where(viol > 0, viol / tau1, 0.0)
+    return float(np.max(f))
+
+
+KKT_FACTOR = 8.0
+
+
+def mixed_wave(oracle, n, dtype, seed=777, budget=4000):
+    """Four problems of order n that need 0, 1, 2 and >= 3 active-set iterations by the oracle in `dtype` (status solved, margin
+    screened), found by a fixed-seed search (every fourth draw has bounds eight times as wide: a feasible unconstrained
+    minimiser is rare at n = 8 otherwise); classes that do not exist for this n are absent from the returned dict
+    {class: (P, q, l, u)}. n = 1 has only 0 and 1: a one-variable problem whose minimiser lies outside [l, u] is moved to the
+    violated bound in step 1, where the convex objective's slope has the multiplier's sign, so step 1 ends the loop."""
+    rng = np.random.default_rng([seed, n])
+    found = {}
+    for trial in range(budget):
+        P, q, l, u = [a.astype(dtype).astype(np.float64) for a in random_problem(rng, n, 8.0 if trial % 4 == 3 else 1.0)]
+        st, x, it = oracle.solve_box_qp(np.tril(P), q, l, u, dtype=dtype)
+        cls = min(int(it), 3)
+        if st != 0 or cls in found:
+            continue
+        st64, x64, _ = oracle.solve_box_qp(np.tril(P), q, l, u)
+        if st64 == 0 and margin_screened(P, q, l, u, x64):
+            found[cls] = (P, q, l, u)
+            if len(found) == (2 if n == 1 else 4):
+                break
+    return found
