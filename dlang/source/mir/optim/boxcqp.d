@@ -52,6 +52,15 @@ extern(C) @system nothrow @nogc pure
     int mir_lsq_batched_box_qp_s(scope const BoxQPSettings!float* settings, size_t count, size_t n, const(float)* P,
         const(float)* q, const(float)* l, const(float)* u, size_t bound_stride, float* x, int* status, int* iterations,
         uint flags, void* stream);
+
+    /// the same for n = 9 .. 16 in the 16-wide layout (P count x 256, q / x count x 16, l / u 16 values or count x 16 with
+    /// bound_stride 0 / 16); enqueued on `stream`, no synchronisation. 0, -1 or -5.
+    int mir_lsq_batched_box_qp16_d(scope const BoxQPSettings!double* settings, size_t count, size_t n, const(double)* P,
+        const(double)* q, const(double)* l, const(double)* u, size_t bound_stride, double* x, int* status, int* iterations,
+        uint flags, void* stream);
+    int mir_lsq_batched_box_qp16_s(scope const BoxQPSettings!float* settings, size_t count, size_t n, const(float)* P,
+        const(float)* q, const(float)* l, const(float)* u, size_t bound_stride, float* x, int* status, int* iterations,
+        uint flags, void* stream);
 }
 
 /// flag of mir_lsq_batched_box_qp_*: x holds the unconstrained minimisers on entry

@@ -376,6 +376,20 @@ int mir_lsq_batched_box_qp_d(const mir_box_qp_settings_d* settings, size_t count
                              const double* l, const double* u, size_t bound_stride, double* x, int* status, int* iterations,
                              unsigned flags, void* stream);
 
+/* The same for orders n = 9 .. 16 (csrc/boxqp_rows16.h: four problems a wavefront, one matrix row and one component of every
+ * vector per lane of a 16-lane row), in the 16-WIDE layout: P count x 256 values, problem p at P + 256 p, row-major with row
+ * stride 16, the LOWER triangle is read; q and x count x 16; l and u 16 values shared by all problems (bound_stride = 0) or
+ * count x 16 (bound_stride = 16). Components >= n are ignored on input and written as 0 in x. settings, status, iterations,
+ * flags and stream as above. Returns 0; -1 for bad arguments (a NULL pointer other than iterations, n outside 9 .. 16,
+ * bound_stride not 0 or 16, count above 2^30); -5 when no device is usable or the launch failed. count == 0 returns 0,
+ * launches nothing and needs no device. mir_lsq_batched_box_qp_* keeps rejecting n > 8: the two layouts are separate entries. */
+int mir_lsq_batched_box_qp16_s(const mir_box_qp_settings_s* settings, size_t count, size_t n, const float* P, const float* q,
+                               const float* l, const float* u, size_t bound_stride, float* x, int* status, int* iterations,
+                               unsigned flags, void* stream);
+int mir_lsq_batched_box_qp16_d(const mir_box_qp_settings_d* settings, size_t count, size_t n, const double* P, const double* q,
+                               const double* l, const double* u, size_t bound_stride, double* x, int* status, int* iterations,
+                               unsigned flags, void* stream);
+
 /* Batched small fits, ONE WAVEFRONT PER PROBLEM (BASELINE cfg 5): `count` independent problems of the same shape
  * with a built-in residual model r_i = model(t_i; x) - data_i evaluated inside the kernel (no callback):
  *   MIR_LSQ_MODEL_EXP_DECAY   n = 3   p0 exp(-t p1) + p2
@@ -561,6 +575,12 @@ typedef struct mir_lsq_resident_options {
 int mir_lsq_batched_posvx_s(size_t count, size_t n, const float* P, const float* rhs, float* x, int* info, void* stream);
 /* the same in double: P count x 64 doubles, rhs and x count x 8 doubles */
 int mir_lsq_batched_posvx_d(size_t count, size_t n, const double* P, const double* rhs, double* x, int* info, void* stream);
+/* Unit-level access to the 16-row ?posvx('E','L') of mir_lsq_batched_box_qp16_* (csrc/boxqp_rows16.h), four systems a
+ * wavefront: `count` systems of order n = 9 .. 16 in the 16-wide layout (P count x 256, row stride 16, the LOWER triangle is
+ * read; rhs and x count x 16, components >= n ignored / zero); info[p] as above. Device pointers, enqueued on `stream`, no
+ * synchronisation. Returns 0; -1 bad arguments; -2 no device; -5 a failed launch. */
+int mir_lsq_batched_posvx16_s(size_t count, size_t n, const float* P, const float* rhs, float* x, int* info, void* stream);
+int mir_lsq_batched_posvx16_d(size_t count, size_t n, const double* P, const double* rhs, double* x, int* info, void* stream);
 
 /* Unit-level access to the hot kernels (parity tests and micro-benchmarks). All pointers are
  * DEVICE pointers; stream may be NULL (default stream; the call synchronises before returning).

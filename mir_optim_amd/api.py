@@ -329,11 +329,15 @@ def lib():
                 fn.restype = C.c_int
                 fn.argtypes = [C.POINTER(S), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
                                C.c_void_p, C.POINTER(BatchedOptions), C.POINTER(BatchedExtras)]
-        for suf in ("s", "d"):
-            fn = getattr(L, "mir_lsq_batched_box_qp_" + suf)
+        for name in ("box_qp_s", "box_qp_d", "box_qp16_s", "box_qp16_d"):
+            fn = getattr(L, "mir_lsq_batched_" + name)
             fn.restype = C.c_int
             fn.argtypes = [C.c_void_p, sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_uint, C.c_void_p]
+        for suf in ("s", "d"):
+            fn = getattr(L, "mir_lsq_batched_posvx16_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mir_lsq_comm_describe.restype = C.c_int
         L.mir_lsq_comm_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         L.mir_lsq_workspace_create.restype = C.c_void_p
@@ -704,21 +708,23 @@ BATCHED_ABSOLUTE_SIGMA = 1      # mir_lsq_batched_extras.flags
 def batchedPosvx(P, rhs, dtype=np.float32):
     """The damped solve of the wave-per-problem kernel on its own (mir_lsq_batched_posvx_s, or with dtype=np.float64
     mir_lsq_batched_posvx_d): P count x n x n (lower triangles read), rhs count x n, n in (3, 8). Returns (x count x n,
-    info count)."""
+    info count). n = 9 .. 16 goes to the 16-row solve of the batched box-constrained QPs in its 16-wide layout
+    (mir_lsq_batched_posvx16_s / _d)."""
     suf = _batched_suffix(dtype)
     dtype = np.float32 if suf == "s" else np.float64
     L = lib()
     P = np.asarray(P, dtype=dtype)
     count, n = P.shape[0], P.shape[1]
-    Pp = np.zeros((count, 8, 8), dtype=dtype); Pp[:, :n, :n] = P
-    bp = np.zeros((count, 8), dtype=dtype); bp[:, :n] = rhs
+    w, name = (8, "mir_lsq_batched_posvx_" + suf) if n <= 8 else (16, "mir_lsq_batched_posvx16_" + suf)
+    Pp = np.zeros((count, w, w), dtype=dtype); Pp[:, :n, :n] = P
+    bp = np.zeros((count, w), dtype=dtype); bp[:, :n] = rhs
     dP, db = DeviceBuffer(Pp), DeviceBuffer(bp)
-    dx = DeviceBuffer(nbytes=count * 8 * np.dtype(dtype).itemsize, dtype=dtype, shape=(count, 8))
+    dx = DeviceBuffer(nbytes=count * w * np.dtype(dtype).itemsize, dtype=dtype, shape=(count, w))
     di = DeviceBuffer(nbytes=count * 4, dtype=np.int32, shape=(count,))
     st = Stream()
-    rc = getattr(L, "mir_lsq_batched_posvx_" + suf)(count, n, dP.ptr, db.ptr, dx.ptr, di.ptr, st.handle)
+    rc = getattr(L, name)(count, n, dP.ptr, db.ptr, dx.ptr, di.ptr, st.handle)
     if rc != 0:
-        raise RuntimeError(f"mir_lsq_batched_posvx_{suf} failed: {rc}")
+        raise RuntimeError(f"{name} failed: {rc}")
     st.synchronize()
     x, info = dx.download()[:, :n].copy(), di.download().copy()
     for b in (dP, db, dx, di):
@@ -818,14 +824,25 @@ BOX_QP_UNCONSTRAINED_SOLUTION = 1      # MIR_LSQ_BOX_QP_UNCONSTRAINED_SOLUTION
 def _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution):
     """The 8-wide layout of mir_lsq_batched_box_qp_* from count x n x n / count x n arrays (host side, no device): returns
     (count, n, P count x 8 x 8, q count x 8, l, u (8,) or count x 8, bound_stride, x count x 8). Raises ValueError."""
+    return _box_qp_batched_pack_w(P, q, l, u, x, dtype, unconstrainedSolution, 8, 1)
+
+
+def _box_qp_batched_pack16(P, q, l, u, x, dtype, unconstrainedSolution):
+    """The 16-wide layout of mir_lsq_batched_box_qp16_* (n = 9 .. 16), by the rules of _box_qp_batched_pack: returns
+    (count, n, P count x 16 x 16, q count x 16, l, u (16,) or count x 16, bound_stride 0 or 16, x count x 16)."""
+    return _box_qp_batched_pack_w(P, q, l, u, x, dtype, unconstrainedSolution, 16, 9)
+
+
+def _box_qp_batched_pack_w(P, q, l, u, x, dtype, unconstrainedSolution, W, nmin):
+    """what the two layouts share: validation and zero padding to W-wide rows for nmin <= n <= W"""
     suf = _batched_suffix(dtype)
     dtype = np.float32 if suf == "s" else np.float64
     P = np.asarray(P, dtype=dtype)
     if P.ndim != 3 or P.shape[1] != P.shape[2]:
         raise ValueError(f"P: count x n x n, not {P.shape}")
     count, n = P.shape[0], P.shape[1]
-    if not 1 <= n <= 8:
-        raise ValueError(f"solveBoxQPBatched: n = {n} is outside 1 .. 8")
+    if not nmin <= n <= W:
+        raise ValueError(f"solveBoxQPBatched: n = {n} is outside {nmin} .. {W}")
     q = np.asarray(q, dtype=dtype)
     if q.shape != (count, n):
         raise ValueError(f"q: {count} x {n}, not {q.shape}")
@@ -833,11 +850,11 @@ def _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution):
     if l.shape != u.shape or l.shape not in ((n,), (count, n)):
         raise ValueError(f"l, u: both {n} values or both {count} x {n}, not {l.shape} and {u.shape}")
     shared = l.ndim == 1
-    Pp = np.zeros((count, 8, 8), dtype=dtype); Pp[:, :n, :n] = P
-    qp = np.zeros((count, 8), dtype=dtype); qp[:, :n] = q
-    lp = np.zeros((8,) if shared else (count, 8), dtype=dtype); lp[..., :n] = l
-    up = np.zeros((8,) if shared else (count, 8), dtype=dtype); up[..., :n] = u
-    xp = np.zeros((count, 8), dtype=dtype)
+    Pp = np.zeros((count, W, W), dtype=dtype); Pp[:, :n, :n] = P
+    qp = np.zeros((count, W), dtype=dtype); qp[:, :n] = q
+    lp = np.zeros((W,) if shared else (count, W), dtype=dtype); lp[..., :n] = l
+    up = np.zeros((W,) if shared else (count, W), dtype=dtype); up[..., :n] = u
+    xp = np.zeros((count, W), dtype=dtype)
     if x is not None:
         x = np.asarray(x, dtype=dtype)
         if x.shape != (count, n):
@@ -845,15 +862,21 @@ def _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution):
         xp[:, :n] = x
     elif unconstrainedSolution:
         raise ValueError("unconstrainedSolution=True needs x, the unconstrained minimisers")
-    return count, n, Pp, qp, lp, up, (0 if shared else 8), xp
+    return count, n, Pp, qp, lp, up, (0 if shared else W), xp
 
 
 def solveBoxQPBatched(P, q, l, u, x=None, settings=None, dtype=np.float64, unconstrainedSolution=False):
-    """`count` solveBoxQP problems of order n <= 8 in one launch (mir_lsq_batched_box_qp_d / _s, four problems a wavefront):
+    """`count` solveBoxQP problems of order n <= 16 in one launch, four problems a wavefront (n <= 8: mir_lsq_batched_box_qp_d
+    / _s in the 8-wide layout; n = 9 .. 16: mir_lsq_batched_box_qp16_d / _s in the 16-wide one):
     argmin_x(1/2 xPx + qx) : l <= x <= u for every problem. P count x n x n (lower triangles read), q count x n, l and u
     n values shared by all problems or count x n; x (only with unconstrainedSolution=True): the unconstrained minimisers,
     count x n. Returns (status[count] of BoxQPStatus values, x[count, n], iterations[count])."""
-    count, n, Pp, qp, lp, up, bound_stride, xp = _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution)
+    n_in = np.shape(P)[1] if np.ndim(P) == 3 else 0
+    if n_in > 16:
+        raise ValueError(f"solveBoxQPBatched: n = {n_in} is above 16, the limit of the batched kernels")
+    wide = n_in > 8
+    pack = _box_qp_batched_pack16 if wide else _box_qp_batched_pack
+    count, n, Pp, qp, lp, up, bound_stride, xp = pack(P, q, l, u, x, dtype, unconstrainedSolution)
     dtype = Pp.dtype.type
     suf = "s" if dtype == np.float32 else "d"
     if settings is None:
@@ -865,11 +888,11 @@ def solveBoxQPBatched(P, q, l, u, x=None, settings=None, dtype=np.float64, uncon
     dst = DeviceBuffer(nbytes=count * 4, dtype=np.int32, shape=(count,))
     dit = DeviceBuffer(nbytes=count * 4, dtype=np.int32, shape=(count,))
     st = Stream()
-    rc = getattr(L, "mir_lsq_batched_box_qp_" + suf)(C.addressof(settings), count, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr,
-                                                    bufs[3].ptr, bound_stride, bufs[4].ptr, dst.ptr, dit.ptr,
-                                                    BOX_QP_UNCONSTRAINED_SOLUTION if unconstrainedSolution else 0, st.handle)
+    name = ("mir_lsq_batched_box_qp16_" if wide else "mir_lsq_batched_box_qp_") + suf
+    rc = getattr(L, name)(C.addressof(settings), count, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bound_stride,
+                          bufs[4].ptr, dst.ptr, dit.ptr, BOX_QP_UNCONSTRAINED_SOLUTION if unconstrainedSolution else 0, st.handle)
     if rc != 0:
-        raise RuntimeError(f"mir_lsq_batched_box_qp_{suf} failed: {rc}")
+        raise RuntimeError(f"{name} failed: {rc}")
     st.synchronize()
     out = dst.download().copy(), bufs[4].download()[:, :n].copy(), dit.download().copy()
     for b in bufs + [dst, dit]:
