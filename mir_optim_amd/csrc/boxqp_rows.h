@@ -1,18 +1,23 @@
-// boxqp_rows.h -- solveBoxQP (/root/reference/source/mir/optim/boxcqp.d:122-379) for n = N <= 8 in the layout of posvx_rows
-// (batched_kernel.h): FOUR PROBLEMS A WAVE, one per 16-lane DPP row (group g = lane >> 4), lane r = lane & 7 of a group holds
-// row r of the group's P and component r of every vector (q, l, u, x, the multipliers, the flags); the upper eight lanes of a
-// group repeat the lower eight. No LDS, no barrier, no register array indexed at run time.
+// boxqp_rows.h -- solveBoxQP (the reference's mir/optim/boxcqp.d:122-379, cited as QP:) for small orders, FOUR PROBLEMS A WAVE,
+// one per 16-lane DPP row (group g = lane >> 4). Two layouts share ONE active-set loop, boxqp_active_set<N, W, T>:
+//   * W = 8, n = N <= 8 (this header: boxqp_rows, k_boxqp_rows): the layout of posvx_rows (batched_kernel.h). Lane r = lane & 7
+//     of a group holds row r of the group's P and component r of every vector (q, l, u, x, the multipliers, the flags); the
+//     upper eight lanes of a group repeat the lower eight.
+//   * W = 16, n = N = 9 .. 16 (boxqp_rows16.h: boxqp_rows16, k_boxqp_rows16): lane r = lane & 15, every lane a row of its own.
+// A layout hands the loop its masked full-order ?posvx as a callable; everything else is the loop's. No LDS, no barrier, no
+// register array indexed at run time.
 //
 // The loop is the one of solve_wave16.h:203-260 restated for groups that hold DIFFERENT problems:
-//   * the reduced system of an active-set step is solved in place at full order by the MASKED posvx_rows (a bound variable's
-//     row and column are the identity's; ?poequ, berr and safe1 see the free rows and their number only);
+//   * the reduced system of an active-set step is solved in place at full order by the layout's MASKED ?posvx (a bound
+//     variable's row and column are the identity's; ?poequ, berr and safe1 see the free rows and their number only);
 //   * its right-hand side is a Kahan-Babuska-Neumaier sum over the bound variables, j ascending (QP:282-305), the multipliers
 //     are two partial sums (QP:333-337), classification uses relTolerance / absTolerance (QP:239-263), the re-check and
 //     applyBounds follow (QP:339-349);
 //   * the loop runs while ANY group of the wave is still iterating (a wave ballot; the group's own bits decide for the group).
 //     A group that has finished -- solved, failed factorization, all variables free (quirk Q8), out of iterations -- keeps its x,
 //     status and iteration count through selects; nothing branches on a group's data, so what a problem returns does not depend
-//     on the three problems it shares a wave with (tests/test_gpu_batched_boxqp.py: every rotation of a mixed wave, bit for bit).
+//     on the three problems it shares a wave with (tests/test_gpu_batched_boxqp.py, tests/test_gpu_batched_boxqp16.py: every
+//     rotation of a mixed wave, bit for bit).
 // Contraction is off and every multiply-add that is meant to be one rounding is __builtin_elementwise_fma, as in posvx_rows.
 #pragma once
 
@@ -22,30 +27,34 @@ namespace mirlsq {
 
 constexpr uint32_t kBoxQpUnconstrainedSolution = 1u;      // MIR_LSQ_BOX_QP_UNCONSTRAINED_SOLUTION
 
-// the bits of the wave ballot that belong to group g (its 16 lanes; lanes 8..15 repeat lanes 0..7)
+// the bits of the wave ballot that belong to group g (its 16 lanes; at W = 8 lanes 8..15 repeat lanes 0..7)
 __device__ __forceinline__ unsigned rows_bits(bool pred, int g)
 {
     return (unsigned)((__builtin_amdgcn_ballot_w64(pred) >> (16 * g)) & 0xffffull);
 }
 
-// Prow: the full symmetric row r of the group's P; q_r, l_r, u_r: component r (r >= N: ignored). x_r: in, the group's
-// unconstrained solution when have_x (wave-uniform: the reference's unconstrainedSolution = true, QP:129, 168, the first solve
-// is then skipped); out, component r of the solution (r >= N: 0). status (BoxQPStatus: 0 solved, 1 numericError,
-// 2 maxIterations) and iters (active-set steps, 0 when the unconstrained solution is feasible) are group-uniform.
-template <int N, int NMAX, class T>
-__device__ inline void boxqp_rows(const T (&Prow)[NMAX], T q_r, T l_r, T u_r, T relTol, T absTol, uint32_t maxIterations,
-                                  bool have_x, int r, int g, T& x_r, int& status, int& iters)
+// The active-set loop of both layouts. W: the row width (8 or 16), r = lane & (W - 1). Prow: the full symmetric row r of the
+// group's P; q_r, l_r, u_r: component r (r >= N: ignored). solve(rhs_r, live_r, order, T& xs_r) -> info: the layout's masked
+// ?posvx of the group's P at full order (rows with live_r == false are identity rows, `order` is the number of live rows); it
+// hands back this lane's component of the solution and a group-uniform info (0, or the failed pivot's 1-based index).
+// x_r: in, the group's unconstrained solution when have_x (wave-uniform: the reference's unconstrainedSolution = true,
+// QP:129, 168, the first solve is then skipped); out, component r of the solution (r >= N: 0). status (BoxQPStatus: 0 solved,
+// 1 numericError, 2 maxIterations) and iters (active-set steps, 0 when the unconstrained solution is feasible) are
+// group-uniform.
+template <int N, int W, class T, class Solve>
+__device__ inline void boxqp_active_set(const T (&Prow)[W], T q_r, T l_r, T u_r, T relTol, T absTol, uint32_t maxIterations,
+                                                 bool have_x, int r, int g, Solve&& solve, T& x_r, int& status, int& iters)
 {
 #pragma clang fp contract(off)
-    static_assert(NMAX == 8 && N >= 1 && N <= NMAX, "row r = lane & 7");
+    static_assert((W == 8 || W == 16) && N >= 1 && N <= W, "row r = lane & (W - 1)");
     const bool el = r < N;
     const T lo = el ? l_r : -Lim<T>::inf(), up = el ? u_r : Lim<T>::inf();
     T x = el ? x_r : T(0);
     int st = 0;
     if (!have_x) {                                                       // QP:168-214
-        T xs[NMAX];
-        const int info = posvx_rows<N, NMAX, T, true>(Prow, -q_r, r, xs, true, N);
-        x = el ? MIRLSQ_ROW_PICK(xs, r) : T(0);
+        T xs;
+        const int info = solve(-q_r, true, N, xs);
+        x = el ? xs : T(0);
         st = info != 0 ? 1 : 0;
     }
     // QP:216-219: a feasible unconstrained solution is the answer (a NaN counts as infeasible)
@@ -69,11 +78,11 @@ __device__ inline void boxqp_rows(const T (&Prow)[NMAX], T q_r, T l_r, T u_r, T 
             la = upd ? (toL ? la : T(0)) : la;
             mu = upd ? (toU ? mu : T(0)) : mu;
         }
-        const int sN = __builtin_popcount(rows_bits(fl == 0, g) & 0xffu);
+        const int sN = __builtin_popcount(rows_bits(fl == 0, g) & ((1u << W) - 1u));   // W = 8: lanes 8..15 repeat
         run = run && sN != N;                                            // QP:265-266 (quirk Q8): leaves with maxIterations
         // right-hand side of the reduced system, QP:282-305: Kahan-Babuska-Neumaier over the bound variables, j ascending
         T ks = q_r, kc = 0;
-        static_for<NMAX>([&](auto JX) {
+        static_for<W>([&](auto JX) {
             constexpr int j = JX.value;
             if constexpr (j < N) {
                 const bool bj = dpp_row_bcast<j>(fl) != 0;
@@ -88,16 +97,16 @@ __device__ inline void boxqp_rows(const T (&Prow)[NMAX], T q_r, T l_r, T u_r, T 
         const T b_r = -(ks + kc);
         const bool need = run && sN != 0;                                // QP:307-329
         if (__builtin_amdgcn_ballot_w64(need) != 0) {
-            T xs[NMAX];
-            const int info = posvx_rows<N, NMAX, T, true>(Prow, b_r, r, xs, fl == 0, sN);
+            T xs;
+            const int info = solve(b_r, fl == 0, sN, xs);
             const bool failed = need && info != 0;
             st = failed ? 1 : st;
             run = run && !failed;
-            x = (need && !failed && fl == 0) ? MIRLSQ_ROW_PICK(xs, r) : x;
+            x = (need && !failed && fl == 0) ? xs : x;
         }
         // multipliers of the bound variables, QP:333-337 (two partial sums, as the reference's two dot products)
         T v1 = 0, v2 = 0;
-        static_for<NMAX>([&](auto JX) {
+        static_for<W>([&](auto JX) {
             constexpr int j = JX.value;
             if constexpr (j < N) {
                 const T xj = dpp_row_bcast<j>(x);
@@ -121,12 +130,34 @@ __device__ inline void boxqp_rows(const T (&Prow)[NMAX], T q_r, T l_r, T u_r, T 
     iters = it;
 }
 
+// n = N <= 8 in the layout of posvx_rows (r = lane & 7); arguments as boxqp_active_set's. The callable is a struct as in
+// boxqp_rows16 (boxqp_rows16.h says why).
+template <int N, int NMAX, class T>
+__device__ inline void boxqp_rows(const T (&Prow)[NMAX], T q_r, T l_r, T u_r, T relTol, T absTol, uint32_t maxIterations,
+                                  bool have_x, int r, int g, T& x_r, int& status, int& iters)
+{
+    static_assert(NMAX == 8, "row r = lane & 7");
+    struct {
+        const T (&Prow)[NMAX]; int r;
+        __device__ __forceinline__ int operator()(T rhs_r, bool live_r, int order, T& xs_r) const
+        {
+#pragma clang fp contract(off)
+            T xs[NMAX];
+            const int info = posvx_rows<N, NMAX, T, true>(Prow, rhs_r, r, xs, live_r, order);
+            xs_r = MIRLSQ_ROW_PICK(xs, r);
+            return info;
+        }
+    } solve{Prow, r};
+    boxqp_active_set<N, NMAX, T>(Prow, q_r, l_r, u_r, relTol, absTol, maxIterations, have_x, r, g, solve, x_r, status, iters);
+}
+
+// the arguments of k_boxqp_rows (W = 8) and of k_boxqp_rows16 (W = 16)
 template <class T> struct BoxQpRowsArgs {
-    const T* P;            // count x 64, row stride 8, lower triangle read
-    const T* q;            // count x 8
-    const T* l;            // 8 (bound_stride 0) or count x 8
+    const T* P;            // count x W^2, row stride W, lower triangle read
+    const T* q;            // count x W
+    const T* l;            // W (bound_stride 0) or count x W
     const T* u;
-    T* x;                  // count x 8, in (kBoxQpUnconstrainedSolution) / out
+    T* x;                  // count x W, in (kBoxQpUnconstrainedSolution) / out
     int* status;           // count
     int* iterations;       // count or nullptr
     int count, bound_stride;

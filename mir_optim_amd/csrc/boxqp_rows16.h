@@ -4,12 +4,10 @@
 // not the one of posvx_rows (batched_kernel.h), whose replicated x[NMAX] in every lane would not fit the register file at
 // sixteen rows. Rows >= N are identity rows and not elements. No LDS, no barrier, no register array indexed at run time.
 //
-// The loop is the one of boxqp_rows.h, statement for statement (the same reference lines are cited), with the masked solve at
-// full order done by the 16-row ?posvx: for double posvx_rows16 of solve_wave16.h as it is, for float the restatement below
-// (IEEE division and square root as in posvx_rows). Four groups hold DIFFERENT problems: the loop runs while any group of the
-// wave iterates, a reduced solve is issued while any group needs one, and everything a step changes goes through selects on
-// `run`, never a branch on a group's data: what a problem returns does not depend on its three wave partners
-// (tests/test_gpu_batched_boxqp16.py: every rotation of a mixed wave, bit for bit).
+// The active-set loop is boxqp_active_set of boxqp_rows.h, the one loop of both layouts; this header gives it the masked solve
+// at full order by the 16-row ?posvx: for double posvx_rows16 of solve_wave16.h as it is, for float the restatement below
+// (IEEE division and square root as in posvx_rows). What the loop promises holds here as there: what a problem returns does
+// not depend on its three wave partners (tests/test_gpu_batched_boxqp16.py: every rotation of a mixed wave, bit for bit).
 // Contraction is off and every multiply-add that is meant to be one rounding is __builtin_elementwise_fma / fma.
 #pragma once
 
@@ -138,111 +136,24 @@ __device__ __forceinline__ int posvx16(const T (&Mrow)[kW16], T d_r, T rhs_r, bo
     else return posvx_rows16_t<N, T>(Mrow, d_r, rhs_r, live, r, x_r, order);
 }
 
-// Prow: the full symmetric row r of the group's P, d_r = Prow[r]; q_r, l_r, u_r: component r (r >= N: ignored). x_r: in, the
-// group's unconstrained solution when have_x (wave-uniform: the reference's unconstrainedSolution = true, QP:129, 168, the
-// first solve is then skipped); out, component r of the solution (r >= N: 0). status (BoxQPStatus: 0 solved, 1 numericError,
-// 2 maxIterations) and iters (active-set steps, 0 when the unconstrained solution is feasible) are group-uniform.
+// n = N = 9 .. 16 (r = lane & 15): boxqp_active_set of boxqp_rows.h with the 16-row ?posvx. d_r = Prow[r]; the other arguments
+// as boxqp_active_set's. The callable is a struct, not a lambda: with a lambda the compiler orders a few instructions of the
+// N = 15 and 16 instances differently; with the struct all sixteen compile to the code of the loop written out here.
 template <int N, class T>
 __device__ inline void boxqp_rows16(const T (&Prow)[kW16], T d_r, T q_r, T l_r, T u_r, T relTol, T absTol, uint32_t maxIterations,
                                     bool have_x, int r, int g, T& x_r, int& status, int& iters)
 {
+    static_assert(N >= 9, "n <= 8 is boxqp_rows");
+    struct {
+        const T (&Prow)[kW16]; T d_r; int r;
+        __device__ __forceinline__ int operator()(T rhs_r, bool live_r, int order, T& xs_r) const
+        {
 #pragma clang fp contract(off)
-    static_assert(N >= 9 && N <= kW16, "row r = lane & 15; n <= 8 is boxqp_rows");
-    const bool el = r < N;
-    const T lo = el ? l_r : -Lim<T>::inf(), up = el ? u_r : Lim<T>::inf();
-    T x = el ? x_r : T(0);
-    int st = 0;
-    if (!have_x) {                                                       // QP:168-214
-        T xs;
-        const int info = posvx16<N, T>(Prow, d_r, -q_r, true, r, xs, N);
-        x = el ? xs : T(0);
-        st = info != 0 ? 1 : 0;
-    }
-    // QP:216-219: a feasible unconstrained solution is the answer (a NaN counts as infeasible)
-    const bool infeasible = rows_bits(el && !(lo <= x && x <= up), g) != 0;
-    bool run = st == 0 && infeasible;
-    st = run ? 2 : st;                                                   // QP:378 unless the loop says otherwise
-    int it = 0;
-    const uint32_t maxit = maxIterations ? maxIterations : (uint32_t)N * 10 + 100;   // QP:224-226
-    T la = 0, mu = 0;                                                    // QP:228-232
-    int fl = el ? 0 : 2;                                                 // -1 lower, 0 free, 1 upper; 2 = not an element
-    for (uint32_t step = 0; step < maxit; ++step) {                      // QP:234
-        if (__builtin_amdgcn_ballot_w64(run) == 0) break;
-        it = run ? (int)step + 1 : it;
-        {                                                                // QP:239-263
-            const T xl = x - lo, ux = up - x;
-            const bool toL = xl < 0 || (xl < relTol + absTol * vabs(lo) && la >= 0);
-            const bool toU = !toL && (ux < 0 || (ux < relTol + absTol * vabs(up) && mu >= 0));
-            const bool upd = run && el;
-            fl = upd ? (toL ? -1 : (toU ? 1 : 0)) : fl;
-            x = upd ? (toL ? lo : (toU ? up : x)) : x;
-            la = upd ? (toL ? la : T(0)) : la;
-            mu = upd ? (toU ? mu : T(0)) : mu;
+            return posvx16<N, T>(Prow, d_r, rhs_r, live_r, r, xs_r, order);
         }
-        const int sN = __builtin_popcount(rows_bits(fl == 0, g));
-        run = run && sN != N;                                            // QP:265-266 (quirk Q8): leaves with maxIterations
-        // right-hand side of the reduced system, QP:282-305: Kahan-Babuska-Neumaier over the bound variables, j ascending
-        T ks = q_r, kc = 0;
-        static_for<kW16>([&](auto JX) {
-            constexpr int j = JX.value;
-            if constexpr (j < N) {
-                const bool bj = dpp_row_bcast<j>(fl) != 0;
-                const T xj = dpp_row_bcast<j>(x);                        // a bound variable sits ON its bound
-                const T v = Prow[j] * xj;
-                const T t = ks + v;
-                const T kn = (vabs(ks) >= vabs(v)) ? kc + ((ks - t) + v) : kc + ((v - t) + ks);
-                kc = bj ? kn : kc;
-                ks = bj ? t : ks;
-            }
-        });
-        const T b_r = -(ks + kc);
-        const bool need = run && sN != 0;                                // QP:307-329
-        if (__builtin_amdgcn_ballot_w64(need) != 0) {
-            T xs;
-            const int info = posvx16<N, T>(Prow, d_r, b_r, fl == 0, r, xs, sN);
-            const bool failed = need && info != 0;
-            st = failed ? 1 : st;
-            run = run && !failed;
-            x = (need && !failed && fl == 0) ? xs : x;
-        }
-        // multipliers of the bound variables, QP:333-337 (two partial sums, as the reference's two dot products)
-        T v1 = 0, v2 = 0;
-        static_for<kW16>([&](auto JX) {
-            constexpr int j = JX.value;
-            if constexpr (j < N) {
-                const T xj = dpp_row_bcast<j>(x);
-                v1 = (j < r) ? __builtin_elementwise_fma(Prow[j], xj, v1) : v1;
-                v2 = (j >= r) ? __builtin_elementwise_fma(Prow[j], xj, v2) : v2;
-            }
-        });
-        const T val = v1 + v2 + q_r;
-        la = (run && fl == -1) ? val : la;
-        mu = (run && fl == 1) ? -val : mu;
-        // QP:339-347
-        const bool again_r = fl == -1 ? !(la >= 0) : (fl == 1 ? !(mu >= 0) : (fl == 0 ? !(x >= lo && x <= up) : false));
-        const bool again = rows_bits(again_r, g) != 0;
-        const bool done = run && !again;
-        x = (done && el) ? vmax(vmin(x, up), lo) : x;                    // QP:349 applyBounds
-        st = done ? 0 : st;
-        run = run && again;
-    }
-    x_r = el ? x : T(0);
-    status = st;
-    iters = it;
+    } solve{Prow, d_r, r};
+    boxqp_active_set<N, kW16, T>(Prow, q_r, l_r, u_r, relTol, absTol, maxIterations, have_x, r, g, solve, x_r, status, iters);
 }
-
-template <class T> struct BoxQpRows16Args {
-    const T* P;            // count x 256, row stride 16, lower triangle read
-    const T* q;            // count x 16
-    const T* l;            // 16 (bound_stride 0) or count x 16
-    const T* u;
-    T* x;                  // count x 16, in (kBoxQpUnconstrainedSolution) / out
-    int* status;           // count
-    int* iterations;       // count or nullptr
-    int count, bound_stride;
-    T relTolerance, absTolerance;
-    uint32_t maxIterations, flags;
-};
 
 // row r of problem p's symmetric matrix from its lower triangle (rows and columns >= N: 0), and its diagonal entry
 template <int N, class T>
@@ -256,7 +167,7 @@ __device__ __forceinline__ void load_row16(const T* __restrict__ P, int p, int r
 
 // a grid-stride over groups of four problems; a short last wave repeats the last problem and writes nothing for the repeats
 template <int N, class T>
-__global__ __launch_bounds__(64) void k_boxqp_rows16(BoxQpRows16Args<T> a)
+__global__ __launch_bounds__(64) void k_boxqp_rows16(BoxQpRowsArgs<T> a)
 {
     const int lane = threadIdx.x, r = lane & 15, g = lane >> 4;
     const bool have_x = (a.flags & kBoxQpUnconstrainedSolution) != 0;

@@ -6,7 +6,8 @@
 Compiles every unit that carries kernels in both trees with build.py's flags and `--offload-device-only -S` into
 OUT_DIR/{parent,branch}/<unit>.s, then compares per kernel the function body (label to .Lfunc_end) and the .amdhsa_kernel
 block as text after local labels are normalised, and prints VGPR / AGPR / scratch / static LDS from the kernels' metadata; for
-a kernel that differs also whether the instruction counts per opcode agree."""
+a kernel that differs also whether the instruction counts per opcode agree. A kernel whose parameter type was renamed is paired
+through RENAMES, applied to the demangled name; its own symbol is blanked in the compared text."""
 import collections
 import os
 import re
@@ -16,7 +17,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only", "-S"]
 UNITS = ["solver_loop", "launch_solve_d", "launch_solve_s", "unit_entries", "batched", "batched_d", "workloads_resident", "workloads",
-         "workloads_gemm", "solver_jacobian", "launch_jtj", "launch_broyden", "comm"]
+         "workloads_gemm", "solver_jacobian", "launch_jtj", "launch_broyden", "comm", "launch_boxqp", "launch_boxqp16_s", "launch_boxqp16_d"]
+RENAMES = {"BoxQpRows16Args": "BoxQpRowsArgs"}
 USER = ["user_model", "user_model_f64", "user_model_weighted"]
 
 
@@ -40,7 +42,7 @@ def kernels(path):
     code = {}
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", s, re.M | re.S):
         body = re.search(r"^" + re.escape(m.group(1)) + r":.*?^\.Lfunc_end[0-9]+:", s, re.M | re.S).group(0)
-        code[m.group(1)] = (norm(body), norm(m.group(2)))
+        code[m.group(1)] = tuple(norm(t.replace(m.group(1), "KERNEL")) for t in (body, m.group(2)))
     res = {}
     for m in re.finditer(r"- \.agpr_count:\s+(\d+).*?\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?"
                          r"\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)", s, re.S):
@@ -57,9 +59,14 @@ def opcounts(body):
     return c
 
 
-def demangle(names):
-    p = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True)
-    return dict(zip(names, p.stdout.splitlines()))
+def by_demangled_name(*dicts):
+    """the dicts re-keyed by the demangled kernel name after RENAMES"""
+    names = sorted(set().union(*dicts))
+    dm = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
+    for old, new in RENAMES.items():
+        dm = [d.replace(old, new) for d in dm]
+    dm = dict(zip(names, dm))
+    return [{dm[k]: v for k, v in d.items()} for d in dicts]
 
 
 def main(parent, branch, out):
@@ -68,12 +75,10 @@ def main(parent, branch, out):
     compile_tree(branch, bd)
     tot = same = 0
     for u in UNITS + USER:
-        pk, pr = kernels("%s/%s.s" % (pd, u))
-        bk, br = kernels("%s/%s.s" % (bd, u))
-        dm = demangle(sorted(set(pk) | set(bk)))
+        pk, pr, bk, br = by_demangled_name(*kernels("%s/%s.s" % (pd, u)), *kernels("%s/%s.s" % (bd, u)))
         print("== %s: %d kernels in the parent, %d in the branch" % (u, len(pk), len(bk)))
         for k in pk:
-            print("  " + dm[k])
+            print("  " + k)
             if k not in bk:
                 print("      only in the parent")
                 continue
@@ -88,7 +93,7 @@ def main(parent, branch, out):
                   % (("yes" if ident else "NO",) + tuple(v for pair in zip(pr[k], br[k]) for v in pair) + (extra,)))
         for k in bk:
             if k not in pk:
-                print("  " + dm[k] + "\n      only in the branch")
+                print("  " + k + "\n      only in the branch")
     print("== total: %d kernels present in both trees, %d text-identical" % (tot, same))
     return 0 if tot == same else 1
 

@@ -1,12 +1,14 @@
-"""Time of one batched BOXCQP launch (mir_lsq_batched_box_qp_s / _d: four problems a wave, csrc/boxqp_rows.h) against the
-only way there was before it, a loop over the one-problem host-pointer entry mir_solve_box_qp_gpu_*.
+"""Time of one batched BOXCQP launch (four problems a wave; --n 8: mir_lsq_batched_box_qp_s / _d, csrc/boxqp_rows.h; --n 16:
+mir_lsq_batched_box_qp16_s / _d, one matrix row per lane, csrc/boxqp_rows16.h) against the only way there was before it, a loop
+over the one-problem host-pointer entry mir_solve_box_qp_gpu_*.
 
-65 536 problems of order 8, P = A^T A / 12 + 0.05 I (A 12 x 8 standard normal), q = 2 N(0, 1), bounds c -+ w with c ~ N(0, 1),
-w ~ U(0.5, 3): about half the variables end on a bound (the share is printed). float32 and float64.
+65 536 problems of order n = 8 or 16, P = A^T A / m + 0.05 I (A m x n standard normal, m = n + 4), q = 2 N(0, 1), bounds c -+ w
+with c ~ N(0, 1), w ~ U(0.5, 3): about half the variables end on a bound (the share is printed). float32 and float64.
   * batched: device events around `reps` launches on one stream after a warm-up, the median per launch; operands resident.
   * loop: a host clock around a loop over the first 256 problems (each call allocates, copies in, launches, synchronises and
     copies out: that is the entry), per problem, extrapolated to the full count.
-Run from the repository root:  timeout 300 python scripts/probes/batched_boxqp.py [--out profiles/r10/batched_boxqp.txt]
+Run from the repository root:  timeout 300 python scripts/probes/batched_boxqp.py --n {8,16} [--out FILE]
+(profiles/r10/batched_boxqp.txt and profiles/r11/batched_boxqp16.txt are the first records at n = 8 and n = 16)
 """
 import argparse
 import ctypes as C
@@ -21,32 +23,32 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import mir_optim_amd as M          # noqa: E402
 from mir_optim_amd import api      # noqa: E402
 
-COUNT, N, SAMPLE = 65536, 8, 256
+COUNT, SAMPLE = 65536, 256
 
 
-def problems(dtype, seed=10):
+def problems(N, dtype, seed=10):
     rng = np.random.default_rng(seed)
-    A = rng.standard_normal((COUNT, 12, N))
-    P = np.einsum("pki,pkj->pij", A, A) / 12 + 0.05 * np.eye(N)
+    A = rng.standard_normal((COUNT, N + 4, N))
+    P = np.einsum("pki,pkj->pij", A, A) / (N + 4) + 0.05 * np.eye(N)
     q = 2 * rng.standard_normal((COUNT, N))
     c, w = rng.standard_normal((COUNT, N)), rng.uniform(0.5, 3.0, (COUNT, N))
     return tuple(a.astype(dtype) for a in (P, q, c - w, c + w))
 
 
-def batched_ms(dtype, P, q, l, u, reps=50):
-    suf = "s" if dtype == np.float32 else "d"
-    fn = getattr(api.lib(), "mir_lsq_batched_box_qp_" + suf)
+def batched_ms(N, dtype, P, q, l, u, reps=50):
+    W = 8 if N <= 8 else 16                                    # the layout's width: operands are padded to it
+    fn = getattr(api.lib(), "mir_lsq_batched_box_qp" + ("" if W == 8 else "16") + ("_s" if dtype == np.float32 else "_d"))
     dev = torch.device("cuda")
-    pad = lambda a, shape: torch.from_numpy(np.pad(a, [(0, 0)] + [(0, 8 - N)] * (a.ndim - 1))).to(dev).reshape(shape).contiguous()
-    dP, dq, dl, du = pad(P, (COUNT, 64)), pad(q, (COUNT, 8)), pad(l, (COUNT, 8)), pad(u, (COUNT, 8))
-    dx = torch.zeros((COUNT, 8), dtype=dP.dtype, device=dev)
+    pad = lambda a, shape: torch.from_numpy(np.pad(a, [(0, 0)] + [(0, W - N)] * (a.ndim - 1))).to(dev).reshape(shape).contiguous()
+    dP, dq, dl, du = pad(P, (COUNT, W * W)), pad(q, (COUNT, W)), pad(l, (COUNT, W)), pad(u, (COUNT, W))
+    dx = torch.zeros((COUNT, W), dtype=dP.dtype, device=dev)
     dst = torch.zeros(COUNT, dtype=torch.int32, device=dev)
     dit = torch.zeros(COUNT, dtype=torch.int32, device=dev)
     s = M.BoxQPSettings(dtype)
     stream = torch.cuda.current_stream().cuda_stream
 
     def launch():
-        rc = fn(C.addressof(s), COUNT, N, dP.data_ptr(), dq.data_ptr(), dl.data_ptr(), du.data_ptr(), 8, dx.data_ptr(),
+        rc = fn(C.addressof(s), COUNT, N, dP.data_ptr(), dq.data_ptr(), dl.data_ptr(), du.data_ptr(), W, dx.data_ptr(),
                 dst.data_ptr(), dit.data_ptr(), 0, stream)
         assert rc == 0, rc
     for _ in range(5):
@@ -73,13 +75,16 @@ def loop_ms_per_problem(dtype, P, q, l, u):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "r10", "batched_boxqp.txt"))
+    ap.add_argument("--n", type=int, choices=(8, 16), default=8)
+    ap.add_argument("--out", default=None, help="default: profiles/r12/batched_boxqp_n<N>.txt")
     args = ap.parse_args()
+    N = args.n
+    out = args.out or os.path.join("profiles", "r12", "batched_boxqp_n%d.txt" % N)
     lines = [f"batched BOXCQP on {torch.cuda.get_device_name(0)}; {api.lib().mir_lsq_version().decode()}",
              f"{COUNT} problems, n = {N}; loop baseline on the first {SAMPLE}, extrapolated", ""]
     for dtype in (np.float32, np.float64):
-        P, q, l, u = problems(dtype)
-        med, lo, hi, x, st, it = batched_ms(dtype, P, q, l, u)
+        P, q, l, u = problems(N, dtype)
+        med, lo, hi, x, st, it = batched_ms(N, dtype, P, q, l, u)
         per, xl, stl, itl = loop_ms_per_problem(dtype, P, q, l, u)
         active = float(np.mean((x == l) | (x == u)))
         agree = int(np.sum((st[:SAMPLE] == stl) & (it[:SAMPLE] == itl)))
@@ -93,8 +98,8 @@ def main():
                   f"max |x - x_loop| {np.max(np.abs(x[:SAMPLE].astype(np.float64) - xl)):.3e}", ""]
     text = "\n".join(lines)
     print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         f.write(text)
 
 

@@ -1,6 +1,7 @@
-"""Seeded families of small box-constrained QPs for the batched BOXCQP tests (tests/test_batched_boxqp_host.py on the CPU,
-tests/test_gpu_batched_boxqp.py on the device), and what the tests share: the oracle's answers, the margin screen, the KKT
-check. Nothing here needs a device.
+"""Seeded families of small box-constrained QPs for the batched BOXCQP tests of both layouts (tests/test_batched_boxqp_host.py
+and test_batched_boxqp16_host.py on the CPU, tests/test_gpu_batched_boxqp.py and test_gpu_batched_boxqp16.py on the device),
+and what the tests share: the oracle's answers, the margin screen, the KKT check, and the device tests' comparison rules
+(solve, same_bits, x_tolerance, check_against_oracle). Nothing here needs a device but a call of solve.
 
 A problem: P = A^T A / m + delta I (A m x n standard normal, m = n + 4, delta = 0.05; redrawn until cond_2(P) <= 1e3), q
 standard normal scaled by 2, bounds l = c - w, u = c + w around a centre c ~ N(0, 1) of half-width w ~ U(0.05, 1.5), each
@@ -18,7 +19,10 @@ import functools
 
 import numpy as np
 
+import mir_optim_amd as M
+
 NS = (1, 2, 3, 5, 8)
+NS16 = (9, 13, 16)                     # the 16-wide layout: lane 8 a row of its own, padding rows inside the row, none
 FAMILY_COUNT = 64
 COUNTS = (1, 3, 4, 5, 7, 257)
 MAX_SCREENED_OUT = 0.10
@@ -170,3 +174,54 @@ def mixed_wave(oracle, n, dtype, seed=777, budget=4000):
             if len(found) == (2 if n == 1 else 4):
                 break
     return found
+
+
+# ---------------------------------------------------------------- what the device tests of both layouts share
+def solve(P, q, l, u, dtype, **kw):
+    st, x, it = M.solveBoxQPBatched(P, q, l, u, dtype=dtype, **kw)
+    assert x.dtype == dtype and st.shape == it.shape == (len(q),) and x.shape == q.shape
+    return st, x, it
+
+
+def bits(x):
+    return np.ascontiguousarray(x).view(np.uint32 if x.dtype == np.float32 else np.uint64)
+
+
+def same_bits(a, b):
+    return all(np.array_equal(bits(x) if x.dtype.kind == "f" else x, bits(y) if y.dtype.kind == "f" else y) for x, y in zip(a, b))
+
+
+def x_tolerance(dtype, P, x64, xo):
+    """per-problem bound on max|x - x64| (the device tests' module docstrings); xo: the same-precision oracle's x"""
+    eps = np.finfo(dtype).eps
+    if dtype == np.float64:
+        return np.array([8 * eps * cond2(P[p]) * np.max(np.abs(x64[p])) for p in range(len(P))])
+    shown = float(np.max(np.abs(xo - x64)))
+    tol = max(4 * shown, 4 * eps * float(np.max(np.abs(x64))))
+    print(f"float oracle's largest distance from the f64 oracle: {shown:.3e}; tolerance {tol:.3e}")
+    return np.full(len(P), tol)
+
+
+def check_against_oracle(dev, ora, ora64, data, dtype, screened, idx=None):
+    """dev, ora, ora64: (status, x, iterations) of the device, the same-precision oracle and the f64 oracle on data = (P, q, l, u)
+    (bounds per problem); idx: the problems of the oracle arrays the device solved, in order"""
+    P, q, l, u = data
+    idx = np.arange(len(q)) if idx is None else idx
+    st, x, it = dev
+    x = x.astype(np.float64)
+    so, xo, io = (a[idx] for a in ora)
+    s64, x64, _ = (a[idx] for a in ora64)
+    P, q, l, u, scr = P[idx], q[idx], l[idx], u[idx], screened[idx]
+    assert np.array_equal(st, so), (st, so)
+    assert np.array_equal(it[scr], io[scr]), (it[scr], io[scr])
+    assert np.array_equal(active_set(x, l, u)[scr], active_set(xo, l, u)[scr])
+    eps = np.finfo(dtype).eps
+    ok = st == 0
+    need = [kkt_factor(P[p], q[p], l[p], u[p], x[p], eps) for p in np.flatnonzero(ok)]
+    print(f"KKT factor needed by the device's x: {max(need, default=0):.2f} (allowed {KKT_FACTOR})")
+    assert all(f <= KKT_FACTOR for f in need), max(need)
+    both = ok & (s64 == 0)
+    tol = x_tolerance(dtype, P, x64, xo)
+    dist = np.max(np.abs(x - x64), axis=1)
+    print(f"largest distance from the f64 oracle: {np.max(dist[both], initial=0):.3e}")
+    assert np.all(dist[both] <= tol[both]), (dist[both] / tol[both]).max()

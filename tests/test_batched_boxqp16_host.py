@@ -16,7 +16,7 @@ import boxqp_cases as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRECISIONS = [pytest.param("_s", np.float32, id="f32"), pytest.param("_d", np.float64, id="f64")]
-NS16 = (9, 13, 16)
+NS16 = B.NS16
 DTYPES = pytest.mark.parametrize("dtype", B.DTYPES, ids=["f32", "f64"])
 
 

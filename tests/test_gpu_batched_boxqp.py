@@ -20,60 +20,11 @@ import pytest
 
 import mir_optim_amd as M
 import boxqp_cases as B
+from boxqp_cases import check_against_oracle, same_bits, solve, x_tolerance
 
 pytestmark = pytest.mark.gpu
 
 DT = [pytest.param(np.float32, id="f32"), pytest.param(np.float64, id="f64")]
-
-
-def solve(P, q, l, u, dtype, **kw):
-    st, x, it = M.solveBoxQPBatched(P, q, l, u, dtype=dtype, **kw)
-    assert x.dtype == dtype and st.shape == it.shape == (len(q),)
-    return st, x, it
-
-
-def bits(x):
-    return np.ascontiguousarray(x).view(np.uint32 if x.dtype == np.float32 else np.uint64)
-
-
-def same_bits(a, b):
-    return all(np.array_equal(bits(x) if x.dtype.kind == "f" else x, bits(y) if y.dtype.kind == "f" else y) for x, y in zip(a, b))
-
-
-def x_tolerance(dtype, P, x64, xo):
-    """per-problem bound on max|x - x64| (module docstring); xo: the same-precision oracle's x"""
-    eps = np.finfo(dtype).eps
-    if dtype == np.float64:
-        return np.array([8 * eps * B.cond2(P[p]) * np.max(np.abs(x64[p])) for p in range(len(P))])
-    shown = float(np.max(np.abs(xo - x64)))
-    tol = max(4 * shown, 4 * eps * float(np.max(np.abs(x64))))
-    print(f"float oracle's largest distance from the f64 oracle: {shown:.3e}; tolerance {tol:.3e}")
-    return np.full(len(P), tol)
-
-
-def check_against_oracle(dev, ora, ora64, data, dtype, screened, idx=None):
-    """dev, ora, ora64: (status, x, iterations) of the device, the same-precision oracle and the f64 oracle on data = (P, q, l, u)
-    (bounds per problem); idx: the problems of the oracle arrays the device solved, in order"""
-    P, q, l, u = data
-    idx = np.arange(len(q)) if idx is None else idx
-    st, x, it = dev
-    x = x.astype(np.float64)
-    so, xo, io = (a[idx] for a in ora)
-    s64, x64, _ = (a[idx] for a in ora64)
-    P, q, l, u, scr = P[idx], q[idx], l[idx], u[idx], screened[idx]
-    assert np.array_equal(st, so), (st, so)
-    assert np.array_equal(it[scr], io[scr]), (it[scr], io[scr])
-    assert np.array_equal(B.active_set(x, l, u)[scr], B.active_set(xo, l, u)[scr])
-    eps = np.finfo(dtype).eps
-    ok = st == 0
-    need = [B.kkt_factor(P[p], q[p], l[p], u[p], x[p], eps) for p in np.flatnonzero(ok)]
-    print(f"KKT factor needed by the device's x: {max(need, default=0):.2f} (allowed {B.KKT_FACTOR})")
-    assert all(f <= B.KKT_FACTOR for f in need), max(need)
-    both = ok & (s64 == 0)
-    tol = x_tolerance(dtype, P, x64, xo)
-    dist = np.max(np.abs(x - x64), axis=1)
-    print(f"largest distance from the f64 oracle: {np.max(dist[both], initial=0):.3e}")
-    assert np.all(dist[both] <= tol[both]), (dist[both] / tol[both]).max()
 
 
 # ---------------------------------------------------------------- the random bounded family
