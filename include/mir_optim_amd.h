@@ -397,7 +397,8 @@ int mir_lsq_batched_box_qp16_d(const mir_box_qp_settings_d* settings, size_t cou
  * x: count x n (in/out), lower/upper: n (shared), t: m values shared by all problems (t_stride = 0) or count x m
  * (t_stride = m), data: count x m, results: count. All HOST pointers. The LM algorithm, statuses and counters are
  * those of mir_optimize_least_squares_s; problems whose step reaches a finite bound are completed by the general
- * solver (BOXCQP active set) transparently. Returns 0, or a negative value: -1 bad arguments, -2 no device, -3 a problem
+ * solver (BOXCQP active set) transparently, one problem at a time -- or, with MIR_LSQ_BATCHED_DEVICE_BOUNDS in
+ * options->variant, by the wave kernel itself in the same launch. Returns 0, or a negative value: -1 bad arguments, -2 no device, -3 a problem
  * does not fit its workgroup's LDS ((n + 2) m floats <= 160 KB - 512: m <= 4083 at n = 8, 8166 at n = 3), -4 / -5 a failed
  * allocation / launch. */
 enum { MIR_LSQ_MODEL_EXP_DECAY = 0, MIR_LSQ_MODEL_EXP3_AFFINE = 1,
@@ -412,6 +413,15 @@ enum { MIR_LSQ_BATCHED_NO_LADDER = 1 };   /* variant bit: every damped solve is 
                                              (boxcqp.d:194 per LS:1080); by default a solve covers lambda and the three values
                                              the rejection rule would give it next (four 16-lane groups of the wave), with
                                              the same steps, bit for bit */
+enum { MIR_LSQ_BATCHED_DEVICE_BOUNDS = 4 };   /* variant bit: a damped step that leaves the box is replaced INSIDE the wave kernel by
+                                             the solution of the reference's box QP (least_squares.d:1074-1085; boxcqp.d:122-379
+                                             with settings->qpSettings), so the one launch finishes every problem: no status
+                                             -100 from the kernel entries, nothing left to the general solver in the host
+                                             entries. A QP that does not end as solved ends its fit with numericError (-26), as
+                                             in the reference. Problems whose steps stay inside the box take the same steps, bit
+                                             for bit, with the bit and without it. Not the default: without the bit every entry
+                                             does what it always did. launch_batched<Model> answers -1 to it
+                                             (launch_batched_bounded<Model> is the header's entry) */
 typedef struct mir_lsq_batched_options {
     uint32_t struct_size;     /* = sizeof(mir_lsq_batched_options) */
     uint32_t variant;         /* MIR_LSQ_BATCHED_* bits; 0 = default */
@@ -436,7 +446,8 @@ int mir_optimize_least_squares_batched_s(const mir_least_squares_settings_s* set
  * `count` records in place; enqueued on options->stream, no synchronisation -- see mir_lsq_batched_options.basis for the one
  * exception): what bench.py --config cfg5 times. Problems whose step reaches a finite bound come back with status -100
  * (MIR_LSQ_BATCHED_NEEDS_GENERAL): the host entry above completes those with the general solver, this one leaves that to
- * the caller. Returns 0 when the launch succeeded. The kernel entry (_s and _d alike) checks its arguments (-1: model id and
+ * the caller -- unless options->variant has MIR_LSQ_BATCHED_DEVICE_BOUNDS: then the kernel solves the bounded steps itself
+ * and no problem comes back with -100 from either entry. Returns 0 when the launch succeeded. The kernel entry (_s and _d alike) checks its arguments (-1: model id and
  * options, then the pointers and t_stride) before it looks for a device (-2).
  * A caller with a residual model of its own -- the reference takes an arbitrary f, least_squares.d:73-80 -- compiles the
  * same kernel for it from include/mir_optim_amd_batched.hpp (launch_batched<Model>); the three built-in models are
@@ -451,7 +462,8 @@ int mir_lsq_batched_kernel_s(const mir_least_squares_settings_s* settings, size_
  * formulas, evaluated in double), contract and return codes as their _s twins; every array is double, the records are the _d
  * ones (32 bytes, written in place by the kernel entry), and a basis table passed in the options holds doubles. A problem
  * needs (n + 2) m doubles of LDS: m <= 2041 at n = 8, 4083 at n = 3. Problems whose step reaches a finite bound are completed
- * by mir_optimize_least_squares_gpu_d in the host entry, and come back with status -100 from the kernel entry. */
+ * by mir_optimize_least_squares_gpu_d in the host entry, and come back with status -100 from the kernel entry; with
+ * MIR_LSQ_BATCHED_DEVICE_BOUNDS the kernel finishes them, as in float. */
 int mir_optimize_least_squares_batched_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
                                          double* x, const double* lower, const double* upper,
                                          const double* t, size_t t_stride, const double* data,

@@ -33,7 +33,12 @@
 //     mir_optim_amd::launch_batched<MyModel>(&settings, count, m, x, lower, upper, t, t_stride, data, results, &options);
 // has the contract of mir_lsq_batched_kernel_s / _d (include/mir_optim_amd.h): every pointer a DEVICE pointer, enqueued on
 // options->stream, results in place, status -100 (MIR_LSQ_BATCHED_NEEDS_GENERAL) for a problem whose step reaches a finite
-// bound. tests/user_model/ holds a complete example that is compiled and compared with the float oracle.
+// bound. A caller with bounds that bind uses
+//     mir_optim_amd::launch_batched_bounded<MyModel>(...the same arguments...);
+// instead: it runs the bounded instance of the model's kernel, which solves the reference's box QP (BOXCQP, boxcqp.d:122-379)
+// for such a step inside the kernel, so every problem is finished by the one launch and none returns -100. The two are separate
+// templates so that a build which only calls launch_batched compiles the kernels it always compiled.
+// tests/user_model/ holds complete examples that are compiled and compared with the oracle (user_model_bounded.hip: bounds).
 //
 // Weights and covariance (mir_lsq_batched_extras, the trailing argument of launch_batched; include/mir_optim_amd.h says the same
 // of the C entries). With extras->weights the residual of row i is  w_i (eval(t_i, basis_i, x) - data_i)  -- w_i = 1 / sigma_i
@@ -45,7 +50,8 @@
 // launch_batched_covariance<Model>: per problem n x n values, cov = s^2 (J^T J)^-1 with J the weighted Jacobian at the final x
 // (grad or central differences, as the fit's options say) and s^2 = residual / (rows with nonzero weight - n), or s^2 = 1 with
 // MIR_LSQ_BATCHED_ABSOLUTE_SIGMA; +inf everywhere when J^T J is not positive definite or the degrees of freedom are <= 0, NaN
-// everywhere for a problem with a negative status (-100 included: finish it, then call launch_batched_covariance).
+// everywhere for a problem with a negative status (-100 included: finish it, then call launch_batched_covariance -- or fit with
+// launch_batched_bounded, which leaves no such problem).
 // tests/user_model/user_model_weighted.hip is the example.
 #pragma once
 
@@ -58,6 +64,7 @@
 
 #include "mir_optim_amd.h"
 #include "../mir_optim_amd/csrc/batched_kernel.h"
+#include "../mir_optim_amd/csrc/batched_bounded.h"
 
 namespace mir_optim_amd {
 
@@ -154,15 +161,26 @@ void enqueue_covariance(const batched_settings_t<Model>* S, size_t count, size_t
 }
 }  // namespace detail
 
-// Returns 0, or: -1 bad arguments, -3 a problem does not fit its workgroup's LDS, -4 allocation of the basis table failed,
-// -5 the launch failed. Does not synchronise (except in the documented hipMalloc fallback of the basis table).
-// A float model takes the _s records and float arrays, a double model the _d records and double arrays.
-// extras (optional): per-row weights and / or the covariance of the fitted parameters, DEVICE pointers (see the top of this file).
-template <class Model>
-int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
-                   const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
-                   size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
-                   const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
+namespace detail {
+// the k_lm_batched instance of a model: weighted or not, with the bounded step or without
+template <class Model, class Bounds>
+bool enqueue_fit(const mirlsq::BatchedArgs<batched_value_t<Model>>& a, bool weighted, size_t lds, hipStream_t stream)
+{
+    auto kern = weighted ? mirlsq::k_lm_batched<Model, true, Bounds> : mirlsq::k_lm_batched<Model, false, Bounds>;   // the host picks the instance
+    if (lds > 48 * 1024
+        && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return false;
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.count), dim3(64), lds, stream, a);
+    return true;
+}
+
+// launch_batched and launch_batched_bounded but for the fit kernel itself: enqueue(args, weighted, lds, stream) -> false when
+// the launch could not be made (the C entries of the library hand in the instances of another translation unit)
+template <class Model, class Enqueue>
+int launch_batched_with(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
+                        const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
+                        size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
+                        const mir_lsq_batched_options* opt, const mir_lsq_batched_extras* extras, Enqueue&& enqueue)
 {
     using namespace mirlsq;
     using T = batched_value_t<Model>;
@@ -189,18 +207,50 @@ int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, b
     a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
     a.results = reinterpret_cast<BatchedResult<T>*>(results);
     a.weights = static_cast<const T*>(e.weights); a.w_stride = (int)e.weight_stride;
-    auto kern = e.weights ? k_lm_batched<Model, true> : k_lm_batched<Model, false>;     // the host picks the instance
-    if (lds > 48 * 1024
-        && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return -5;
     detail::BasisTable<Model> basis;
     if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
     a.basis = basis.table;
-    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64), lds, stream, a);
+    if (!enqueue(a, e.weights != nullptr, lds, stream)) {
+        (void)basis.release(stream, hipSuccess);
+        return -5;
+    }
     if (e.covariance)
         detail::enqueue_covariance<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, a.variant, e, stream);
     const hipError_t err = basis.release(stream, hipGetLastError());
     return err == hipSuccess ? 0 : -5;
+}
+}  // namespace detail
+
+// Returns 0, or: -1 bad arguments, -3 a problem does not fit its workgroup's LDS, -4 allocation of the basis table failed,
+// -5 the launch failed. Does not synchronise (except in the documented hipMalloc fallback of the basis table).
+// A float model takes the _s records and float arrays, a double model the _d records and double arrays.
+// extras (optional): per-row weights and / or the covariance of the fitted parameters, DEVICE pointers (see the top of this file).
+// It instantiates the default kernels of the model only: with MIR_LSQ_BATCHED_DEVICE_BOUNDS in options->variant it returns -1
+// (call launch_batched_bounded).
+template <class Model>
+int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
+                   const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
+                   size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
+                   const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
+{
+    if (opt && (opt->variant & MIR_LSQ_BATCHED_DEVICE_BOUNDS)) return -1;
+    return detail::launch_batched_with<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, opt, extras,
+                                              detail::enqueue_fit<Model, mirlsq::BatchedNoBoundedStep>);
+}
+
+// launch_batched with the BOUNDED instance of the model's kernel (csrc/batched_bounded.h): a damped step that leaves the box is
+// replaced, inside the kernel, by the solution of the reference's box QP (least_squares.d:1074-1085, boxcqp.d:122-379 with
+// settings->qpSettings), so no problem returns -100; a QP that does not end as solved ends its fit with numericError (-26), as
+// in the reference. Same arguments and return codes; MIR_LSQ_BATCHED_DEVICE_BOUNDS in options->variant is accepted and not
+// needed. A problem whose steps stay inside the box takes the steps, bit for bit, of launch_batched.
+template <class Model>
+int launch_batched_bounded(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
+                           const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
+                           size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
+                           const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
+{
+    return detail::launch_batched_with<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, opt, extras,
+                                              detail::enqueue_fit<Model, mirlsq::BatchedBoxQpStep>);
 }
 
 // The covariance of the fitted parameters on its own: x (count x n) and results (the fit's records: status and residual are

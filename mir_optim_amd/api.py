@@ -29,7 +29,7 @@ __all__ = [
     "LeastSquaresException", "optimize", "optimizeLeastSquares", "solveBoxQP", "leastSquaresStatusString",
     "mir_least_squares_work_length", "mir_least_squares_iwork_length", "mir_box_qp_work_length",
     "mir_box_qp_iwork_length", "GpuOptions", "Stats", "lib", "workloads_lib", "device_count",
-    "DeviceBuffer", "Stream", "jtj", "fd_jtj", "DEVICE_CALLBACKS", "TIME_KERNELS", "optimizeLeastSquaresBatched", "batchedPosvx", "BATCHED_NO_LADDER",
+    "DeviceBuffer", "Stream", "jtj", "fd_jtj", "DEVICE_CALLBACKS", "TIME_KERNELS", "optimizeLeastSquaresBatched", "batchedPosvx", "BATCHED_NO_LADDER", "BATCHED_DEVICE_BOUNDS",
     "solveBoxQPBatched", "BOX_QP_UNCONSTRAINED_SOLUTION",
     "MODEL_EXP_DECAY", "MODEL_EXP3_AFFINE", "MODEL_EXP_DECAY_PAD8", "ResultS", "Trace", "TraceRecord", "Spline", "FitSplineResult", "fitSpline",
     "fit_spline_residuals", "variant_lr_cap",
@@ -702,6 +702,7 @@ def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None
 
 
 BATCHED_NO_LADDER = 1
+BATCHED_DEVICE_BOUNDS = 4       # MIR_LSQ_BATCHED_DEVICE_BOUNDS: bounded steps are solved inside the wave kernel (no -100, no fallback)
 BATCHED_ABSOLUTE_SIGMA = 1      # mir_lsq_batched_extras.flags
 
 

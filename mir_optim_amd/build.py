@@ -22,7 +22,8 @@ WORKLOADS_LIB = os.path.join(LIBDIR, "libmir_optim_amd_workloads.so")
 
 SOLVER_UNITS = ["abi.hip", "workspace.hip", "solver_loop.hip", "solver_jacobian.hip", "launch_jtj.hip", "launch_broyden.hip",
                 "launch_solve_d.hip", "launch_solve_s.hip", "batched.hip", "batched_d.hip", "comm.hip", "unit_entries.hip", "covariance.hip",
-                "launch_spd_inverse.hip", "launch_boxqp.hip", "launch_boxqp16_s.hip", "launch_boxqp16_d.hip", "fit_spline.cpp"]
+                "launch_spd_inverse.hip", "launch_boxqp.hip", "launch_boxqp16_s.hip", "launch_boxqp16_d.hip", "batched_bounded.hip",
+                "batched_bounded_d.hip", "fit_spline.cpp"]
 WORKLOAD_UNITS = ["workloads.hip", "workloads_gemm.hip", "workloads_resident.hip"]
 
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("MIR_OPTIM_AMD_CXXFLAGS", "").split()
@@ -101,23 +102,27 @@ def build_user_model_example(force=False, verbose=False):
     """tests/user_model/: a caller's own residual models compiled against include/mir_optim_amd_batched.hpp and
     include/mir_optim_amd_resident.hpp (the device headers of the batched fit and of the resident-J path) into a library of its own -- what a user of that header does. Built here so that it travels prebuilt.
     The double model of user_model_f64.hip goes into a library of its own next to it (user_model_f64_lib()), and so does the
-    weighted fit with covariance of user_model_weighted.hip (user_model_weighted_lib())."""
+    weighted fit with covariance of user_model_weighted.hip (user_model_weighted_lib()) and the fit with binding bounds of
+    user_model_bounded.hip (user_model_bounded_lib())."""
     root = os.path.dirname(HERE)
     src = os.path.join(root, "tests", "user_model", "user_model.hip")
     out = os.path.join(root, "tests", "user_model", "libuser_model.so")
     deps = [src, os.path.join(root, "include", "mir_optim_amd_batched.hpp"), os.path.join(root, "include", "mir_optim_amd.h"),
             os.path.join(CSRC, "batched_kernel.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "solve_types.h"),
-            os.path.join(CSRC, "lm_rules.h"),
+            os.path.join(CSRC, "lm_rules.h"), os.path.join(CSRC, "batched_bounded.h"), os.path.join(CSRC, "boxqp_rows.h"),
             os.path.join(root, "include", "mir_optim_amd_resident.hpp"), os.path.join(CSRC, "resident_kernel.h"),
             os.path.join(CSRC, "solve_wave16.h"), os.path.join(CSRC, "solve_kernel.h"), os.path.join(CSRC, "solve_lds.h")]
     if force or _stale(out, deps):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out, src], verbose)
     src64, out64 = user_model_f64_paths()
-    if force or _stale(out64, [src64] + deps[1:7]):
+    if force or _stale(out64, [src64] + deps[1:9]):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out64, src64], verbose)
     srcw, outw = user_model_weighted_paths()
-    if force or _stale(outw, [srcw] + deps[1:7]):
+    if force or _stale(outw, [srcw] + deps[1:9]):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", outw, srcw], verbose)
+    srcb, outb = user_model_bounded_paths()
+    if force or _stale(outb, [srcb] + deps[1:9]):
+        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", outb, srcb], verbose)
     return out
 
 
@@ -143,3 +148,15 @@ def user_model_weighted_lib(force=False, verbose=False):
     """Builds (when stale) and returns the path of tests/user_model/libuser_model_weighted.so."""
     build_user_model_example(force=force, verbose=verbose)
     return user_model_weighted_paths()[1]
+
+
+def user_model_bounded_paths():
+    """(source, library) of the caller's fit with binding bounds (tests/user_model/user_model_bounded.hip)"""
+    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
+    return os.path.join(d, "user_model_bounded.hip"), os.path.join(d, "libuser_model_bounded.so")
+
+
+def user_model_bounded_lib(force=False, verbose=False):
+    """Builds (when stale) and returns the path of tests/user_model/libuser_model_bounded.so."""
+    build_user_model_example(force=force, verbose=verbose)
+    return user_model_bounded_paths()[1]

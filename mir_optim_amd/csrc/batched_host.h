@@ -5,7 +5,8 @@
 //   batched_covariance_entry<T>  the covariance kernel on its own (mir_lsq_batched_covariance_s / _d),
 //   batched_posvx_entry<T>    the ?posvx unit entry (mir_lsq_batched_posvx_s / _d),
 //   batched_host_entry<T>     the host-pointer entry (mir_optimize_least_squares_batched_s / _d), which completes problems whose
-//                             step reaches a finite bound with the general solver (BOXCQP on the device, boxcqp.d:234-376).
+//                             step reaches a finite bound with the general solver (BOXCQP on the device, boxcqp.d:234-376) --
+//                             with MIR_LSQ_BATCHED_DEVICE_BOUNDS the kernel finishes them and that loop finds nothing to do.
 // batched.hip (float) and batched_d.hip (double) instantiate one precision each -- two translation units, so that the six
 // k_lm_batched instances compile in parallel -- and hold that precision's extern "C" forwarders.
 // Nothing here is process-wide state: the A/B switch of the ladder and the profiling buffer travel in mir_lsq_batched_options.
@@ -26,6 +27,44 @@ int with_builtin_model(int id, F&& f)
     case kModelExpDecayPad8: return f(typename BuiltinModel<kModelExpDecayPad8, T>::type{});
     }
     return -1;
+}
+
+// The BOUNDED kernel instances of the three built-in models (k_lm_batched<Model, WEIGHTED, BatchedBoxQpStep>, batched_bounded.h)
+// are compiled in translation units of their own -- batched_bounded.hip (float), batched_bounded_d.hip (double) -- so that
+// batched.hip / batched_d.hip compile the device code they always compiled and the build stays parallel. This is their launch:
+// false when it could not be made.
+bool batched_bounded_enqueue(int model, const BatchedArgs<float>& a, bool weighted, size_t lds, hipStream_t stream);
+bool batched_bounded_enqueue(int model, const BatchedArgs<double>& a, bool weighted, size_t lds, hipStream_t stream);
+// what the two units define it with
+template <class T>
+bool batched_bounded_enqueue_builtin(int model, const BatchedArgs<T>& a, bool weighted, size_t lds, hipStream_t stream)
+{
+    return with_builtin_model<T>(model, [&](auto mdl) {
+        return (int)mir_optim_amd::detail::enqueue_fit<decltype(mdl), BatchedBoxQpStep>(a, weighted, lds, stream);
+    }) == 1;
+}
+
+template <class Model> constexpr int builtin_model_id()
+{
+    using T = batched_value_t<Model>;
+    return std::is_same<Model, typename BuiltinModel<kModelExpDecay, T>::type>::value ? kModelExpDecay
+        : std::is_same<Model, typename BuiltinModel<kModelExp3Affine, T>::type>::value ? kModelExp3Affine : kModelExpDecayPad8;
+}
+
+// launch_batched<Model> for a built-in model as the C entries make it: the default instances of this unit, or -- with
+// MIR_LSQ_BATCHED_DEVICE_BOUNDS in the options -- the bounded ones of the other unit
+template <class Model, class T = batched_value_t<Model>>
+int launch_builtin(const typename Abi<T>::Settings* S, size_t count, size_t m, T* x, const T* lower, const T* upper, const T* t,
+                   size_t t_stride, const T* data, typename Abi<T>::Result* results, const mir_lsq_batched_options* o,
+                   const mir_lsq_batched_extras* extras)
+{
+    if (!(o && (o->variant & MIR_LSQ_BATCHED_DEVICE_BOUNDS)))
+        return mir_optim_amd::launch_batched<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, o, extras);
+    return mir_optim_amd::detail::launch_batched_with<Model>(
+        S, count, m, x, lower, upper, t, t_stride, data, results, o, extras,
+        [](const BatchedArgs<T>& a, bool weighted, size_t lds, hipStream_t stream) {
+            return batched_bounded_enqueue(builtin_model_id<Model>(), a, weighted, lds, stream);
+        });
 }
 
 // the options as this build understands them (struct_size-versioned like mir_lsq_gpu_options)
@@ -61,7 +100,7 @@ int batched_kernel_entry(const typename Abi<T>::Settings* S, size_t count, size_
         if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
         if (count != 0 && !device_available()) return -2;
         const mir_lsq_batched_options o = batched_options(options);
-        return mir_optim_amd::launch_batched<decltype(mdl)>(S, count, m, x, lower, upper, t, t_stride, data, results, &o, extras);
+        return launch_builtin<decltype(mdl)>(S, count, m, x, lower, upper, t, t_stride, data, results, &o, extras);
     });
 }
 
@@ -159,8 +198,8 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
     std::vector<Result> res(count);
     std::vector<T> x0(x, x + count * n);       // starts, for the fallback problems
     if (good && !bad) {
-        good = mir_optim_amd::launch_batched<Model>(S, count, m, dx, (const T*)(base + ol), (const T*)(base + ou), dt, t_stride, ddata,
-                                                    dres, &o, extras ? &de : nullptr) == 0;
+        good = launch_builtin<Model>(S, count, m, dx, (const T*)(base + ol), (const T*)(base + ou), dt, t_stride, ddata, dres, &o,
+                                     extras ? &de : nullptr) == 0;
         good = good && hipDeviceSynchronize() == hipSuccess
             && hipMemcpy(res.data(), dres, count * sizeof(Result), hipMemcpyDeviceToHost) == hipSuccess
             && hipMemcpy(x, dx, xb, hipMemcpyDeviceToHost) == hipSuccess;

@@ -8,8 +8,10 @@
 //     + one wave reduction, the n x n damped solve with one matrix row per lane (?posvx semantics: equilibrate,
 //     Cholesky, refine: posvx_rows), acceptance and the lambda/mu schedule exactly as the reference;
 //   * all control flow is wave-uniform, there is no barrier and no host round trip.
-// Problems whose step hits a finite bound are not finished here (BOXCQP's active-set loop is not part of this
-// kernel): they return status kBatchedNeedsGeneral and the host entry re-solves them with the general solver.
+// A problem whose step hits a finite bound: the default instances do not finish it (BOXCQP's active-set loop is not part of
+// them): it returns status kBatchedNeedsGeneral and the host entry re-solves it with the general solver. The BOUNDED instances
+// (third template parameter of k_lm_batched, batched_bounded.h; MIR_LSQ_BATCHED_DEVICE_BOUNDS) solve the step's box QP in
+// place, as the reference does (LS:1074-1085), and never return that status.
 #pragma once
 
 #include "common.h"
@@ -393,7 +395,7 @@ __global__ __launch_bounds__(64) void k_posvx_rows(const T* __restrict__ P, cons
 
 // -DMIRLSQ_BATCHED_TIMING: per problem, the shader-clock cycles (s_memtime) spent in [0] residual evaluations, [1] Jacobian
 // refreshes (FD or Broyden), [2] J^T J / J^T y with its reductions, [3] damped solves, [4] the whole fit, and [5] the number of
-// solve calls, [6] a trial's preparation, [7] an accepted step's bookkeeping, written to BatchedArgs::timing (10 x uint64 a problem). A profiling build only (scripts/probes/cfg5_phases.py).
+// solve calls, [6] a trial's preparation, [7] an accepted step's bookkeeping, [8] the box QPs of a bounded instance, written to BatchedArgs::timing (10 x uint64 a problem). A profiling build only (scripts/probes/cfg5_phases.py).
 #ifdef MIRLSQ_BATCHED_TIMING
 #define MIRLSQ_T0() const uint64_t t0_ = __builtin_readcyclecounter()
 #define MIRLSQ_T1(k) tacc[k] += __builtin_readcyclecounter() - t0_
@@ -418,7 +420,14 @@ template <class Model> constexpr int batched_waves_per_simd()
 // a batch of problems of different lengths is padded to a common m with zero-weight rows. Non-finite weights are the caller's
 // error: a NaN residual takes the reference's numericError exits. The unweighted instances do not read a.weights and are,
 // instruction for instruction, what they were before the parameter existed.
-template <class Model, bool WEIGHTED = false>
+// Bounds: what the kernel does with a damped step that leaves the box. BatchedNoBoundedStep (the default): the problem returns
+// kBatchedNeedsGeneral, as it always did. BatchedBoxQpStep (batched_bounded.h, which includes boxqp_rows.h; this header knows
+// neither): Bounds::step<N>(...) replaces the step by the solution of the box QP of LS:1074-1085. The default instances do
+// not see the parameter: they are, instruction for instruction, what they were before it existed.
+struct BatchedNoBoundedStep { static constexpr bool enabled = false; };
+constexpr uint32_t kBatchedDeviceBounds = 4u;  // MIR_LSQ_BATCHED_DEVICE_BOUNDS: the host launches a bounded instance (the kernel does not read the bit)
+
+template <class Model, bool WEIGHTED = false, class Bounds = BatchedNoBoundedStep>
 __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batched(BatchedArgs<batched_value_t<Model>> a)
 {
     // Nothing in this body is left to the compiler's choice of what to fuse: contraction is off and every multiply-add that is
@@ -693,8 +702,24 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
                 if (!((lo[j] - x[j]) <= sol[j] && sol[j] <= (up[j] - x[j]))) feasible = false;   // QP:216-219
                 if (!(sol[j] <= sol[j])) nan = true;
             }
-            if (nan) { ret.status = -26; break; }                          // LS:1087
-            if (!feasible) { ret.status = kBatchedNeedsGeneral; break; }   // active-set loop: general solver
+            if constexpr (Bounds::enabled) {
+                // LS:1074-1085: the box QP of this level's system (P = J^T J + this level's lambda: the level is used only while
+                // lambda is bit for bit the ladder's value), started from the level's unconstrained solution. The ladder is not
+                // touched: its other levels stay valid across rejections.
+                if (!feasible) {
+                    MIRLSQ_T0();
+                    const bool solved = Bounds::template step<N>(JJrow, Jy_r, lambda, lo, up, x, S, r, lane >> 4, sol);
+                    MIRLSQ_T1(8);
+                    if (!solved) { ret.status = -26; break; }              // LS:1083
+                    nan = false;
+#pragma unroll
+                    for (int j = 0; j < NMAX; ++j) if (j < N && !(sol[j] <= sol[j])) nan = true;
+                }
+                if (nan) { ret.status = -26; break; }                      // LS:1087
+            } else {
+                if (nan) { ret.status = -26; break; }                      // LS:1087
+                if (!feasible) { ret.status = kBatchedNeedsGeneral; break; }   // active-set loop: general solver
+            }
             T trial[NMAX], ndd = 0;
 #pragma unroll
             for (int j = 0; j < NMAX; ++j) {

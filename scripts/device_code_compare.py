@@ -18,8 +18,11 @@ from concurrent.futures import ThreadPoolExecutor
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only", "-S"]
 UNITS = ["solver_loop", "launch_solve_d", "launch_solve_s", "unit_entries", "batched", "batched_d", "workloads_resident", "workloads",
          "workloads_gemm", "solver_jacobian", "launch_jtj", "launch_broyden", "comm", "launch_boxqp", "launch_boxqp16_s", "launch_boxqp16_d"]
-RENAMES = {"BoxQpRows16Args": "BoxQpRowsArgs"}
+# (a defaulted template parameter that the parent did not have is dropped from the name: k_lm_batched's Bounds, profiles/r13)
+RENAMES = {"BoxQpRows16Args": "BoxQpRowsArgs", ", mirlsq::BatchedNoBoundedStep>": ">"}
 USER = ["user_model", "user_model_f64", "user_model_weighted"]
+NEW_UNITS = ["batched_bounded", "batched_bounded_d"]        # in the branch only: their kernels are listed, not compared
+NEW_USER = ["user_model_bounded"]
 
 
 def compile_tree(tree, out):
@@ -27,6 +30,10 @@ def compile_tree(tree, out):
     cmds = [["hipcc"] + FLAGS + (["-fopenmp"] if u.startswith("workloads") else []) + ["mir_optim_amd/csrc/%s.hip" % u, "-o", "%s/%s.s" % (out, u)]
             for u in UNITS]
     cmds += [["hipcc"] + FLAGS + ["-I", "include", "tests/user_model/%s.hip" % u, "-o", "%s/%s.s" % (out, u)] for u in USER]
+    cmds += [["hipcc"] + FLAGS + ["mir_optim_amd/csrc/%s.hip" % u, "-o", "%s/%s.s" % (out, u)]
+             for u in NEW_UNITS if os.path.exists(os.path.join(tree, "mir_optim_amd/csrc/%s.hip" % u))]
+    cmds += [["hipcc"] + FLAGS + ["-I", "include", "tests/user_model/%s.hip" % u, "-o", "%s/%s.s" % (out, u)]
+             for u in NEW_USER if os.path.exists(os.path.join(tree, "tests/user_model/%s.hip" % u))]
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
         list(ex.map(lambda c: subprocess.check_call(c, cwd=tree, stderr=subprocess.DEVNULL), cmds))
 
@@ -38,6 +45,8 @@ def norm(t):
 
 
 def kernels(path):
+    if not os.path.exists(path):
+        return {}, {}
     s = open(path).read()
     code = {}
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", s, re.M | re.S):
@@ -74,7 +83,7 @@ def main(parent, branch, out):
     compile_tree(parent, pd)
     compile_tree(branch, bd)
     tot = same = 0
-    for u in UNITS + USER:
+    for u in UNITS + USER + NEW_UNITS + NEW_USER:
         pk, pr, bk, br = by_demangled_name(*kernels("%s/%s.s" % (pd, u)), *kernels("%s/%s.s" % (bd, u)))
         print("== %s: %d kernels in the parent, %d in the branch" % (u, len(pk), len(bk)))
         for k in pk:
@@ -93,7 +102,7 @@ def main(parent, branch, out):
                   % (("yes" if ident else "NO",) + tuple(v for pair in zip(pr[k], br[k]) for v in pair) + (extra,)))
         for k in bk:
             if k not in pk:
-                print("  " + k + "\n      only in the branch")
+                print("  " + k + "\n      only in the branch   VGPR %d  AGPR %d  scratch %d  static LDS %d" % br[k])
     print("== total: %d kernels present in both trees, %d text-identical" % (tot, same))
     return 0 if tot == same else 1
 
