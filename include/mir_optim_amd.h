@@ -537,6 +537,41 @@ int mir_lsq_batched_covariance_d(const mir_least_squares_settings_d* settings, s
                                  const mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
                                  const mir_lsq_batched_extras* extras);
 
+/* Batched fits of models with 9 to 16 PARAMETERS, double precision: one wavefront per problem as above, in a kernel of its own
+ * (csrc/batched16_kernel.h): J is held in LDS with a row stride of 16, J^T J is one 16 x 16 tile of the f64 matrix instruction,
+ * and the n x n work of a pass runs in the 16-lane-row layout of mir_lsq_batched_box_qp16_d. Finite bounds are handled inside
+ * the kernel (the reference's box QP, boxcqp.d:122-379): no problem returns -100 and nothing is left to the general solver; a QP
+ * that does not end as solved ends its fit with numericError (-26). Every solve is made for one damping value.
+ *   MIR_LSQ_MODEL16_EXP_HARM16     n = 16   p0 exp(-t p1) + p2 + sum_{j = 3 .. 15} p_j h_j(t),  h_j = sin(k w t) for odd j and
+ *                                           cos(k w t) for even j, k = (j - 1) / 2 (integer division), w = pi / 2: seven sines
+ *                                           and six cosines, a 13-value per-row basis (options->basis: 13 doubles a row)
+ *   MIR_LSQ_MODEL16_GAUSS3_AFFINE  n = 11   sum_{k < 3} p_{3k} exp(-((t - p_{3k+1}) / p_{3k+2})^2 / 2) + p9 + p10 t
+ * The ids start at 16 and belong to these entries alone: every other batched entry answers -1 to them, and these answer -1 to
+ * 0, 1 and 2. Arguments as mir_optimize_least_squares_batched_ex_d (HOST pointers) and mir_lsq_batched_kernel_ex_d (DEVICE
+ * pointers, enqueued on options->stream, results in place, no synchronisation except for a basis table the call had to
+ * allocate). extras must be NULL or carry neither weights nor covariance: anything else is -1 (the argument is there so that
+ * the signature need not change when they arrive). options->variant: MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN is honoured (-1 for a
+ * model without a derivative: GAUSS3_AFFINE); MIR_LSQ_BATCHED_NO_LADDER and MIR_LSQ_BATCHED_DEVICE_BOUNDS are accepted and
+ * change nothing. Checks in the usual order: -1 for the model id, the options and the extras, then the pointers and t_stride,
+ * then -2 for the device; -3: m = 0 or a problem does not fit its workgroup's LDS ((16 + 2) m + 272 doubles <= 160 KB - 512:
+ * m <= 1119); -4 / -5 a failed allocation / launch. A caller's own model of this size: launch_batched16<Model> of
+ * include/mir_optim_amd_batched.hpp. */
+enum { MIR_LSQ_MODEL16_EXP_HARM16 = 16, MIR_LSQ_MODEL16_GAUSS3_AFFINE = 17 };
+int mir_optimize_least_squares_batched16_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                                           double* x, const double* lower, const double* upper,
+                                           const double* t, size_t t_stride, const double* data,
+                                           mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
+                                           const mir_lsq_batched_extras* extras);
+int mir_lsq_batched16_kernel_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                               double* x, const double* lower, const double* upper,
+                               const double* t, size_t t_stride, const double* data,
+                               mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
+                               const mir_lsq_batched_extras* extras);
+/* Unit-level access to the J^T J stage of that kernel: J count x m x n (row-major, 1 <= n <= 16) and y count x m give, per
+ * problem, the 16 x 16 tile J^T J (exactly symmetric; rows and columns >= n are zero) and the 16 values J^T y. DEVICE pointers,
+ * enqueued on `stream`. -1 bad arguments, -3 m = 0 or (17 m + 272) doubles above the LDS limit, -2 no device, -5 launch. */
+int mir_lsq_batched16_jtj_d(size_t count, size_t m, size_t n, const double* J, const double* y, double* JJ, double* Jy, void* stream);
+
 /* Resident-J solver (include/mir_optim_amd_resident.hpp, launch_resident<Model>): the whole loop of least_squares.d:972-1175
  * in ONE cooperative launch for problems whose Jacobian, residuals and per-row data fit the LDS of the chip (BASELINE
  * cfg 2). The residual model is a compile-time type of the caller's, as on the batched path. Options and statistics of

@@ -53,6 +53,11 @@
 // everywhere for a problem with a negative status (-100 included: finish it, then call launch_batched_covariance -- or fit with
 // launch_batched_bounded, which leaves no such problem).
 // tests/user_model/user_model_weighted.hip is the example.
+//
+// Models with 9 to 16 parameters (double only): launch_batched16<Model>, at the end of this file. The model contract is the one
+// above with `using value_type = double;`, 9 <= n <= 16 and 16 entries in x (x[n..16) = 0); the kernel is a different one
+// (mir_optim_amd/csrc/batched16_kernel.h: J^T J on the matrix unit, the n x n work in the 16-lane-row layout, bounds always
+// handled in the kernel) and takes (16 + 2) m + 272 doubles of LDS: m <= 1119. tests/user_model/user_model_n16.hip is the example.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -65,6 +70,7 @@
 #include "mir_optim_amd.h"
 #include "../mir_optim_amd/csrc/batched_kernel.h"
 #include "../mir_optim_amd/csrc/batched_bounded.h"
+#include "../mir_optim_amd/csrc/batched16_kernel.h"
 
 namespace mir_optim_amd {
 
@@ -288,6 +294,62 @@ void launch_model_residual(const batched_value_t<Model>* t, const batched_value_
 {
     hipLaunchKernelGGL(mirlsq::k_batched_model_eval<Model>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, t, data, x, y, (int)m,
                        weights);
+}
+
+// ---- 9 <= n <= 16, double: k_lm_batched16 (mir_optim_amd/csrc/batched16_kernel.h) --------------------------------------------
+// LDS bytes one problem needs at m rows: J with a row stride of 16, y, the trial residual, the 16 x 16 J^T J tile and J^T y.
+// launch_batched16 returns -3 when it exceeds kBatchedLdsLimit: (16 + 2) 8 m + 2176 <= 160 KB - 512, m <= kBatched16MaxRows.
+template <class Model> constexpr size_t batched16_lds_bytes(size_t m)
+{
+    return ((size_t)(mirlsq::kW16 + 2) * m + mirlsq::kBatched16TileDoubles) * sizeof(double);
+}
+constexpr size_t kBatched16MaxRows = (kBatchedLdsLimit - mirlsq::kBatched16TileDoubles * sizeof(double)) / ((mirlsq::kW16 + 2) * sizeof(double));
+static_assert(kBatched16MaxRows == 1119, "the m limit the headers document");
+
+// launch_batched for a double model with 9 to 16 parameters. Same contract: every pointer a DEVICE pointer, enqueued on
+// options->stream, results in place, no synchronisation except in the hipMalloc fallback of the basis table. Returns 0, or -1
+// bad arguments (also MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN for a model without grad), -3 m = 0 or above kBatched16MaxRows, -4
+// allocation of the basis table, -5 the launch failed. Finite bounds are handled inside the kernel (the reference's box QP,
+// boxcqp.d:122-379): no problem returns -100; every solve is made for one damping value. MIR_LSQ_BATCHED_NO_LADDER and
+// MIR_LSQ_BATCHED_DEVICE_BOUNDS are accepted and change nothing. No weights, no covariance.
+template <class Model>
+int launch_batched16(const mir_least_squares_settings_d* S, size_t count, size_t m, double* x, const double* lower, const double* upper,
+                     const double* t, size_t t_stride, const double* data, mir_least_squares_result_d* results,
+                     const mir_lsq_batched_options* opt = nullptr)
+{
+    using namespace mirlsq;
+    static_assert(std::is_same<batched_value_t<Model>, double>::value, "launch_batched16: Model::value_type must be double");
+    static_assert(Model::n >= kBatched16NMin && Model::n <= kBatched16NMax, "9 <= n <= 16 (launch_batched takes n <= 8)");
+    static_assert(Model::nb >= 0, "nb: number of per-row basis values");
+    static_assert(sizeof(BatchedResult<double>) == sizeof(mir_least_squares_result_d)
+                  && offsetof(BatchedResult<double>, residual) == offsetof(mir_least_squares_result_d, residual)
+                  && offsetof(BatchedResult<double>, lambda) == offsetof(mir_least_squares_result_d, lambda),
+                  "the kernel writes the C result records in place");
+    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
+    if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
+    if (count == 0) return 0;
+    const size_t lds = batched16_lds_bytes<Model>(m);
+    if (m == 0 || lds > kBatchedLdsLimit) return -3;
+    hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
+    BatchedArgs<double> a{};
+    a.set = lm_settings_dev(S);
+    a.maxIterations = S->maxIterations; a.maxAge = S->maxAge;
+    a.count = (int)count; a.m = (int)m; a.t_stride = (int)t_stride;
+    a.variant = opt ? opt->variant : 0;
+    a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
+    a.results = reinterpret_cast<BatchedResult<double>*>(results);
+    detail::BasisTable<Model> basis;
+    if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
+    a.basis = basis.table;
+    auto kern = k_lm_batched16<Model>;
+    if (lds > 48 * 1024
+        && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)basis.release(stream, hipSuccess);
+        return -5;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64), lds, stream, a);
+    const hipError_t err = basis.release(stream, hipGetLastError());
+    return err == hipSuccess ? 0 : -5;
 }
 
 }  // namespace mir_optim_amd

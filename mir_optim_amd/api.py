@@ -31,7 +31,7 @@ __all__ = [
     "mir_box_qp_iwork_length", "GpuOptions", "Stats", "lib", "workloads_lib", "device_count",
     "DeviceBuffer", "Stream", "jtj", "fd_jtj", "DEVICE_CALLBACKS", "TIME_KERNELS", "optimizeLeastSquaresBatched", "batchedPosvx", "BATCHED_NO_LADDER", "BATCHED_DEVICE_BOUNDS",
     "solveBoxQPBatched", "BOX_QP_UNCONSTRAINED_SOLUTION",
-    "MODEL_EXP_DECAY", "MODEL_EXP3_AFFINE", "MODEL_EXP_DECAY_PAD8", "ResultS", "Trace", "TraceRecord", "Spline", "FitSplineResult", "fitSpline",
+    "MODEL_EXP_DECAY", "MODEL_EXP3_AFFINE", "MODEL_EXP_DECAY_PAD8", "MODEL16_EXP_HARM16", "MODEL16_GAUSS3_AFFINE", "batched16JtJ", "ResultS", "Trace", "TraceRecord", "Spline", "FitSplineResult", "fitSpline",
     "fit_spline_residuals", "variant_lr_cap",
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
     "VARIANT_SOLVE_BOUNDED", "VARIANT_DEBUG_SOLVE", "VARIANT_HOST_PROFILE", "VARIANT_SOLVE_GENERIC", "VARIANT_SOLVE_ONE_WORKGROUP", "VARIANT_DEBUG_HELPERS_ABSENT", "VARIANT_FD_HOST_COLUMNS",
@@ -42,6 +42,10 @@ __all__ = [
 MODEL_EXP_DECAY = 0      # n = 3: p0 exp(-t p1) + p2
 MODEL_EXP3_AFFINE = 1    # n = 8: p0 exp(-t p1) + p2 exp(-t p3) + p4 exp(-t p5) + p6 + p7 t
 MODEL_EXP_DECAY_PAD8 = 2  # n = 8: p0 exp(-t p1) + p2 + p3 sin 2t + p4 cos 2t + p5 sin 5t + p6 cos 5t + p7 t   (cfg 5)
+# models of the 9 .. 16 parameter entries (mir_optimize_least_squares_batched16_d; double only)
+MODEL16_EXP_HARM16 = 16     # n = 16: p0 exp(-t p1) + p2 + sum_{j=3..15} p_j h_j(t), h_j = sin / cos((j - 1) // 2 * pi / 2 * t) for odd / even j
+MODEL16_GAUSS3_AFFINE = 17  # n = 11: sum_{k<3} p_3k exp(-((t - p_3k+1) / p_3k+2)^2 / 2) + p9 + p10 t
+_MODELS16 = (MODEL16_EXP_HARM16, MODEL16_GAUSS3_AFFINE)
 
 DEVICE_CALLBACKS = 1
 TIME_KERNELS = 2
@@ -329,6 +333,13 @@ def lib():
                 fn.restype = C.c_int
                 fn.argtypes = [C.POINTER(S), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
                                C.c_void_p, C.POINTER(BatchedOptions), C.POINTER(BatchedExtras)]
+        for name in ("mir_optimize_least_squares_batched16_d", "mir_lsq_batched16_kernel_d"):
+            fn = getattr(L, name)
+            fn.restype = C.c_int
+            fn.argtypes = [C.POINTER(_Sd), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
+                           C.c_void_p, C.POINTER(BatchedOptions), C.POINTER(BatchedExtras)]
+        L.mir_lsq_batched16_jtj_d.restype = C.c_int
+        L.mir_lsq_batched16_jtj_d.argtypes = [sz, sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("box_qp_s", "box_qp_d", "box_qp16_s", "box_qp16_d"):
             fn = getattr(L, "mir_lsq_batched_" + name)
             fn.restype = C.c_int
@@ -660,7 +671,11 @@ def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None
     removes the row. covariance=True: returns (results, x, cov), cov count x n x n = s^2 inv(J^T J) at the returned x with
     s^2 = residual / (rows with nonzero weight - n), or s^2 = 1 with absolute_sigma=True; +inf for a singular J^T J or no
     degrees of freedom, NaN for a problem with a negative status. Any of the three goes through the _ex entry
-    (mir_optimize_least_squares_batched_ex_s / _d); a call without them is the call it always was."""
+    (mir_optimize_least_squares_batched_ex_s / _d); a call without them is the call it always was.
+    A MODEL16_* id (9 to 16 parameters) goes to mir_optimize_least_squares_batched16_d: dtype must be float64, and weights,
+    covariance and absolute_sigma raise ValueError (that entry has neither yet)."""
+    if int(model) in _MODELS16:
+        return _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weights, covariance, absolute_sigma)
     suf = _batched_suffix(dtype)
     dtype = np.float32 if suf == "s" else np.float64
     L = lib()
@@ -699,6 +714,53 @@ def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None
         raise RuntimeError(f"mir_optimize_least_squares_batched_ex_{suf} failed: {rc}")
     res = [LeastSquaresResult(r) for r in raw]
     return (res, x, cov) if covariance else (res, x)
+
+
+def _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weights, covariance, absolute_sigma):
+    """optimizeLeastSquaresBatched for a MODEL16_* id"""
+    if np.dtype(dtype) != np.float64:
+        raise ValueError(f"the MODEL16_* models are fitted in float64 only, not {np.dtype(dtype)}: pass dtype=np.float64")
+    if weights is not None or covariance or absolute_sigma:
+        raise ValueError("the MODEL16_* models take neither weights nor covariance")
+    L = lib()
+    x = np.array(x, dtype=np.float64, order="C")
+    count, n = x.shape
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    m = data.shape[1]
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    t_stride = 0 if t.ndim == 1 else m
+    lo = np.full(n, -np.inf) if l is None else np.ascontiguousarray(l, dtype=np.float64)
+    up = np.full(n, np.inf) if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    if settings is None:
+        settings = LeastSquaresSettings(np.float64)
+    raw = (_Rd * count)()
+    rc = L.mir_optimize_least_squares_batched16_d(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data,
+                                                  up.ctypes.data, t.ctypes.data, t_stride, data.ctypes.data, raw,
+                                                  C.byref(BatchedOptions(variant=variant)), None)
+    if rc != 0:
+        raise RuntimeError(f"mir_optimize_least_squares_batched16_d failed: {rc}")
+    return [LeastSquaresResult(r) for r in raw], x
+
+
+def batched16JtJ(J, y):
+    """The J^T J stage of the 9 .. 16 parameter batched kernel on its own (mir_lsq_batched16_jtj_d): J count x m x n (n <= 16),
+    y count x m. Returns (JJ count x 16 x 16, Jy count x 16)."""
+    L = lib()
+    J = np.ascontiguousarray(J, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    count, m, n = J.shape
+    dJ, dy = DeviceBuffer(J), DeviceBuffer(y)
+    dJJ = DeviceBuffer(nbytes=count * 256 * 8, dtype=np.float64, shape=(count, 16, 16))
+    dJy = DeviceBuffer(nbytes=count * 16 * 8, dtype=np.float64, shape=(count, 16))
+    st = Stream()
+    rc = L.mir_lsq_batched16_jtj_d(count, m, n, dJ.ptr, dy.ptr, dJJ.ptr, dJy.ptr, st.handle)
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_batched16_jtj_d failed: {rc}")
+    st.synchronize()
+    JJ, Jy = dJJ.download().copy(), dJy.download().copy()
+    for b in (dJ, dy, dJJ, dJy):
+        b.free()
+    return JJ, Jy
 
 
 BATCHED_NO_LADDER = 1
