@@ -549,8 +549,8 @@ int mir_lsq_batched_covariance_d(const mir_least_squares_settings_d* settings, s
  * The ids start at 16 and belong to these entries alone: every other batched entry answers -1 to them, and these answer -1 to
  * 0, 1 and 2. Arguments as mir_optimize_least_squares_batched_ex_d (HOST pointers) and mir_lsq_batched_kernel_ex_d (DEVICE
  * pointers, enqueued on options->stream, results in place, no synchronisation except for a basis table the call had to
- * allocate). extras must be NULL or carry neither weights nor covariance: anything else is -1 (the argument is there so that
- * the signature need not change when they arrive). options->variant: MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN is honoured (-1 for a
+ * allocate). extras must be NULL or carry neither weights nor covariance: anything else is -1 (weights and covariance have
+ * entries of their own, the _ex entries below). options->variant: MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN is honoured (-1 for a
  * model without a derivative: GAUSS3_AFFINE); MIR_LSQ_BATCHED_NO_LADDER and MIR_LSQ_BATCHED_DEVICE_BOUNDS are accepted and
  * change nothing. Checks in the usual order: -1 for the model id, the options and the extras, then the pointers and t_stride,
  * then -2 for the device; -3: m = 0 or a problem does not fit its workgroup's LDS ((16 + 2) m + 272 doubles <= 160 KB - 512:
@@ -567,6 +567,33 @@ int mir_lsq_batched16_kernel_d(const mir_least_squares_settings_d* settings, siz
                                const double* t, size_t t_stride, const double* data,
                                mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
                                const mir_lsq_batched_extras* extras);
+/* Per-row WEIGHTS and the COVARIANCE of the fitted parameters for these models: the counterparts of the n <= 8 _ex entries and
+ * of mir_lsq_batched_covariance_d, with their meaning of mir_lsq_batched_extras (weights w_i = 1 / sigma_i multiply the residual
+ * of their row wherever a residual or a Jacobian row is formed; a weight of exactly 0 removes its row, which is how problems of
+ * different lengths share a launch; covariance = s^2 (J^T J)^-1 at the returned x, n x n values a problem, row-major and
+ * symmetric, s^2 = residual / (rows with a nonzero weight - n) or 1 with MIR_LSQ_BATCHED_ABSOLUTE_SIGMA; every entry +inf when
+ * a pivot of the factorization is not positive or the degrees of freedom are <= 0, NaN when the problem's status is negative).
+ * The two entries above keep answering -1 to such extras; these take them, and with extras == NULL they make the fit of the
+ * entries above. Arguments, models and return codes are those of the entries above, the order of the checks that of the
+ * n <= 8 _ex entries (the host entry answers -1 to a non-finite weight). The weights are read from global memory: the LDS of
+ * the fit and m <= 1119 are unchanged; the covariance kernel takes (16 + 1) m + 272 doubles. The kernel entry computes the
+ * covariance on the same stream right after the fit; mir_lsq_batched16_covariance_d (DEVICE pointers) computes it alone from
+ * the x and the result records (status and residual are read) that a fit left: extras->covariance is required (-1). */
+int mir_optimize_least_squares_batched16_ex_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                                              double* x, const double* lower, const double* upper,
+                                              const double* t, size_t t_stride, const double* data,
+                                              mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
+                                              const mir_lsq_batched_extras* extras);
+int mir_lsq_batched16_kernel_ex_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                                  double* x, const double* lower, const double* upper,
+                                  const double* t, size_t t_stride, const double* data,
+                                  mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
+                                  const mir_lsq_batched_extras* extras);
+int mir_lsq_batched16_covariance_d(const mir_least_squares_settings_d* settings, size_t count, size_t m, int model,
+                                   const double* x, const double* lower, const double* upper,
+                                   const double* t, size_t t_stride, const double* data,
+                                   const mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
+                                   const mir_lsq_batched_extras* extras);
 /* Unit-level access to the J^T J stage of that kernel: J count x m x n (row-major, 1 <= n <= 16) and y count x m give, per
  * problem, the 16 x 16 tile J^T J (exactly symmetric; rows and columns >= n are zero) and the 16 values J^T y. DEVICE pointers,
  * enqueued on `stream`. -1 bad arguments, -3 m = 0 or (17 m + 272) doubles above the LDS limit, -2 no device, -5 launch. */

@@ -58,6 +58,8 @@
 // above with `using value_type = double;`, 9 <= n <= 16 and 16 entries in x (x[n..16) = 0); the kernel is a different one
 // (mir_optim_amd/csrc/batched16_kernel.h: J^T J on the matrix unit, the n x n work in the 16-lane-row layout, bounds always
 // handled in the kernel) and takes (16 + 2) m + 272 doubles of LDS: m <= 1119. tests/user_model/user_model_n16.hip is the example.
+// Weights and covariance work as above through the trailing extras of launch_batched16 and launch_batched16_covariance<Model>
+// (k_lm_batched16<Model, true>, k_batched16_covariance<Model>); tests/user_model/user_model_n16_weighted.hip is the example.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -306,16 +308,37 @@ template <class Model> constexpr size_t batched16_lds_bytes(size_t m)
 constexpr size_t kBatched16MaxRows = (kBatchedLdsLimit - mirlsq::kBatched16TileDoubles * sizeof(double)) / ((mirlsq::kW16 + 2) * sizeof(double));
 static_assert(kBatched16MaxRows == 1119, "the m limit the headers document");
 
-// launch_batched for a double model with 9 to 16 parameters. Same contract: every pointer a DEVICE pointer, enqueued on
-// options->stream, results in place, no synchronisation except in the hipMalloc fallback of the basis table. Returns 0, or -1
-// bad arguments (also MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN for a model without grad), -3 m = 0 or above kBatched16MaxRows, -4
-// allocation of the basis table, -5 the launch failed. Finite bounds are handled inside the kernel (the reference's box QP,
-// boxcqp.d:122-379): no problem returns -100; every solve is made for one damping value. MIR_LSQ_BATCHED_NO_LADDER and
-// MIR_LSQ_BATCHED_DEVICE_BOUNDS are accepted and change nothing. No weights, no covariance.
-template <class Model>
-int launch_batched16(const mir_least_squares_settings_d* S, size_t count, size_t m, double* x, const double* lower, const double* upper,
-                     const double* t, size_t t_stride, const double* data, mir_least_squares_result_d* results,
-                     const mir_lsq_batched_options* opt = nullptr)
+// LDS bytes of the covariance kernel of these models (k_batched16_covariance: J, one m-vector, the tile): below the fit's.
+constexpr size_t batched16_covariance_lds_bytes(size_t m)
+{
+    return ((size_t)(mirlsq::kW16 + 1) * m + mirlsq::kBatched16TileDoubles) * sizeof(double);
+}
+
+namespace detail {
+// The kernels a launch_batched16 may enqueue: every instance of the model. (The library's entries without extras hand in a
+// set with the unweighted fit alone, so that their translation unit compiles the device code it always compiled.)
+template <class Model> struct Batched16Kernels {
+    static bool fit(const mirlsq::BatchedArgs<double>& a, bool weighted, size_t lds, hipStream_t stream)
+    {
+        auto kern = weighted ? mirlsq::k_lm_batched16<Model, true> : mirlsq::k_lm_batched16<Model, false>;   // the host picks the instance
+        if (lds > 48 * 1024
+            && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return false;
+        hipLaunchKernelGGL(kern, dim3((unsigned)a.count), dim3(64), lds, stream, a);
+        return true;
+    }
+    static bool covariance(const mirlsq::BatchedCovArgs<double>& c, size_t lds, hipStream_t stream)
+    {
+        auto kern = mirlsq::k_batched16_covariance<Model>;
+        if (lds > 48 * 1024
+            && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return false;
+        hipLaunchKernelGGL(kern, dim3((unsigned)c.count), dim3(64), lds, stream, c);
+        return true;
+    }
+};
+
+template <class Model> constexpr void batched16_model_checks()
 {
     using namespace mirlsq;
     static_assert(std::is_same<batched_value_t<Model>, double>::value, "launch_batched16: Model::value_type must be double");
@@ -325,7 +348,36 @@ int launch_batched16(const mir_least_squares_settings_d* S, size_t count, size_t
                   && offsetof(BatchedResult<double>, residual) == offsetof(mir_least_squares_result_d, residual)
                   && offsetof(BatchedResult<double>, lambda) == offsetof(mir_least_squares_result_d, lambda),
                   "the kernel writes the C result records in place");
+}
+
+template <class Model, class Kernels>
+bool enqueue_covariance16(const mir_least_squares_settings_d* S, size_t count, size_t m, const double* x, const double* lower,
+                          const double* upper, const double* t, size_t t_stride, const double* data,
+                          const mir_least_squares_result_d* results, const double* table, uint32_t variant,
+                          const mir_lsq_batched_extras& e, hipStream_t stream)
+{
+    mirlsq::BatchedCovArgs<double> c{};
+    c.jacobianEpsilon = S->jacobianEpsilon;
+    c.count = (int)count; c.m = (int)m; c.t = t; c.t_stride = (int)t_stride; c.data = data; c.x = x; c.lower = lower; c.upper = upper;
+    c.results = reinterpret_cast<const mirlsq::BatchedResult<double>*>(results);
+    c.basis = table;
+    c.weights = static_cast<const double*>(e.weights); c.w_stride = (int)e.weight_stride;
+    c.variant = variant; c.flags = e.flags;
+    c.cov = static_cast<double*>(e.covariance);
+    return Kernels::covariance(c, batched16_covariance_lds_bytes(m), stream);
+}
+
+// launch_batched16 but for the kernels themselves (Kernels::fit / ::covariance -> false when the launch could not be made)
+template <class Model, class Kernels>
+int launch_batched16_with(const mir_least_squares_settings_d* S, size_t count, size_t m, double* x, const double* lower,
+                          const double* upper, const double* t, size_t t_stride, const double* data,
+                          mir_least_squares_result_d* results, const mir_lsq_batched_options* opt, const mir_lsq_batched_extras* extras)
+{
+    using namespace mirlsq;
+    batched16_model_checks<Model>();
     if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
+    mir_lsq_batched_extras e;
+    if (!batched_extras(extras, m, e)) return -1;
     if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
     if (count == 0) return 0;
     const size_t lds = batched16_lds_bytes<Model>(m);
@@ -338,17 +390,65 @@ int launch_batched16(const mir_least_squares_settings_d* S, size_t count, size_t
     a.variant = opt ? opt->variant : 0;
     a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
     a.results = reinterpret_cast<BatchedResult<double>*>(results);
-    detail::BasisTable<Model> basis;
+    a.weights = static_cast<const double*>(e.weights); a.w_stride = (int)e.weight_stride;
+    BasisTable<Model> basis;
     if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
     a.basis = basis.table;
-    auto kern = k_lm_batched16<Model>;
-    if (lds > 48 * 1024
-        && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    bool launched = Kernels::fit(a, e.weights != nullptr, lds, stream);
+    if (launched && e.covariance)
+        launched = enqueue_covariance16<Model, Kernels>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, a.variant, e,
+                                                        stream);
+    if (!launched) {
         (void)basis.release(stream, hipSuccess);
         return -5;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)count), dim3(64), lds, stream, a);
     const hipError_t err = basis.release(stream, hipGetLastError());
+    return err == hipSuccess ? 0 : -5;
+}
+}  // namespace detail
+
+// launch_batched for a double model with 9 to 16 parameters. Same contract: every pointer a DEVICE pointer, enqueued on
+// options->stream, results in place, no synchronisation except in the hipMalloc fallback of the basis table. Returns 0, or -1
+// bad arguments (also MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN for a model without grad, and implausible extras), -3 m = 0 or above
+// kBatched16MaxRows, -4 allocation of the basis table, -5 a launch failed. Finite bounds are handled inside the kernel (the
+// reference's box QP, boxcqp.d:122-379): no problem returns -100; every solve is made for one damping value.
+// MIR_LSQ_BATCHED_NO_LADDER and MIR_LSQ_BATCHED_DEVICE_BOUNDS are accepted and change nothing.
+// extras (optional, DEVICE pointers), as for launch_batched: with extras->weights the weighted instance of the kernel runs
+// (k_lm_batched16<Model, true>; an unweighted launch runs the code it always ran); with extras->covariance the fit is followed,
+// on the same stream, by launch_batched16_covariance<Model>: count x n x n values, +inf / NaN in the degenerate cases named at
+// the top of this file. tests/user_model/user_model_n16_weighted.hip is the example.
+template <class Model>
+int launch_batched16(const mir_least_squares_settings_d* S, size_t count, size_t m, double* x, const double* lower, const double* upper,
+                     const double* t, size_t t_stride, const double* data, mir_least_squares_result_d* results,
+                     const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
+{
+    return detail::launch_batched16_with<Model, detail::Batched16Kernels<Model>>(S, count, m, x, lower, upper, t, t_stride, data, results,
+                                                                                 opt, extras);
+}
+
+// The covariance of the fitted parameters on its own, the counterpart of launch_batched_covariance: x (count x n) and results
+// (status and residual are read) as a launch_batched16 left them give extras->covariance (required; count x n x n doubles).
+// Device pointers, enqueued on options->stream; the return codes of launch_batched16.
+template <class Model, class Kernels = detail::Batched16Kernels<Model>>
+int launch_batched16_covariance(const mir_least_squares_settings_d* S, size_t count, size_t m, const double* x, const double* lower,
+                                const double* upper, const double* t, size_t t_stride, const double* data,
+                                const mir_least_squares_result_d* results, const mir_lsq_batched_options* opt,
+                                const mir_lsq_batched_extras* extras)
+{
+    using namespace mirlsq;
+    detail::batched16_model_checks<Model>();
+    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
+    mir_lsq_batched_extras e;
+    if (!extras || !detail::batched_extras(extras, m, e) || !e.covariance) return -1;
+    if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
+    if (count == 0) return 0;
+    if (m == 0 || batched16_lds_bytes<Model>(m) > kBatchedLdsLimit) return -3;       // the fit's limit: the records come from one
+    hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
+    detail::BasisTable<Model> basis;
+    if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
+    const bool launched = detail::enqueue_covariance16<Model, Kernels>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table,
+                                                                       opt ? opt->variant : 0, e, stream);
+    const hipError_t err = basis.release(stream, launched ? hipGetLastError() : hipErrorLaunchFailure);
     return err == hipSuccess ? 0 : -5;
 }
 

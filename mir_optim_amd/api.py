@@ -31,7 +31,7 @@ __all__ = [
     "mir_box_qp_iwork_length", "GpuOptions", "Stats", "lib", "workloads_lib", "device_count",
     "DeviceBuffer", "Stream", "jtj", "fd_jtj", "DEVICE_CALLBACKS", "TIME_KERNELS", "optimizeLeastSquaresBatched", "batchedPosvx", "BATCHED_NO_LADDER", "BATCHED_DEVICE_BOUNDS",
     "solveBoxQPBatched", "BOX_QP_UNCONSTRAINED_SOLUTION",
-    "MODEL_EXP_DECAY", "MODEL_EXP3_AFFINE", "MODEL_EXP_DECAY_PAD8", "MODEL16_EXP_HARM16", "MODEL16_GAUSS3_AFFINE", "batched16JtJ", "ResultS", "Trace", "TraceRecord", "Spline", "FitSplineResult", "fitSpline",
+    "MODEL_EXP_DECAY", "MODEL_EXP3_AFFINE", "MODEL_EXP_DECAY_PAD8", "MODEL16_EXP_HARM16", "MODEL16_GAUSS3_AFFINE", "batched16JtJ", "optimizeLeastSquaresBatched16", "ResultS", "Trace", "TraceRecord", "Spline", "FitSplineResult", "fitSpline",
     "fit_spline_residuals", "variant_lr_cap",
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
     "VARIANT_SOLVE_BOUNDED", "VARIANT_DEBUG_SOLVE", "VARIANT_HOST_PROFILE", "VARIANT_SOLVE_GENERIC", "VARIANT_SOLVE_ONE_WORKGROUP", "VARIANT_DEBUG_HELPERS_ABSENT", "VARIANT_FD_HOST_COLUMNS",
@@ -333,7 +333,8 @@ def lib():
                 fn.restype = C.c_int
                 fn.argtypes = [C.POINTER(S), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
                                C.c_void_p, C.POINTER(BatchedOptions), C.POINTER(BatchedExtras)]
-        for name in ("mir_optimize_least_squares_batched16_d", "mir_lsq_batched16_kernel_d"):
+        for name in ("mir_optimize_least_squares_batched16_d", "mir_lsq_batched16_kernel_d", "mir_optimize_least_squares_batched16_ex_d",
+                     "mir_lsq_batched16_kernel_ex_d", "mir_lsq_batched16_covariance_d"):
             fn = getattr(L, name)
             fn.restype = C.c_int
             fn.argtypes = [C.POINTER(_Sd), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
@@ -673,7 +674,7 @@ def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None
     degrees of freedom, NaN for a problem with a negative status. Any of the three goes through the _ex entry
     (mir_optimize_least_squares_batched_ex_s / _d); a call without them is the call it always was.
     A MODEL16_* id (9 to 16 parameters) goes to mir_optimize_least_squares_batched16_d: dtype must be float64, and weights,
-    covariance and absolute_sigma raise ValueError (that entry has neither yet)."""
+    covariance and absolute_sigma raise ValueError (optimizeLeastSquaresBatched16 takes them)."""
     if int(model) in _MODELS16:
         return _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weights, covariance, absolute_sigma)
     suf = _batched_suffix(dtype)
@@ -721,7 +722,7 @@ def _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weigh
     if np.dtype(dtype) != np.float64:
         raise ValueError(f"the MODEL16_* models are fitted in float64 only, not {np.dtype(dtype)}: pass dtype=np.float64")
     if weights is not None or covariance or absolute_sigma:
-        raise ValueError("the MODEL16_* models take neither weights nor covariance")
+        raise ValueError("the MODEL16_* models take neither weights nor covariance here: call optimizeLeastSquaresBatched16")
     L = lib()
     x = np.array(x, dtype=np.float64, order="C")
     count, n = x.shape
@@ -740,6 +741,61 @@ def _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weigh
     if rc != 0:
         raise RuntimeError(f"mir_optimize_least_squares_batched16_d failed: {rc}")
     return [LeastSquaresResult(r) for r in raw], x
+
+
+def optimizeLeastSquaresBatched16(model, x, t, data, l=None, u=None, settings=None, variant=0, weights=None, covariance=False,
+                                  absolute_sigma=False):
+    """Many independent fits of a MODEL16_* model (9 to 16 parameters, float64 only), one wavefront per problem, with per-row
+    weights and the covariance of the fitted parameters (mir_optimize_least_squares_batched16_ex_d). x: count x n starts (a copy
+    is updated and returned), t: m (shared) or count x m, data: count x m, m <= 1119. weights: m (shared) or count x m values
+    w_i = 1 / sigma_i; the residual of row i becomes w_i (model - data_i), a weight of 0 removes the row (problems of different
+    lengths are padded to a common m that way). covariance=True: returns (results, x, cov), cov count x n x n =
+    s^2 inv(J^T J) at the returned x with s^2 = residual / (rows with nonzero weight - n), or s^2 = 1 with absolute_sigma=True;
+    +inf for a singular J^T J or no degrees of freedom, NaN for a problem with a negative status. Otherwise returns (results, x).
+    A call with none of the three is the call optimizeLeastSquaresBatched makes for these models."""
+    if int(model) not in _MODELS16:
+        raise ValueError(f"optimizeLeastSquaresBatched16 takes a MODEL16_* id, not {model}")
+    for name, a in (("x", x), ("t", t), ("data", data), ("weights", weights)):
+        dt = getattr(a, "dtype", None)
+        if dt is not None and np.issubdtype(dt, np.floating) and dt != np.float64:
+            raise ValueError(f"the MODEL16_* models are fitted in float64 only: {name} is {dt}")
+    if weights is None and not covariance and not absolute_sigma:
+        return _optimize_batched16(model, x, t, data, l, u, settings, variant, np.float64, None, False, False)
+    L = lib()
+    x = np.array(x, dtype=np.float64, order="C")
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    if x.ndim != 2 or data.ndim != 2 or data.shape[0] != x.shape[0]:
+        raise ValueError(f"x: count x n and data: count x m, not {x.shape} and {data.shape}")
+    count, n = x.shape
+    m = data.shape[1]
+    if t.shape not in ((m,), (count, m)):
+        raise ValueError(f"t: {m} values or {count} x {m}, not {t.shape}")
+    t_stride = 0 if t.ndim == 1 else m
+    lo = np.full(n, -np.inf) if l is None else np.ascontiguousarray(l, dtype=np.float64)
+    up = np.full(n, np.inf) if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    if lo.shape != (n,) or up.shape != (n,):
+        raise ValueError(f"l and u: {n} values each, not {lo.shape} and {up.shape}")
+    if settings is None:
+        settings = LeastSquaresSettings(np.float64)
+    ex = BatchedExtras(flags=BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0)
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.shape not in ((m,), (count, m)):
+            raise ValueError(f"weights: {m} values or {count} x {m}, not {weights.shape}")
+        ex.weights = weights.ctypes.data
+        ex.weight_stride = 0 if weights.ndim == 1 else m
+    cov = np.empty((count, n, n), dtype=np.float64) if covariance else None
+    if covariance:
+        ex.covariance = cov.ctypes.data
+    raw = (_Rd * count)()
+    rc = L.mir_optimize_least_squares_batched16_ex_d(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data,
+                                                     up.ctypes.data, t.ctypes.data, t_stride, data.ctypes.data, raw,
+                                                     C.byref(BatchedOptions(variant=variant)), C.byref(ex))
+    if rc != 0:
+        raise RuntimeError(f"mir_optimize_least_squares_batched16_ex_d failed: {rc}")
+    res = [LeastSquaresResult(r) for r in raw]
+    return (res, x, cov) if covariance else (res, x)
 
 
 def batched16JtJ(J, y):

@@ -23,7 +23,7 @@ WORKLOADS_LIB = os.path.join(LIBDIR, "libmir_optim_amd_workloads.so")
 SOLVER_UNITS = ["abi.hip", "workspace.hip", "solver_loop.hip", "solver_jacobian.hip", "launch_jtj.hip", "launch_broyden.hip",
                 "launch_solve_d.hip", "launch_solve_s.hip", "batched.hip", "batched_d.hip", "comm.hip", "unit_entries.hip", "covariance.hip",
                 "launch_spd_inverse.hip", "launch_boxqp.hip", "launch_boxqp16_s.hip", "launch_boxqp16_d.hip", "batched_bounded.hip",
-                "batched_bounded_d.hip", "batched16_d.hip", "fit_spline.cpp"]
+                "batched_bounded_d.hip", "batched16_d.hip", "batched16_ex_d.hip", "fit_spline.cpp"]
 WORKLOAD_UNITS = ["workloads.hip", "workloads_gemm.hip", "workloads_resident.hip"]
 
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("MIR_OPTIM_AMD_CXXFLAGS", "").split()
@@ -104,7 +104,7 @@ def build_user_model_example(force=False, verbose=False):
     The double model of user_model_f64.hip goes into a library of its own next to it (user_model_f64_lib()), and so does the
     weighted fit with covariance of user_model_weighted.hip (user_model_weighted_lib()) and the fit with binding bounds of
     user_model_bounded.hip (user_model_bounded_lib()), and the 9 and 13 parameter models of user_model_n16.hip
-    (user_model_n16_lib())."""
+    (user_model_n16_lib()) and their weighted fits with covariance of user_model_n16_weighted.hip (user_model_n16_weighted_lib())."""
     root = os.path.dirname(HERE)
     src = os.path.join(root, "tests", "user_model", "user_model.hip")
     out = os.path.join(root, "tests", "user_model", "libuser_model.so")
@@ -128,6 +128,9 @@ def build_user_model_example(force=False, verbose=False):
     deps16 = deps[1:9] + [os.path.join(CSRC, "batched16_kernel.h"), os.path.join(CSRC, "solve_wave16.h")]
     if force or _stale(out16, [src16] + deps16):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out16, src16], verbose)
+    src16w, out16w = user_model_n16_weighted_paths()
+    if force or _stale(out16w, [src16w] + deps16):
+        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out16w, src16w], verbose)
     return out
 
 
@@ -177,3 +180,15 @@ def user_model_n16_lib(force=False, verbose=False):
     """Builds (when stale) and returns the path of tests/user_model/libuser_model_n16.so."""
     build_user_model_example(force=force, verbose=verbose)
     return user_model_n16_paths()[1]
+
+
+def user_model_n16_weighted_paths():
+    """(source, library) of the caller's weighted 9 and 13 parameter fits with covariance (tests/user_model/user_model_n16_weighted.hip)"""
+    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
+    return os.path.join(d, "user_model_n16_weighted.hip"), os.path.join(d, "libuser_model_n16_weighted.so")
+
+
+def user_model_n16_weighted_lib(force=False, verbose=False):
+    """Builds (when stale) and returns the path of tests/user_model/libuser_model_n16_weighted.so."""
+    build_user_model_example(force=force, verbose=verbose)
+    return user_model_n16_weighted_paths()[1]

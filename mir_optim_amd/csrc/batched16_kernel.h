@@ -114,7 +114,13 @@ __device__ __forceinline__ void jtj16_tile(const double* Jl, const double* yv, i
     wave_lds_fence();
 }
 
-template <class Model>
+// WEIGHTED: the rules of k_lm_batched (batched_kernel.h) at this width. The residual of row i is w_i (eval - data_i), ONE
+// multiplication after the subtraction, wherever a residual or a Jacobian row is formed (feval; each finite-difference point
+// before the two are differenced; J_ij = w_i g_j on the analytic path; the Broyden update sees weighted residuals only). The
+// weights are read from global memory next to t and data, in the same clamped loads: the LDS and the m limit are unchanged. A
+// weight of exactly 0 gives a zero residual and a zero Jacobian row. The unweighted instance does not read a.weights and is,
+// instruction for instruction, what it was before the parameter existed.
+template <class Model, bool WEIGHTED = false>
 __global__ __launch_bounds__(64, 1) void k_lm_batched16(BatchedArgs<double> a)
 {
 #pragma clang fp contract(off)
@@ -133,6 +139,8 @@ __global__ __launch_bounds__(64, 1) void k_lm_batched16(BatchedArgs<double> a)
     const T* dp = a.data + (size_t)prob * m;
     const T* bp = NB ? a.basis + (size_t)(a.t_stride ? prob : 0) * a.t_stride * NB : nullptr;
     const LmSettingsDev<T>& S = a.set;
+    const T* wp = nullptr;
+    if constexpr (WEIGHTED) wp = a.weights + (size_t)(a.w_stride ? prob : 0) * a.w_stride;
 
     // component r of x and of the bounds in lane r of every 16-lane group; x replicated in every lane beside it
     T xr = a.x[(size_t)prob * N + (el ? r : 0)];
@@ -152,16 +160,20 @@ __global__ __launch_bounds__(64, 1) void k_lm_batched16(BatchedArgs<double> a)
         constexpr int UNR = NB > 4 ? 2 : 4;
         T ss = 0;
         for (int base = lane; base - lane < m; base += kWave * UNR) {
-            T tv[UNR], dv[UNR], rv[UNR];
+            T tv[UNR], dv[UNR], rv[UNR], wv[WEIGHTED ? UNR : 1];
             BasisRow<NB, T> bv[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int i = min(base + kWave * u, m - 1);
                 tv[u] = tp[i]; dv[u] = dp[i];
+                if constexpr (WEIGHTED) wv[u] = wp[i];
                 bv[u].load(bp, i);
             }
 #pragma unroll
-            for (int u = 0; u < UNR; ++u) rv[u] = Model::eval(tv[u], bv[u].v, p) - dv[u];
+            for (int u = 0; u < UNR; ++u) {
+                rv[u] = Model::eval(tv[u], bv[u].v, p) - dv[u];
+                if constexpr (WEIGHTED) rv[u] = wv[u] * rv[u];
+            }
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int i = base + kWave * u;
@@ -228,6 +240,11 @@ __global__ __launch_bounds__(64, 1) void k_lm_batched16(BatchedArgs<double> a)
 #pragma unroll
                             for (int j = 0; j < W; ++j) gi[j] = 0;
                             Model::grad(tp[i], b.v, x, gi);
+                            if constexpr (WEIGHTED) {
+                                const T wi = wp[i];
+#pragma unroll
+                                for (int j = 0; j < N; ++j) gi[j] = wi * gi[j];
+                            }
 #pragma unroll
                             for (int j = 0; j < N; ++j) Jl[(size_t)i * W + j] = gi[j];
                         }
@@ -253,9 +270,11 @@ __global__ __launch_bounds__(64, 1) void k_lm_batched16(BatchedArgs<double> a)
 #pragma unroll
                         for (int j = 0; j < N; ++j) {
                             p[j] = xph[j];
-                            const T fp = Model::eval(ti, b.v, p) - di;
+                            T fp = Model::eval(ti, b.v, p) - di;
+                            if constexpr (WEIGHTED) fp = wp[i] * fp;          // wp[i]: one load a row. (A local for it, declared outside
                             p[j] = xmh[j];
-                            const T fm = Model::eval(ti, b.v, p) - di;
+                            T fm = Model::eval(ti, b.v, p) - di;
+                            if constexpr (WEIGHTED) fm = wp[i] * fm;          // the branch, reorders two moves of the unweighted instance.)
                             p[j] = x[j];
                             const T v = fp - fm;
                             Jl[(size_t)i * W + j] = inv[j] != 0 ? v * inv[j] : T(0);
@@ -323,6 +342,133 @@ __global__ __launch_bounds__(64, 1) void k_lm_batched16(BatchedArgs<double> a)
     }
     if (lane == 0) a.results[prob] = ret;
     if (lane < N) a.x[(size_t)prob * N + lane] = xr;
+}
+
+// ---- covariance of the fitted parameters in the 16-lane layout, one single-wave workgroup per problem -------------------------
+// The contract of k_batched_covariance (batched_kernel.h): cov = s^2 (J^T J)^-1, s^2 = ||f(x)||^2 / (rows with a nonzero weight
+// - n) or 1 with kBatchedAbsoluteSigma; status and ||f(x)||^2 come from the fit's record. J is rebuilt at the final x into LDS
+// as a refresh of k_lm_batched16 builds it (Model::grad with kBatchedAnalytic, else central differences with jacobianEpsilon
+// clipped to the bounds; weighted rows; row stride 16, padded columns zero), J^T J is the jtj16_tile of the fit, and the inverse
+// is posvx_rows16<N> without a shift on unit right-hand sides: the four 16-lane groups take four columns a call. The columns
+// meet in LDS (where the tile was), and element (i, c) is s^2 (v_ic + v_ci) / 2: symmetric bit for bit. n x n values a problem,
+// row-major. Degenerate cases:
+//     status < 0                                                        every entry NaN
+//     a non-positive pivot in the factorization, or rows - n <= 0        every entry +inf
+// LDS: J, one m-vector of zeros where jtj16_tile reads y, the tile: (16 + 1) m + 272 doubles -- less than the fit's.
+// Control flow is wave-uniform; lanes exchange data through LDS behind wave_lds_fence(), there is no barrier.
+template <class Model>
+__global__ __launch_bounds__(64, 1) void k_batched16_covariance(BatchedCovArgs<double> a)
+{
+#pragma clang fp contract(off)
+    using T = double;
+    static_assert(std::is_same<batched_value_t<Model>, double>::value, "k_batched16_covariance: value_type = double");
+    constexpr int N = Model::n, NB = Model::nb, W = kW16;
+    static_assert(N >= kBatched16NMin && N <= kBatched16NMax, "9 <= n <= 16");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
+    const int lane = threadIdx.x, r = lane & 15, g = lane >> 4, prob = blockIdx.x, m = a.m;
+    const bool el = r < N;
+    T* out = a.cov + (size_t)prob * N * N;
+    if (a.results[prob].status < 0) {
+        for (int idx = lane; idx < N * N; idx += kWave) out[idx] = Lim<T>::inf() - Lim<T>::inf();   // NaN
+        return;
+    }
+    T* Jl = reinterpret_cast<T*>(smem_b);                        // J: m x 16 row-major
+    T* yv = Jl + (size_t)W * m;
+    T* tile = yv + m;
+    const T* tp = a.t + (size_t)(a.t_stride ? prob : 0) * a.t_stride;
+    const T* dp = a.data + (size_t)prob * m;
+    const T* bp = NB ? a.basis + (size_t)(a.t_stride ? prob : 0) * a.t_stride * NB : nullptr;
+    const T* wp = a.weights ? a.weights + (size_t)(a.w_stride ? prob : 0) * a.w_stride : nullptr;
+
+    T xr = a.x[(size_t)prob * N + (el ? r : 0)];
+    T lo_r = a.lower[el ? r : 0], up_r = a.upper[el ? r : 0];
+    xr = el ? xr : T(0);
+    lo_r = el ? lo_r : -Lim<T>::inf();
+    up_r = el ? up_r : Lim<T>::inf();
+    T x[W];
+    static_for<W>([&](auto K) { constexpr int k = decltype(K)::value; x[k] = dpp_row_bcast<k>(xr); });
+
+    constexpr bool HAS_GRAD = batched_has_grad<Model>::value;
+    const bool use_g = HAS_GRAD && (a.variant & kBatchedAnalytic) != 0;
+    T rows = 0;
+    if (use_g) {
+        if constexpr (HAS_GRAD) {
+            for (int i = lane; i < m; i += kWave) {
+                BasisRow<NB, T> b;
+                b.load(bp, i);
+                const T wi = wp ? wp[i] : T(1);
+                rows += wi != 0 ? T(1) : T(0);
+                T gi[W];
+#pragma unroll
+                for (int j = 0; j < W; ++j) gi[j] = 0;
+                Model::grad(tp[i], b.v, x, gi);
+                if (wp) {
+#pragma unroll
+                    for (int j = 0; j < N; ++j) gi[j] = wi * gi[j];
+                }
+#pragma unroll
+                for (int j = 0; j < W; ++j) Jl[(size_t)i * W + j] = j < N ? gi[j] : T(0);
+                yv[i] = T(0);
+            }
+        }
+    } else {
+        const T xmh_r = vmax(xr - a.jacobianEpsilon, lo_r), xph_r = vmin(xr + a.jacobianEpsilon, up_r);
+        const T twh_r = xph_r - xmh_r;
+        const T inv_r = twh_r != 0 ? T(1) / twh_r : T(0);
+        T xph[W], xmh[W], inv[W];
+        static_for<W>([&](auto K) {
+            constexpr int k = decltype(K)::value;
+            xph[k] = dpp_row_bcast<k>(xph_r); xmh[k] = dpp_row_bcast<k>(xmh_r); inv[k] = dpp_row_bcast<k>(inv_r);
+        });
+        for (int i = lane; i < m; i += kWave) {
+            BasisRow<NB, T> b;
+            b.load(bp, i);
+            const T ti = tp[i], di = dp[i], wi = wp ? wp[i] : T(1);
+            rows += wi != 0 ? T(1) : T(0);
+            T p[W];
+#pragma unroll
+            for (int k = 0; k < W; ++k) p[k] = x[k];
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                p[j] = xph[j];
+                T fp = Model::eval(ti, b.v, p) - di;
+                p[j] = xmh[j];
+                T fm = Model::eval(ti, b.v, p) - di;
+                p[j] = x[j];
+                if (wp) { fp = wi * fp; fm = wi * fm; }
+                const T v = fp - fm;
+                Jl[(size_t)i * W + j] = inv[j] != 0 ? v * inv[j] : T(0);
+            }
+#pragma unroll
+            for (int j = N; j < W; ++j) Jl[(size_t)i * W + j] = T(0);
+            yv[i] = T(0);
+        }
+    }
+    const T dof = wave_sum(rows) - T(N);                  // row counts are small integers: exact
+    jtj16_tile(Jl, yv, m, tile);
+    T JJrow[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) JJrow[k] = tile[r * W + k];
+    const T djj = tile[r * W + r];
+    wave_lds_fence();                                     // every lane holds its row: the tile now takes the inverse
+    // column c = 4 q + g of the inverse by group g: the right-hand side is the unit vector e_c (zero for c >= N: not read)
+    int info = 0;
+#pragma nounroll
+    for (int q = 0; q < (N + 3) / 4; ++q) {
+        const int c = 4 * q + g;
+        T v_r;
+        info |= posvx_rows16<N>(JJrow, 0.0, djj, (r == c && el) ? T(1) : T(0), el, r, v_r, N);
+        tile[r * W + c] = v_r;                            // c <= 15
+    }
+    info = __builtin_amdgcn_readfirstlane(info);          // the four groups factor the same matrix
+    wave_lds_fence();
+    const T s2 = (a.flags & kBatchedAbsoluteSigma) ? T(1) : a.results[prob].residual / dof;
+    const bool degenerate = info != 0 || !(dof > 0);
+    for (int idx = lane; idx < N * N; idx += kWave) {
+        const int i = idx / N, c = idx - i * N;
+        const T v = s2 * ((tile[i * W + c] + tile[c * W + i]) / 2);
+        out[idx] = degenerate ? Lim<T>::inf() : v;
+    }
 }
 
 // unit entry of jtj16_tile (mir_lsq_batched16_jtj_d): J count x m x n and y count x m in global memory, one wave per problem;
