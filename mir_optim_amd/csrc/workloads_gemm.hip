@@ -148,6 +148,34 @@ template <int NK> struct TlbCfg {
     static constexpr int FORK_LDS_BYTES = VOTE_OFF + 16;
 };
 
+// The two 16-point groups of compute wave w in the forked kernel (which = 0: the one that forks first). Group g costs
+// 32 - 2 g k-steps per tile, and the waves w, w + 4 share SIMD w % 4; the loader waves 8, 9 sit on SIMDs 0 and 1. The table
+// is chosen by measurement: the SIMDs that also carry a loader get 60 k-steps per tile (30 per wave), the other two 76
+// (38 per wave). Tables with 56, 58, 62 and 64 on the loader SIMDs were each 1 to 3 % slower (DESIGN section 3,
+// profiles/r16): a loader's DMA issue and waits cost its SIMD more than its instruction count says.
+// tlb_fork_vote and tlb_fork_compute both read the table.
+__host__ __device__ constexpr int tlb_fork_group(int w, int which)
+{
+    constexpr int T[8][2] = {{2, 15}, {3, 14}, {0, 13}, {1, 12}, {6, 11}, {7, 10}, {4, 9}, {5, 8}};
+    return T[w][which];
+}
+constexpr bool tlb_fork_groups_ok()
+{
+    int owners[16] = {};
+    for (int w = 0; w < 8; ++w) {
+        if (tlb_fork_group(w, 0) >= tlb_fork_group(w, 1)) return false;        // tlb_fork_compute starts the second group inside the first's loop
+        for (int which = 0; which < 2; ++which) {
+            const int g = tlb_fork_group(w, which);
+            if (g < 0 || g > 15) return false;
+            ++owners[g];
+        }
+    }
+    for (int g = 0; g < 16; ++g)
+        if (owners[g] != 1) return false;
+    return true;
+}
+static_assert(tlb_fork_groups_ok(), "every 16-point group 0..15 belongs to exactly one compute wave");
+
 // loader LOADER's share of the DMA of flat stage f (f % S of this workgroup's stages) into ring slot f % NS; loader 1 also b
 template <int NK, int LOADER>
 __device__ __forceinline__ void tlb_issue(const double* __restrict__ A, const double* __restrict__ b, size_t m,
@@ -563,14 +591,17 @@ __device__ __forceinline__ void tlb_compute_once(const double* __restrict__ X, d
 //      8 g .. 8 g + 7) meets its own coordinates first at k-step 2 g. Before that every column of its MFMAs has the inputs of the
 //      chain of x itself (same A fragment, same B value, same accumulator), and an element of an MFMA result depends only on its
 //      own row, column and accumulator: the group's accumulator after 2 g steps IS the base chain's P_2g, bit for bit. So
-//        * the two loader waves also run the base chain (x in all 16 columns) of one tile each, one stage ahead of the compute
-//          waves, and publish P_2, P_4, ..., P_30 through LDS (16 doubles per prefix and tile: all columns of P_s are equal);
-//        * compute wave w owns the groups w ^ 2 and 15 - w, starts each from its prefix, then runs the group's own k-steps
-//          2 g .. NK - 1 in the order of tlb_compute: 302 instead of 512 MFMAs per tile. Balance: a group costs 32 - 2 g k-steps
-//          per tile, and the loader waves 8, 9 share the SIMDs of waves 0, 4 and 1, 5 (waves w and w + 4 share one). So those
-//          four waves get 30 k-steps per tile ({2, 15}, {3, 14}, {6, 11}, {7, 10}) and the other four 38 ({0, 13}, {1, 12},
-//          {4, 9}, {5, 8}): with a loader's base chain (15 per tile) 75 / 76 per SIMD and tile (groups {w, 15 - w}: 83 / 68);
-//        * a stage of A is DMA'd once for all 256 points; the epilogue is tlb_compute's.
+//        * the two loader waves also run the base chain of one tile each, one stage ahead of the compute waves, and publish
+//          P_2, P_4, ..., P_30 through LDS (16 doubles per prefix and tile). The base chain is A times ONE vector, so it runs
+//          on v_mfma_f64_4x4x4_4b_f64 (four 4-row blocks, x in 4 columns, 16 cycles of the matrix pipe) and not on the
+//          16x16x4 form (x in 16 columns, 64 cycles): the same fused multiply-adds per element, the same bits;
+//        * compute wave w owns the two groups of tlb_fork_group(w, .), starts each from its prefix, then runs the group's own
+//          k-steps 2 g .. NK - 1 in the order of tlb_compute: 272 16x16x4 MFMAs per tile instead of 512, and 30 short ones.
+//          Balance: a group costs 32 - 2 g k-steps per tile, and the loader waves 8, 9 share the SIMDs of waves 0, 4 and
+//          1, 5 (waves w and w + 4 share one). Those four waves get 30 k-steps per tile ({2, 15}, {3, 14}, {6, 11}, {7, 10})
+//          and the other four 38 ({0, 13}, {1, 12}, {4, 9}, {5, 8});
+//        * a stage of A is DMA'd once for all 256 points; the epilogue is tlb_compute's, with the row compares compiled out
+//          of every stage but a workgroup's last and the store addresses carried from stage to stage.
 //      The structure is never assumed: tlb_fork_vote compares, as bit patterns, every X entry a forked chain takes from the base
 //      chain with the base value, and the workgroup runs the dense tlb_compute unless all of them agree.
 //      Barriers: the loaders pass B_f once stage f is in LDS, then DMA stage f + D and run the base chain of f; the compute waves
@@ -588,7 +619,7 @@ __device__ __forceinline__ bool tlb_fork_vote(const double* __restrict__ X, unsi
     __syncthreads();
     if (wave < C::COMPUTE_WAVES) {
         const int fr = lane & 15, fq = lane >> 4;
-        const int s0 = 2 * (wave ^ 2), s1 = 2 * (2 * C::COMPUTE_WAVES - 1 - wave);   // its groups (tlb_fork_compute) fork at s0, s1
+        const int s0 = 2 * tlb_fork_group(wave, 0), s1 = 2 * tlb_fork_group(wave, 1);   // its groups (tlb_fork_compute) fork at s0, s1
         const unsigned long long* xr = reinterpret_cast<const unsigned long long*>(X);
         const unsigned long long* x0 = xr + (size_t)(8 * s0 + fr) * N;         // point 16 g + fr
         const unsigned long long* x1 = xr + (size_t)(8 * s1 + fr) * N;
@@ -612,7 +643,6 @@ __device__ __forceinline__ void tlb_fork_loader(const double* __restrict__ A, co
                                                 const double* __restrict__ X, size_t m, unsigned char* smem, int lane, size_t S)
 {
     using C = TlbCfg<NK>;
-    using Acc = __attribute__((ext_vector_type(4))) double;
     constexpr int N = C::N, P = 2 * N;
     constexpr int OPS = C::IPS / 2 + (LOADER == 1 ? 1 : 0);
     const int fr = lane & 15, fq = lane >> 4;
@@ -634,19 +664,21 @@ __device__ __forceinline__ void tlb_fork_loader(const double* __restrict__ A, co
         __builtin_amdgcn_s_barrier();                       // B_f: stage f is in LDS; stage f - 2 has no readers left
         asm volatile("" ::: "memory");
         if (f + C::D < S) issue(f + C::D);
-        // base chain of tile LOADER of stage f: after k-steps 2 j + 1, lanes of column 0 store P_{2 j + 2}
+        // base chain of tile LOADER of stage f on v_mfma_f64_4x4x4_4b_f64: four blocks of 4 rows x 4 columns, 16 cycles of the
+        // matrix pipe instead of the 64 of the 16x16x4 form, whose 16 columns would all hold x. Lane i + 4 b + 16 k holds A[4 b + i][k]
+        // -- row fr, k = fq: the 16x16x4 A operand, so the same LDS reads -- lane j + 4 b + 16 k holds B[k][j] = x[k], and the
+        // result lane j + 4 b + 16 i holds row 4 b + i. Each element is the same sequence of four fused multiply-adds as in
+        // the 16x16x4 form: every prefix is bitwise equal (scripts/probes/f64_mfma_4x4_probe.hip). After k-steps 2 j + 1 the
+        // lanes of column j = 0 store P_{2 j + 2}: row 4 b + i = D row fq + 4 r with fq = i, r = b.
         const unsigned char* slot = smem + (f % C::NS) * C::STAGE_BYTES;
-        double* pre = reinterpret_cast<double*>(smem + C::PRE_OFF + (f & 1) * C::PRE_STAGE) + LOADER * C::NPRE * 16 + 4 * fq;
-        Acc acc = {0.0, 0.0, 0.0, 0.0};
+        double* pre = reinterpret_cast<double*>(smem + C::PRE_OFF + (f & 1) * C::PRE_STAGE) + LOADER * C::NPRE * 16 + 4 * fq + (fr >> 2);
+        double acc = 0.0;
 #pragma unroll
         for (int j = 0; j < C::NPRE; ++j) {
             const double2 a = *reinterpret_cast<const double2*>(slot + laddr[j & 3] + (j >> 2) * 256);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, xb[2 * j], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, xb[2 * j + 1], acc, 0, 0, 0);
-            if (fr == 0) {
-                *reinterpret_cast<double2*>(pre + 16 * j) = make_double2(acc[0], acc[1]);
-                *reinterpret_cast<double2*>(pre + 16 * j + 2) = make_double2(acc[2], acc[3]);
-            }
+            acc = __builtin_amdgcn_mfma_f64_4x4x4f64(a.x, xb[2 * j], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_4x4x4f64(a.y, xb[2 * j + 1], acc, 0, 0, 0);
+            if ((fr & 3) == 0) pre[16 * j] = acc;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the prefixes are in LDS before the next barrier
     }
@@ -660,7 +692,7 @@ __device__ __forceinline__ void tlb_fork_compute(const double* __restrict__ X, d
     using C = TlbCfg<NK>;
     using Acc = __attribute__((ext_vector_type(4))) double;
     constexpr int N = C::N;
-    constexpr int GA = W ^ 2, GC = 2 * C::COMPUTE_WAVES - 1 - W;   // this wave's two groups (see the balance note above)
+    constexpr int GA = tlb_fork_group(W, 0), GC = tlb_fork_group(W, 1);   // this wave's two groups (see the balance note above)
     constexpr int SA = 2 * GA, SC = 2 * GC;                 // the k-step where each forks off the base chain
     constexpr int GROUP = W < C::COMPUTE_WAVES / 2 ? 0 : 1; // waves w and w + 4 share a SIMD: run them out of phase
     const int fr = lane & 15, fq = lane >> 4;
@@ -674,9 +706,16 @@ __device__ __forceinline__ void tlb_fork_compute(const double* __restrict__ X, d
     for (int s = SA; s < NK; ++s) xa[s - SA] = X[(size_t)pa * N + 8 * (s >> 1) + 2 * fq + (s & 1)];
 #pragma unroll
     for (int s = SC; s < NK; ++s) xc[s - SC] = X[(size_t)pc * N + 8 * (s >> 1) + 2 * fq + (s & 1)];
-    double* const da = D + (pa >> 1);
-    double* const dc = D + (pc >> 1);
     constexpr size_t ldr = N;                               // D is m x n row-major
+    // Where this lane stores: sb is the pending stage's first row, the same for the whole wave (scalar registers), and voff
+    // the lane's own byte offset in it: row 2 fq, group GA's column. Group GC's column is DC doubles further, and the
+    // lane's other rows lie 1, 8, 9, 16, ... rows below: compile-time offsets. sb advances by one stage of the grid after
+    // every epilogue (the epilogues run in stage order), so a stage's sixteen store addresses cost a few 64-bit adds and
+    // immediate offsets, not a shift and a shift-add per store.
+    constexpr int DC = 8 * (GC - GA);
+    const unsigned voff = (unsigned)(((pa >> 1) + 2 * fq * ldr) * 8);
+    unsigned char* sb = reinterpret_cast<unsigned char*>(D + (size_t)blockIdx.x * C::ROWS * ldr);
+    const size_t stage_step = (size_t)gridDim.x * C::ROWS * ldr * 8;
 
     // acc[0], acc[1]: group GA, tiles 0 and 1; acc[2], acc[3]: group GC
     auto mfma_stage = [&](size_t f, Acc (&acc)[4]) {
@@ -711,33 +750,36 @@ __device__ __forceinline__ void tlb_fork_compute(const double* __restrict__ X, d
             }
         });
     };
-    auto epilogue_tile = [&](const Acc& acc, size_t row0, const unsigned char* bslot, double* yp, bool full) {
+    // yb + voff: row ra = 2 fq of the tile in the group's column; the lane's rows are ra, ra + 1, ra + 8, ra + 9
+    auto epilogue_tile = [&](const Acc& acc, unsigned char* yb, size_t ra, const unsigned char* bslot, auto full_tag) {
+        constexpr bool FULL = decltype(full_tag)::value;
         const double2 b0 = *reinterpret_cast<const double2*>(bslot + 16 * fq);
         const double2 b1 = *reinterpret_cast<const double2*>(bslot + 64 + 16 * fq);
         const double y0 = dtanh(acc[0]) - b0.x, y1 = dtanh(acc[1]) - b0.y;
         const double y2 = dtanh(acc[2]) - b1.x, y3 = dtanh(acc[3]) - b1.y;
         const double d0 = y0 - lane_pair_swap(y0), d1 = y1 - lane_pair_swap(y1);         // f(x + h e_j) - f(x - h e_j), LS:1041 + 1045
         const double d2 = y2 - lane_pair_swap(y2), d3 = y3 - lane_pair_swap(y3);
-        const size_t ra = row0 + 2 * fq, rb = row0 + 8 + 2 * fq;
+        double* const yp = reinterpret_cast<double*>(yb + voff);
         if ((fr & 1) == 0) {
-            if (full || ra < m) yp[ra * ldr] = d0;
-            if (full || ra + 1 < m) yp[(ra + 1) * ldr] = d1;
-            if (full || rb < m) yp[rb * ldr] = d2;
-            if (full || rb + 1 < m) yp[(rb + 1) * ldr] = d3;
+            if (FULL || ra < m) yp[0] = d0;
+            if (FULL || ra + 1 < m) yp[ldr] = d1;
+            if (FULL || ra + 8 < m) yp[8 * ldr] = d2;
+            if (FULL || ra + 9 < m) yp[9 * ldr] = d3;
         }
     };
-    auto epilogue = [&](const Acc (&acc)[4], size_t f) {
-        const size_t row0 = (blockIdx.x + f * (size_t)gridDim.x) * C::ROWS;
+    // the pending stage f; FULL: all its 32 rows exist (only the last stage of a workgroup can be partial), no row is compared
+    auto epilogue = [&](const Acc (&acc)[4], size_t f, auto full_tag) {
+        const size_t ra = (blockIdx.x + f * (size_t)gridDim.x) * C::ROWS + 2 * fq;
         const unsigned char* bs = smem + C::B_OFF + (f % C::NSB) * 256;
-        const bool full = f + 1 < S;                        // only the last stage of a workgroup can be partial
-        epilogue_tile(acc[0], row0, bs, da, full);
+        epilogue_tile(acc[0], sb, ra, bs, full_tag);
         __builtin_amdgcn_sched_barrier(0);                  // one tile at a time: bounds the live tanh temporaries
-        epilogue_tile(acc[1], row0 + 16, bs + 128, da, full);
+        epilogue_tile(acc[1], sb + 16 * ldr * 8, ra + 16, bs + 128, full_tag);
         __builtin_amdgcn_sched_barrier(0);
-        epilogue_tile(acc[2], row0, bs, dc, full);
+        epilogue_tile(acc[2], sb + DC * 8, ra, bs, full_tag);
         __builtin_amdgcn_sched_barrier(0);
-        epilogue_tile(acc[3], row0 + 16, bs + 128, dc, full);
+        epilogue_tile(acc[3], sb + (DC + 16 * ldr) * 8, ra + 16, bs + 128, full_tag);
         __builtin_amdgcn_sched_barrier(0);
+        sb += stage_step;
     };
     auto barrier = [] {
         asm volatile("" ::: "memory");
@@ -750,17 +792,18 @@ __device__ __forceinline__ void tlb_fork_compute(const double* __restrict__ X, d
         for (size_t f = 0; f < S; ++f) {
             barrier();                                      // B_{f + 1}: stage f and its prefixes are in LDS
             mfma_stage(f, acc);
-            epilogue(acc, f);
+            if (f + 1 < S) epilogue(acc, f, std::true_type{});
+            else epilogue(acc, f, std::false_type{});
         }
     } else {
         barrier();
         mfma_stage(0, acc);
         for (size_t f = 1; f < S; ++f) {
             barrier();
-            epilogue(acc, f - 1);
+            epilogue(acc, f - 1, std::true_type{});
             mfma_stage(f, acc);
         }
-        epilogue(acc, S - 1);
+        epilogue(acc, S - 1, std::false_type{});
     }
 }
 

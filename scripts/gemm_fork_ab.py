@@ -1,8 +1,9 @@
 """The caller-side difference-panel GEMM at n = 128 (m = 1e6 by default), default entry (prefix forking when X passes the check)
 against the dense entry: on finite-difference X, and on X one ulp off in point 255, which fails the check (the default entry then
-runs the dense GEMM behind the check: the check's cost). With the path of another build's workload library, its default entry
-too. HIP events over 20 launches per case, five rounds with the cases interleaved: median (min .. max) per case; then the bits of
-every panel against the dense entry's on the same X.  usage: gemm_fork_ab.py [m] [path of another build of the workload library]"""
+runs the dense GEMM behind the check: the check's cost). With the paths of other builds of the workload library (the parent's,
+or variants of the group table), the default entry of each too. HIP events over 20 launches per case, five rounds with the cases
+interleaved: median (min .. max) per case; then the bits of every panel against the dense entry's on the same X.
+usage: gemm_fork_ab.py [m] [paths of other builds of the workload library]"""
 import ctypes as C, sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -19,13 +20,13 @@ dX, dXb = api.DeviceBuffer(X), api.DeviceBuffer(Xbad)
 dY = api.DeviceBuffer(nbytes=m * n * 8, dtype=np.float64, shape=(m, n))
 WL = api.workloads_lib()
 # RTLD_DEEPBIND: see gemm_only.py
-other = C.CDLL(sys.argv[2], mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND) if len(sys.argv) > 2 else None
+others = [(path, C.CDLL(path, mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND)) for path in sys.argv[2:]]
 cases = [("default entry, FD X (forked)", WL.wl_tanh_linear_fbd_d, dX, "dense, FD X"),
          ("dense entry, FD X", WL.wl_tanh_linear_fbd_dense_d, dX, None),
          ("default entry, X fails the check", WL.wl_tanh_linear_fbd_d, dXb, "dense, bad X"),
          ("dense entry, same X", WL.wl_tanh_linear_fbd_dense_d, dXb, None)]
-if other is not None:
-    cases.append((f"{os.path.basename(sys.argv[2])} (other build), FD X", other.wl_tanh_linear_fbd_d, dX, "dense, FD X"))
+for path, other in others:
+    cases.append((f"{os.path.basename(path)} (other build), FD X", other.wl_tanh_linear_fbd_d, dX, "dense, FD X"))
 ctx = C.c_void_p(C.addressof(prob.ctx))
 s = torch.cuda.ExternalStream(prob.stream.handle)
 
