@@ -177,7 +177,22 @@ typedef void (*mir_lsq_batched_function_d)(void* context, size_t m, size_t n, si
 typedef void (*mir_lsq_batched_function_s)(void* context, size_t m, size_t n, size_t p, const float* X, float* Y);
 enum {
     MIR_LSQ_DEVICE_CALLBACKS = 1u,   /* f/g/fb receive DEVICE pointers and enqueue on `stream` (no host staging) */
-    MIR_LSQ_TIME_KERNELS = 2u        /* bracket the hot kernels with HIP events and fill `stats` */
+    MIR_LSQ_TIME_KERNELS = 2u,       /* bracket the hot kernels with HIP events and fill `stats` */
+    MIR_LSQ_FD_BASE_POINT = 4u       /* "my fbRowMajorDiff callback also accepts p = 2n + 1": X then holds the 2n finite-difference
+                                        points followed by ONE MORE point (any point: the contract does not say it is their
+                                        base). The callback writes the m x n difference panel of the first 2n points to
+                                        Y[0 .. m n) exactly as for p = 2n, and the residual VECTOR of the last point to
+                                        Y[m n .. m n + m), bit for bit what f writes for that point. With the bit (device
+                                        callbacks, no g, a difference panel in one piece, no MIR_LSQ_VARIANT_FD_SEPARATE_FILL)
+                                        a solve makes its entry residual f(x0) (LS:953) and the first refresh's panel -- same
+                                        x0 -- in one call: a caller whose kernel has each row of its data in hand for the 2n
+                                        points saves a whole sweep over the data per solve. Results, fCalls, statistics and the
+                                        trace are those of the solve without the bit. One difference a callback can observe:
+                                        it is called at the 2n clipped points even when the entry residual already satisfies
+                                        fConverged and the reference would stop at LS:974 -- that panel is discarded and its
+                                        evaluations are not counted (the rule of discarded ladder trials). Without the bit
+                                        p is always 2n. Host callbacks, an analytic Jacobian, the pair-panel and point-major
+                                        paths and panels evaluated in pieces keep the separate f(x0) */
 };
 
 /* `variant` bits of mir_lsq_gpu_options. 0 = the product path. The first six select LITERAL RESTATEMENTS of the reference's
@@ -195,6 +210,8 @@ enum {
     MIR_LSQ_VARIANT_SOLVE_GENERIC = 1u << 10,    /* the any-n solve kernel (solve_big.h) also for n <= 256 */
     MIR_LSQ_VARIANT_SOLVE_ONE_WORKGROUP = 1u << 11, /* n > 256: the any-n solve on ONE workgroup per damping level, without the
                                                     helper workgroups that share its factorisation (solve_coop.h) */
+    MIR_LSQ_VARIANT_NO_FD_BASE_POINT = 1u << 14, /* ignore MIR_LSQ_FD_BASE_POINT: f(x0) by a call of its own, p = 2n always
+                                                    (A/B runs and tests; bit-identical results either way) */
     MIR_LSQ_VARIANT_FD_HOST_COLUMNS = 1u << 13,  /* host-callback finite differences column by column (per-slot staging vectors,
                                                     a strided column write and a stream synchronisation per task, under a
                                                     lock) instead of through the pinned point-major panel */

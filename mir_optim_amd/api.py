@@ -35,7 +35,7 @@ __all__ = [
     "fit_spline_residuals", "variant_lr_cap",
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
     "VARIANT_SOLVE_BOUNDED", "VARIANT_DEBUG_SOLVE", "VARIANT_HOST_PROFILE", "VARIANT_SOLVE_GENERIC", "VARIANT_SOLVE_ONE_WORKGROUP", "VARIANT_DEBUG_HELPERS_ABSENT", "VARIANT_FD_HOST_COLUMNS",
-    "VARIANT_NO_PIPELINE", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA",
+    "VARIANT_NO_PIPELINE", "FD_BASE_POINT", "VARIANT_NO_FD_BASE_POINT", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA",
     "covariance", "spdInverse", "COVARIANCE_ABSOLUTE_SIGMA",
 ]
 
@@ -49,6 +49,7 @@ _MODELS16 = (MODEL16_EXP_HARM16, MODEL16_GAUSS3_AFFINE)
 
 DEVICE_CALLBACKS = 1
 TIME_KERNELS = 2
+FD_BASE_POINT = 4        # MIR_LSQ_FD_BASE_POINT: the fbRowMajorDiff callback also takes p = 2n + 1 (panel + one residual vector)
 
 # MIR_LSQ_VARIANT_* (include/mir_optim_amd.h): literal restatements the tests compare the product path with, and
 # diagnostics; 0 = the product path
@@ -63,6 +64,7 @@ VARIANT_SOLVE_GENERIC = 1 << 10
 VARIANT_SOLVE_ONE_WORKGROUP = 1 << 11
 VARIANT_DEBUG_HELPERS_ABSENT = 1 << 12
 VARIANT_FD_HOST_COLUMNS = 1 << 13
+VARIANT_NO_FD_BASE_POINT = 1 << 14
 VARIANT_NO_PIPELINE = 1 << 22
 
 

@@ -160,6 +160,14 @@ struct Solver {
     FB fbr = nullptr;          // batched residual callback writing Y row-major (m x p): the pair panel of the fused FD kernels
     FB fbd = nullptr;          // batched residual callback writing the m x n row-major DIFFERENCE panel (fbRowMajorDiff)
     int fd_fused = 0;          // 1: the (+h, -h) pair panel, 2: the difference panel of this refresh is in ws->ypanel and J has not been filled yet
+    // MIR_LSQ_FD_BASE_POINT (fd_entry, solver_jacobian.hip): the caller's fbd also takes p = 2n + 1, so the entry residual f(x0)
+    // and the first refresh's difference panel -- same x0 -- come from ONE call. fd_entry_ready: that panel is in ws->ypanel and
+    // the first pass's fd_device() has only its bookkeeping left; a solve that ends before that pass discards it.
+    bool fd_base_point = false;
+    bool fd_entry_ready = false;
+    size_t fd_entry_event = (size_t)-1;   // the timed bracket of that call (MIR_LSQ_TIME_KERNELS), dropped with a discarded panel
+    uint64_t launches_early = 0;      // launched at entry on behalf of the first refresh round (k_fd_points): booked to that round,
+    uint64_t launches_held = 0;       // not to the entry -- held here from the entry's close_round() to the round's
     int sums_pending = 0;      // > 0: the trial sums of this round are still k_lr_sumsq's stage-1 partials (k_decide_chain finishes them)
     uint32_t fd_batch;
     bool device_cb;
@@ -257,9 +265,12 @@ struct Solver {
     void close_round()
     {
         const uint64_t now = launches_now();
+        uint64_t cnt = now - launches_mark;
+        if (round_kind < 0) { cnt -= launches_early; launches_held += launches_early; launches_early = 0; }
+        else { cnt += launches_held; launches_held = 0; }
         if (stats) {
-            stats->library_launches += now - launches_mark;
-            if (round_kind >= 0) { stats->round_launches[round_kind] += now - launches_mark - launches_excluded; stats->rounds[round_kind]++; }
+            stats->library_launches += cnt;
+            if (round_kind >= 0) { stats->round_launches[round_kind] += cnt - launches_excluded; stats->rounds[round_kind]++; }
         }
         launches_mark = now;
         launches_excluded = 0;
@@ -298,6 +309,10 @@ struct Solver {
     JtjUnpack<T> unpack_target() { JtjUnpack<T> u; u.JJ = B.JJ; u.Jy = B.Jy; return u; }
     bool finish_products(bool direct);
     bool jacobian_products(bool broyden, const T* y_dev, const T* yold_dev);
+    bool fd_panel(size_t& pb, bool& use_diff);
+    void fd_widths_host();
+    bool fd_entry(bool& done);
+    void fd_entry_discard();
     bool fd_device();
     static void fd_task_trampoline(mir_least_squares_task task, uint32_t totalThreads, uint32_t threadId, uint32_t j);
     void fd_task(uint32_t totalThreads, uint32_t threadId, uint32_t j);

@@ -125,6 +125,10 @@ __global__ void k_fd_points(const T* __restrict__ x, const T* __restrict__ lower
                             T eps, int n, T* __restrict__ X, T* __restrict__ twh)
 {
     const int j = blockIdx.x;
+    if (j >= n) {                       // block n, launched by the combined entry call only (Solver::fd_entry): x itself as row 2n
+        for (int k = threadIdx.x; k < n; k += blockDim.x) X[(size_t)(2 * n) * n + k] = x[k];
+        return;
+    }
     const T save = x[j];
     T xmh = save - eps, xph = save + eps;
     xmh = dfmax(xmh, lower[j]);

@@ -101,20 +101,28 @@ bool Solver<T>::jacobian_products(bool broyden, const T* y_dev, const T* yold_de
 // ---- finite-difference Jacobian, device callbacks (LS:1016-1050 restructured: all perturbed
 //      points are generated at once, evaluated one by one or in batches, and written to J in
 //      coalesced column panels)
+// the interval widths of k_fd_points with the same arithmetic on the host, to skip collapsed intervals like LS:1033
 template <typename T>
-bool Solver<T>::fd_device()
+void Solver<T>::fd_widths_host()
 {
-    MIRLSQ_LAUNCH(k_fd_points<T>, dim3(n), dim3(64), 0, stream, B.x, B.lower, B.upper, sd.jacobianEpsilon, (int)n, B.X, B.twh);
-    for (uint32_t j = 0; j < n; ++j) {   // same arithmetic on the host, to skip collapsed intervals like LS:1033
+    for (uint32_t j = 0; j < n; ++j) {
         const T save = xh[j];
         T xmh = save - S->jacobianEpsilon, xph = save + S->jacobianEpsilon;
         xmh = std::fmax(xmh, lh[j]);
         xph = std::fmin(xph, uh[j]);
         twh_h[j] = xph - xmh;
     }
+}
+
+// The panel of a device-callback refresh, decided in ONE place for fd_device() and fd_entry(): pb, the columns per callback
+// call; use_diff, whether the caller's difference-panel callback serves the refresh in one piece; and the allocation behind
+// ws->ypanel (with MIR_LSQ_FD_BASE_POINT the difference panel has an m-vector behind it).
+template <typename T>
+bool Solver<T>::fd_panel(size_t& pb, bool& use_diff)
+{
     // panel width bounded by the scratch the device can spare: half of the free HBM, at most 64 GiB (288 GB per GPU: the
     // whole 2n-point panel of cfg 4's 8e6 x 256 problem, 33 GB, stays in one piece), at least 1 GiB
-    size_t pb = n;
+    pb = n;
     size_t cap = (size_t)64 << 30;
     if (ws->ypanel_bytes < 2 * pb * m * sizeof(T)) {              // the whole panel is not there yet: ask the device
         size_t free_b = 0, total_b = 0;
@@ -131,14 +139,73 @@ bool Solver<T>::fd_device()
     if (pb < 1) pb = 1;
     if (fb && fd_batch && fd_batch / 2 < pb) pb = fd_batch / 2 ? fd_batch / 2 : 1;
     const bool no_fuse = (variant & MIR_LSQ_VARIANT_FD_SEPARATE_FILL) != 0;
-    const bool use_diff = fbd && plan.fd_diff.kernel != JtjKernel::none && pb == n && !no_fuse;   // m x n difference panel
-    const size_t need = (use_diff ? 1 : 2) * pb * m * sizeof(T);
+    use_diff = fbd && plan.fd_diff.kernel != JtjKernel::none && pb == n && !no_fuse;   // m x n difference panel
+    const size_t need = use_diff ? (pb * m + (fd_base_point ? m : 0)) * sizeof(T) : 2 * pb * m * sizeof(T);
     if (ws->ypanel_bytes < need) {
         if (ws->ypanel) (void)hipFree(ws->ypanel);
         ws->ypanel = nullptr; ws->ypanel_bytes = 0;
         if (!ok(hipMalloc(&ws->ypanel, need), "hipMalloc(FD panel)")) return false;
         ws->ypanel_bytes = need;
     }
+    return true;
+}
+
+// ---- the entry of a solve whose difference-panel callback also takes p = 2n + 1 (MIR_LSQ_FD_BASE_POINT): f(x0), LS:953, and the
+//      difference panel of the first refresh, LS:1016-1050 at the same x0 (needJacobian and age == maxAge at entry), in ONE
+//      call -- the caller's kernel has every row of its data in hand for the 2n points anyway. Central differences do not use
+//      f(x0), so nothing is reordered: y is copied out of the panel's tail (not aliased: the y / mB / fr rotation would walk into
+//      the panel) and the first pass's fd_device() finds the panel ready. done = false: the conditions do not hold (no flag, an
+//      analytic g, no difference panel in one piece, FD_SEPARATE_FILL) and the caller evaluates f(x0) on its own, as ever.
+template <typename T>
+bool Solver<T>::fd_entry(bool& done)
+{
+    done = false;
+    if (!fd_base_point || !device_cb || g || !fbd) return true;
+    size_t pb;
+    bool use_diff;
+    if (!fd_panel(pb, use_diff)) return false;
+    if (!use_diff) return true;
+    // block n of the grid copies x0 into row 2n of B.X; the launch belongs to the first refresh round (close_round())
+    MIRLSQ_LAUNCH(k_fd_points<T>, dim3(n + 1), dim3(64), 0, stream, B.x, B.lower, B.upper, sd.jacobianEpsilon, (int)n, B.X, B.twh);
+    launches_early = 1;
+    T* Y = static_cast<T*>(ws->ypanel);
+    ev_begin(4);
+    fd_entry_event = time_kernels ? events.size() - 1 : (size_t)-1;
+    fbd(fbctx, m, n, 2 * (size_t)n + 1, B.X, Y);
+    ev_end();
+    if (!ok(hipMemcpyAsync(y, Y + m * (size_t)n, m * sizeof(T), hipMemcpyDeviceToDevice, stream), "D2D entry residual")) return false;
+    fd_entry_ready = true;
+    done = true;
+    return ok(hipGetLastError(), "fd entry callback");
+}
+// the solve ended before its first refresh (the entry residual converged, LS:974): the panel's 2n evaluations are not counted,
+// like ladder trials that are evaluated and then discarded
+template <typename T>
+void Solver<T>::fd_entry_discard()
+{
+    fd_entry_ready = false;
+    launches_early = launches_held = 0;
+    if (fd_entry_event < events.size()) events[fd_entry_event].kind = -1;
+}
+
+template <typename T>
+bool Solver<T>::fd_device()
+{
+    if (fd_entry_ready) {
+        // fd_entry() made this refresh's call (same x: nothing has moved since): what is left is the bookkeeping of the branch below
+        fd_entry_ready = false;
+        fd_widths_host();
+        if (stats) { stats->fd_callback_points += 2 * (uint64_t)n; stats->fd_callback_calls++; }
+        fd_fused = 2;
+        ret.fCalls += n;
+        return true;
+    }
+    MIRLSQ_LAUNCH(k_fd_points<T>, dim3(n), dim3(64), 0, stream, B.x, B.lower, B.upper, sd.jacobianEpsilon, (int)n, B.X, B.twh);
+    fd_widths_host();
+    size_t pb;
+    bool use_diff;
+    if (!fd_panel(pb, use_diff)) return false;
+    const bool no_fuse = (variant & MIR_LSQ_VARIANT_FD_SEPARATE_FILL) != 0;
     T* Y = static_cast<T*>(ws->ypanel);
     if (use_diff) {
         // all 2n points in one sweep, the caller's kernel hands over D[i][j] = f(x + h e_j)_i - f(x - h e_j)_i (LS:1041, 1045);
@@ -372,6 +439,10 @@ bool Solver<T>::analytic_jacobian()
     template bool Solver<T>::plain_products(const T*);                                              \
     template bool Solver<T>::finish_products(bool);                                                 \
     template bool Solver<T>::jacobian_products(bool, const T*, const T*);                           \
+    template void Solver<T>::fd_widths_host();                                                      \
+    template bool Solver<T>::fd_panel(size_t&, bool&);                                              \
+    template bool Solver<T>::fd_entry(bool&);                                                       \
+    template void Solver<T>::fd_entry_discard();                                                    \
     template bool Solver<T>::fd_device();                                                           \
     template void Solver<T>::fd_task_trampoline(mir_least_squares_task, uint32_t, uint32_t, uint32_t); \
     template void Solver<T>::fd_task(uint32_t, uint32_t, uint32_t);                                 \

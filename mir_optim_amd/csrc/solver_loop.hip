@@ -449,7 +449,9 @@ typename Solver<T>::Result Solver<T>::run()
 
     bool fail = false;
     do {   // single-exit block for device errors
-        if (!eval_f(B.x, xh, y)) { fail = true; break; }                 // LS:953
+        bool entry_done = false;                                         // f(x0) came with the first refresh's panel (fd_entry)
+        if (!fd_entry(entry_done)) { fail = true; break; }
+        if (!entry_done && !eval_f(B.x, xh, y)) { fail = true; break; }  // LS:953
         ++ret.fCalls;
         ++seq;
         if (!sumsq(y, 0)) { fail = true; break; }                        // LS:955
@@ -658,6 +660,7 @@ typename Solver<T>::Result Solver<T>::run()
         }
     } while (ret.iterations < S->maxIterations);                         // LS:1175
 
+    if (fd_entry_ready) fd_entry_discard();                              // ended before the first refresh
     close_round();
     if (fail) ret.status = mir_ls_numericError;
     if (stats) stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
@@ -702,6 +705,7 @@ void Solver<T>::apply_options(const mir_lsq_gpu_options* opt)
         s.fbr = reinterpret_cast<typename Abi<T>::FB>(opt->fbRowMajor);
     if (opt->struct_size >= offsetof(mir_lsq_gpu_options, fbRowMajorDiff) + sizeof(void*) && s.device_cb)
         s.fbd = reinterpret_cast<typename Abi<T>::FB>(opt->fbRowMajorDiff);
+    s.fd_base_point = s.fbd && (opt->flags & MIR_LSQ_FD_BASE_POINT) != 0 && !(opt->variant & MIR_LSQ_VARIANT_NO_FD_BASE_POINT);
 }
 
 template <typename T>

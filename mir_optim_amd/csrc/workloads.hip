@@ -76,9 +76,7 @@ __global__ __launch_bounds__(256) void k_tanh_linear(const T* __restrict__ A, co
         constexpr int buf = decltype(B)::value;
         const size_t row = 4 * g + q;
         const bool rok = row < m;
-        T s = 0;
-#pragma unroll
-        for (int c = 0; c < NCP; ++c) s += v0[buf][c] * x0[c] + v1[buf][c] * x1[c];
+        T s = tanh_linear_row_sum<T, NCP>(v0[buf], v1[buf], x0, x1);
         s = sum16(s);
         const T t = dtanh(s);
         if constexpr (MODE == 0) {
@@ -367,17 +365,24 @@ void wl_tanh_linear_fbr_d(void* vctx, size_t m, size_t n, size_t p, const double
 }
 // the same p = 2n points [x + h e_0, x - h e_0, ...] with the m x n row-major DIFFERENCE panel written
 // (mir_lsq_gpu_options.fbRowMajorDiff): D[i n + j] = f(X_2j)_i - f(X_2j+1)_i
+// p = 2n + 1 (MIR_LSQ_FD_BASE_POINT): one more point behind the 2n, its residual VECTOR behind the panel at D[m n .. m n + m) --
+// at n = 128 from the stage of A the GEMM already holds in LDS, elsewhere by the one-point sweep; the same bits either way
+static void tanh_linear_fbd(wl_tanh_linear_ctx* c, size_t m, size_t n, size_t p, const double* X, double* D, bool dense)
+{
+    const double *A = (const double*)c->A, *b = (const double*)c->b;
+    const bool base = p == 2 * n + 1;
+    const bool folded = launch_tanh_linear_batched_diff(A, b, X, D, m, (int)n, (int)(base ? 2 * n : p), (hipStream_t)c->stream,
+                                                        c->read_a_once, dense, base);
+    if (base && !folded) launch_tanh_linear<double, 0>(A, b, X + 2 * n * n, D + m * n, m, (int)n, (hipStream_t)c->stream);
+}
 void wl_tanh_linear_fbd_d(void* vctx, size_t m, size_t n, size_t p, const double* X, double* D)
 {
-    auto* c = static_cast<wl_tanh_linear_ctx*>(vctx);
-    launch_tanh_linear_batched_diff((const double*)c->A, (const double*)c->b, X, D, m, (int)n, (int)p, (hipStream_t)c->stream, c->read_a_once);
+    tanh_linear_fbd(static_cast<wl_tanh_linear_ctx*>(vctx), m, n, p, X, D, false);
 }
 // the same panel with every product of the GEMM computed (n = 128: no forking off the base point's chain): for A/B runs and tests
 void wl_tanh_linear_fbd_dense_d(void* vctx, size_t m, size_t n, size_t p, const double* X, double* D)
 {
-    auto* c = static_cast<wl_tanh_linear_ctx*>(vctx);
-    launch_tanh_linear_batched_diff((const double*)c->A, (const double*)c->b, X, D, m, (int)n, (int)p, (hipStream_t)c->stream, c->read_a_once,
-                                    true);
+    tanh_linear_fbd(static_cast<wl_tanh_linear_ctx*>(vctx), m, n, p, X, D, true);
 }
 void wl_tanh_linear_f_s(void* vctx, size_t m, size_t n, const float* x, float* y)
 {

@@ -80,6 +80,27 @@ __device__ inline double dtanh(double x)
     return copysign(fma(-2.0, q, 1.0), x);
 }
 __device__ inline float dtanh(float v) { return tanhf(v); }
+
+// The row sum of the tanh-linear residual as the one-point sweep forms it (k_tanh_linear, workloads.hip): 16 lanes per row, lane p
+// holds the column pairs (32 c + 2 p, 32 c + 2 p + 1), c < NCP; this is the lane's share, sum16() then adds the 16 lanes.
+// ONE definition with the operations written out -- per pair one multiply and one fused multiply-add, t = fma(v0, x0, v1 x1), then
+// s = (0 + t_0) + t_1 + ... in c order: the sequence the compiler's contraction used to pick for `s += v0 x0 + v1 x1` in every
+// instance of that kernel. The difference-panel GEMM evaluates the extra point of fbRowMajorDiff (p = 2n + 1) with it from its
+// LDS image of A, and that residual has to be the sweep's bit for bit; left to contraction, two call sites may round differently.
+// (s: the sum over the pairs before these, for a caller that takes the row in pieces.)
+template <typename T, int NCP>
+__device__ __forceinline__ T tanh_linear_row_sum(const T (&v0)[NCP], const T (&v1)[NCP], const T (&x0)[NCP], const T (&x1)[NCP],
+                                                 T s = T(0))
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < NCP; ++c) {
+        const T hi = v1[c] * x1[c];
+        const T t = fma(v0[c], x0[c], hi);
+        s = s + t;
+    }
+    return s;
+}
 __device__ inline double dexp(double v) { return exp(v); }
 __device__ inline float dexp(float v) { return expf(v); }
 

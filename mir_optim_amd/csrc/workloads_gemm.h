@@ -9,5 +9,7 @@ bool launch_tanh_linear_batched(const double* A, const double* b, const double* 
 void launch_tanh_linear_batched_rm(const double* A, const double* b, const double* X, double* Y, size_t m, int n, int P, hipStream_t s);
 // P = 2n finite-difference points: the m x n row-major DIFFERENCE panel D[i n + j] = f(X_2j)_i - f(X_2j+1)_i
 // (dense: every product of the GEMM is computed -- no forking off the base point's chain at n = 128; the same bits)
-void launch_tanh_linear_batched_diff(const double* A, const double* b, const double* X, double* D, size_t m, int n, int P, hipStream_t s,
-                                     int read_a_once, bool dense = false);
+// base: X holds one more point behind the P (row P) whose residual vector belongs at D[m n .. m n + m). True when the launch
+// has written it too (n = 128: from the stage of A in LDS, with the one-point sweep's arithmetic); false: the caller still has to
+bool launch_tanh_linear_batched_diff(const double* A, const double* b, const double* X, double* D, size_t m, int n, int P, hipStream_t s,
+                                     int read_a_once, bool dense = false, bool base = false);

@@ -146,7 +146,61 @@ template <int NK> struct TlbCfg {
     static constexpr int PRE_OFF = LDS_BYTES;
     static constexpr int VOTE_OFF = PRE_OFF + 2 * PRE_STAGE;
     static constexpr int FORK_LDS_BYTES = VOTE_OFF + 16;
+    // the extra point of fbRowMajorDiff with p = 2n + 1 (BASE instances, n = 128): its n coordinates behind the vote word
+    static constexpr int BASE_OFF = FORK_LDS_BYTES;
+    static constexpr int BASE_LDS_BYTES = BASE_OFF + N * 8;
 };
+
+// ---- the extra point of a p = 2n + 1 call (n = 128): its residual for the 32 rows of the stage in `slot`, in eight shares of
+//      four LDS rows (`wave` names the share; tlb_fork_compute says which wave takes which), each one wave's work,
+//      with the arithmetic of the one-point sweep k_tanh_linear<double, 4, 0, true> -- 16 lanes per row,
+//      lane p the column pairs 32 c + 2 p, + 1 (piece 16 c + p of the row, at position 16 c + (p ^ sigma) of its LDS image),
+//      tanh_linear_row_sum, sum16, dtanh, - b: bit for bit what that kernel writes. (The base chain of the loader waves sums the
+//      same products in the MFMA's order; it cannot serve.) LDS row R holds memory row (R & 16) + rho(R & 15) of the stage.
+// the lane number, formed where it is asked for (volatile: not hoisted, not merged with the kernel's own copy)
+__device__ __forceinline__ int tlb_lane_now()
+{
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+template <int NK>
+__device__ __forceinline__ void tlb_base_rows(const unsigned char* slot, const unsigned char* bslot, const unsigned char* smem,
+                                              double* __restrict__ ybase, size_t row0, size_t m, int wave)
+{
+    using C = TlbCfg<NK>;
+    static_assert(C::N == 128 && C::ROWS == 32 && C::COMPUTE_WAVES == 8, "four rows a wave, four column pairs a lane");
+    // The forked kernel runs at its register limit (168): everything here that depends on the lane is formed again per stage from
+    // a lane number the optimiser cannot see through -- a dozen integer operations -- instead of living in registers across the
+    // MFMA chains and the epilogues (hoisted, the addresses below and three of dtanh's constants went to scratch memory, whose
+    // reloads wait behind the epilogue's stores); the row bound and the store's base are wave-uniform.
+    const int lane = tlb_lane_now();
+    const int q = lane >> 4, p = lane & 15;
+    const int R = 4 * wave + q;
+    const unsigned char* rp = slot + R * C::N * 8 + (p ^ tlb_sigma(R & 15)) * 16;
+    const unsigned char* xp = smem + C::BASE_OFF + p * 16;
+    // two column pairs at a time (the same sum, c ascending): 16 registers of operands in flight instead of 32
+    double s = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        double v0[2], v1[2], x0[2], x1[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const double2 a = *reinterpret_cast<const double2*>(rp + (2 * h + c) * 256);
+            const double2 x = *reinterpret_cast<const double2*>(xp + (2 * h + c) * 256);
+            v0[c] = a.x; v1[c] = a.y;
+            x0[c] = x.x; x1[c] = x.y;
+        }
+        s = tanh_linear_row_sum<double, 2>(v0, v1, x0, x1, s);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    s = sum16(s);
+    const double t = dtanh(s);
+    const int lr = (R & 16) + tlb_rho(R & 15);
+    const double bv = *reinterpret_cast<const double*>(bslot + lr * 8);
+    const int rows = m - row0 < (size_t)C::ROWS ? (int)(m - row0) : C::ROWS;      // rows of the stage that exist (row0 < m)
+    if (p == 0 && lr < rows) (ybase + row0)[lr] = t - bv;
+}
 
 // The two 16-point groups of compute wave w in the forked kernel (which = 0: the one that forks first). Group g costs
 // 32 - 2 g k-steps per tile, and the waves w, w + 4 share SIMD w % 4; the loader waves 8, 9 sit on SIMDs 0 and 1. The table
@@ -685,7 +739,7 @@ __device__ __forceinline__ void tlb_fork_loader(const double* __restrict__ A, co
     __builtin_amdgcn_s_barrier();                           // B_S: the prefixes of the last stage
 }
 
-template <int NK, int W>
+template <int NK, int W, bool BASE = false>
 __device__ __forceinline__ void tlb_fork_compute(const double* __restrict__ X, double* __restrict__ D, size_t m,
                                                  unsigned char* smem, int lane, size_t S)
 {
@@ -786,28 +840,77 @@ __device__ __forceinline__ void tlb_fork_compute(const double* __restrict__ X, d
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
+    // BASE: the extra point of a p = 2n + 1 call, four rows of stage f per share (the stage's slot is held until B_{f + 2}).
+    // Waves 2 and 3 -- 38 k-steps per tile and the epilogue straight behind the chains: 168 registers without this -- take none:
+    // with a share they kept a dozen values in scratch memory, reloaded every stage behind the epilogue's stores. Their shares
+    // go to waves 6 and 7, which sit on the same two SIMDs, so every SIMD still carries eight rows per stage.
+    constexpr int BASE_SHARES = !BASE || W == 2 || W == 3 ? 0 : W >= 6 ? 2 : 1;
+    [[maybe_unused]] auto base_rows = [&](size_t f) {
+        wl_static_for<BASE_SHARES>([&](auto hh) {
+            tlb_base_rows<NK>(smem + (f % C::NS) * C::STAGE_BYTES, smem + C::B_OFF + (f % C::NSB) * 256, smem, D + m * ldr,
+                              (blockIdx.x + f * (size_t)gridDim.x) * C::ROWS, m, W - 4 * decltype(hh)::value);
+            __builtin_amdgcn_sched_barrier(0);              // between two stages' accumulators, mixed with neither: no registers to spare
+        });
+    };
     Acc acc[4];
     barrier();                                              // B_0
     if constexpr (GROUP == 0) {
         for (size_t f = 0; f < S; ++f) {
             barrier();                                      // B_{f + 1}: stage f and its prefixes are in LDS
+            base_rows(f);
             mfma_stage(f, acc);
             if (f + 1 < S) epilogue(acc, f, std::true_type{});
             else epilogue(acc, f, std::false_type{});
         }
     } else {
         barrier();
+        base_rows(0);
         mfma_stage(0, acc);
         for (size_t f = 1; f < S; ++f) {
             barrier();
             epilogue(acc, f - 1, std::true_type{});
+            base_rows(f);
             mfma_stage(f, acc);
         }
         epilogue(acc, S - 1, std::false_type{});
     }
 }
 
-template <int NK, bool RM = false, bool DIFF = false>
+// The same point when X fails tlb_fork_vote and the workgroup has run the chunked sweep (tests and foreign X only: the sweep's
+// compute waves have neither vector nor scalar registers to spare for tlb_base_rows): behind the sweep, every wave takes its
+// share of the workgroup's stages once more from memory -- the one-point kernel's loads, lanes and arithmetic.
+template <int NK>
+__device__ __forceinline__ void tlb_base_sweep(const double* __restrict__ A, const double* __restrict__ b, const double* __restrict__ x,
+                                               double* __restrict__ ybase, size_t m, int wave, size_t S)
+{
+    using C = TlbCfg<NK>;
+    static_assert(C::N == 128, "four column pairs a lane");
+    const int lane = tlb_lane_now();                        // (nothing of this is alive during the sweeps before it)
+    const int q = lane >> 4, p = lane & 15;
+    double x0[4], x1[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double2 t = *reinterpret_cast<const double2*>(x + 32 * c + 2 * p);
+        x0[c] = t.x; x1[c] = t.y;
+    }
+    for (size_t k = wave; k < S; k += C::THREADS / 64) {
+        const size_t row0 = (blockIdx.x + k * (size_t)gridDim.x) * C::ROWS;
+        for (int g = 0; g < C::ROWS / 4; ++g) {
+            const size_t row = row0 + 4 * g + q, rc = row < m ? row : m - 1;
+            double v0[4], v1[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const double2 t = *reinterpret_cast<const double2*>(A + rc * C::N + 32 * c + 2 * p);
+                v0[c] = t.x; v1[c] = t.y;
+            }
+            const double s = sum16(tanh_linear_row_sum<double, 4>(v0, v1, x0, x1));
+            const double t = dtanh(s);
+            if (p == 0 && row < m) ybase[row] = t - b[rc];
+        }
+    }
+}
+
+template <int NK, bool RM = false, bool DIFF = false, bool BASE = false>
 __global__ __launch_bounds__(TlbCfg<NK>::THREADS) void k_tanh_linear_batched_dma(const double* __restrict__ A,
                                                                                   const double* __restrict__ b,
                                                                                   const double* __restrict__ X,
@@ -829,12 +932,17 @@ __global__ __launch_bounds__(TlbCfg<NK>::THREADS) void k_tanh_linear_batched_dma
     const bool once = DIFF && mode == 1 && NK <= 32 && P == 2 * C::N;
     const size_t F = once ? S : S * (size_t)nchunks;            // flat (chunk, stage) sequence: the ring never drains
     if (S == 0) return;
+    if constexpr (BASE) {                                   // (launched with P = 2n and mode 0 or 2 only) the extra point: row P of X
+        static_assert(DIFF && C::FORK, "the extra point rides on the n = 128 difference panel");
+        if (threadIdx.x < C::N) reinterpret_cast<double*>(tlb_smem + C::BASE_OFF)[threadIdx.x] = X[(size_t)P * C::N + threadIdx.x];
+        __syncthreads();
+    }
     if constexpr (DIFF && C::FORK) {
         if (mode == 2 && P == 2 * C::N && tlb_fork_vote<NK>(X, tlb_smem, lane, wave)) {       // (workgroup-uniform)
             if (wave == C::COMPUTE_WAVES) tlb_fork_loader<NK, 0>(A, b, X, m, tlb_smem, lane, S);
             else if (wave == C::COMPUTE_WAVES + 1) tlb_fork_loader<NK, 1>(A, b, X, m, tlb_smem, lane, S);
             else wl_static_for<C::COMPUTE_WAVES>([&](auto ww) {
-                if (wave == decltype(ww)::value) tlb_fork_compute<NK, decltype(ww)::value>(X, Y, m, tlb_smem, lane, S);
+                if (wave == decltype(ww)::value) tlb_fork_compute<NK, decltype(ww)::value, BASE>(X, Y, m, tlb_smem, lane, S);
             });
             return;
         }
@@ -861,21 +969,22 @@ __global__ __launch_bounds__(TlbCfg<NK>::THREADS) void k_tanh_linear_batched_dma
             }
         }
     }
+    if constexpr (BASE) tlb_base_sweep<NK>(A, b, X + (size_t)P * C::N, Y + m * (size_t)C::N, m, wave, S);
 }
 
-template <int NK, bool RM = false, bool DIFF = false>
+template <int NK, bool RM = false, bool DIFF = false, bool BASE = false>
 bool launch_tlb_dma(const double* A, const double* b, const double* X, double* Y, size_t m, int P, hipStream_t s, int mode = 0)
 {
     using C = TlbCfg<NK>;
-    constexpr int lds = DIFF && C::FORK ? C::FORK_LDS_BYTES : C::LDS_BYTES;
+    constexpr int lds = BASE ? C::BASE_LDS_BYTES : DIFF && C::FORK ? C::FORK_LDS_BYTES : C::LDS_BYTES;
     static bool attr_ok = [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_tanh_linear_batched_dma<NK, RM, DIFF>),
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_tanh_linear_batched_dma<NK, RM, DIFF, BASE>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
     }();
     if (!attr_ok) return false;
     const size_t Stot = (m + C::ROWS - 1) / C::ROWS;
     const unsigned grid = (unsigned)(Stot < 256 ? Stot : 256);
-    hipLaunchKernelGGL((k_tanh_linear_batched_dma<NK, RM, DIFF>), dim3(grid), dim3(C::THREADS), lds, s, A, b, X, Y, m, P, mode);
+    hipLaunchKernelGGL((k_tanh_linear_batched_dma<NK, RM, DIFF, BASE>), dim3(grid), dim3(C::THREADS), lds, s, A, b, X, Y, m, P, mode);
     return true;
 }
 
@@ -1004,24 +1113,27 @@ __global__ __launch_bounds__(256) void k_tanh_linear_batched_wide(const double* 
 
 }  // namespace
 
-void launch_tanh_linear_batched_diff(const double* A, const double* b, const double* X, double* D, size_t m, int n, int P,
-                                     hipStream_t s, int read_a_once, bool dense)
+bool launch_tanh_linear_batched_diff(const double* A, const double* b, const double* X, double* D, size_t m, int n, int P,
+                                     hipStream_t s, int read_a_once, bool dense, bool base)
 {
     if (m >= 32 && P % 16 == 0) {                          // whole 16-point MFMA tiles: no clamped lanes, whose pairs would store zeros
         const int mode = read_a_once ? 1 : dense ? 0 : 2;
-        if (n == 256 && launch_tlb_dma<64, true, true>(A, b, X, D, m, P, s, mode)) return;
-        if (n == 128 && launch_tlb_dma<32, true, true>(A, b, X, D, m, P, s, mode)) return;
-        if (n == 64 && launch_tlb_dma<16, true, true>(A, b, X, D, m, P, s, mode)) return;
-        if (n == 32 && launch_tlb_dma<8, true, true>(A, b, X, D, m, P, s, mode)) return;
+        // the extra point of a p = 2n + 1 call rides on the n = 128 kernel (forked or dense; not on the read-A-once experiment)
+        if (base && n == 128 && P == 2 * n && mode != 1 && launch_tlb_dma<32, true, true, true>(A, b, X, D, m, P, s, mode)) return true;
+        if (n == 256 && launch_tlb_dma<64, true, true>(A, b, X, D, m, P, s, mode)) return false;
+        if (n == 128 && launch_tlb_dma<32, true, true>(A, b, X, D, m, P, s, mode)) return false;
+        if (n == 64 && launch_tlb_dma<16, true, true>(A, b, X, D, m, P, s, mode)) return false;
+        if (n == 32 && launch_tlb_dma<8, true, true>(A, b, X, D, m, P, s, mode)) return false;
     }
     if (n > 256 && n % 8 == 0 && P % 2 == 0 && m > 0) {
         const size_t nt = (m + 63) / 64;
         hipLaunchKernelGGL(k_tanh_linear_batched_wide<1>, dim3((unsigned)(nt < 256 * 8 ? nt : 256 * 8)), dim3(256), 0, s, A, b, X, D, m, n, P);
-        return;
+        return false;
     }
     size_t blocks = (m * (size_t)(P / 2) + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(k_tanh_linear_batched_diff_generic, dim3((unsigned)(blocks ? blocks : 1)), dim3(256), 0, s, A, b, X, D, m, n, P);
+    return false;
 }
 
 void launch_tanh_linear_batched_rm(const double* A, const double* b, const double* X, double* Y, size_t m, int n, int P,

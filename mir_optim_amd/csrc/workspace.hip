@@ -39,7 +39,7 @@ Buffers<T> carve(void* base, size_t m, size_t n, int num_cu)
     b.y = (T*)take(m, sizeof(T));
     b.mB = (T*)take(m, sizeof(T));
     b.ytmp = (T*)take(m, sizeof(T));
-    b.X = (T*)take(2 * n * n, sizeof(T));
+    b.X = (T*)take((2 * n + 1) * n, sizeof(T));      // the 2n finite-difference points + the point itself (Solver::fd_entry)
     b.twh = (T*)take(n, sizeof(T));
     b.x = (T*)take(n, sizeof(T));
     b.lower = (T*)take(n, sizeof(T));

@@ -42,6 +42,7 @@ class DeviceProblem:
     """Common part: stream, context, callback addresses, GpuOptions."""
 
     suffix = "d"
+    fbd_base_point = False       # the class's fbd callback also takes p = 2n + 1 (api.FD_BASE_POINT)
 
     def options(self, flags=0, stats=None, comm=None, workspace=None, batched=False, fd_batch=0, trace=None, variant=0):
         o = api.GpuOptions()
@@ -58,6 +59,8 @@ class DeviceProblem:
                 o.fbRowMajor = self.fbr          # row-major FD panel: the fill is fused into the J^T J kernel
             if getattr(self, "fbd", None) is not None and batched not in ("pointmajor", "rowmajor"):
                 o.fbRowMajorDiff = self.fbd      # m x n difference panel: half the bytes between the two kernels
+                if self.fbd_base_point:
+                    o.flags |= api.FD_BASE_POINT     # f(x0) rides on the first refresh's call
         if stats is not None:
             o.stats = C.pointer(stats)
         if trace is not None:
@@ -76,6 +79,8 @@ class DeviceProblem:
 
 
 class TanhLinear(DeviceProblem):
+    fbd_base_point = True        # wl_tanh_linear_fbd_d / wl_tanh_linear_fbd_dense_d (TanhLinearView inherits it)
+
     def __init__(self, A, b, dtype=np.float64, stream=None):
         self.dtype = dtype
         self.m, self.n = A.shape
