@@ -411,7 +411,7 @@ int mir_lsq_batched_box_qp16_d(const mir_box_qp_settings_d* settings, size_t cou
  * with a built-in residual model r_i = model(t_i; x) - data_i evaluated inside the kernel (no callback):
  *   MIR_LSQ_MODEL_EXP_DECAY   n = 3   p0 exp(-t p1) + p2
  *   MIR_LSQ_MODEL_EXP3_AFFINE n = 8   p0 exp(-t p1) + p2 exp(-t p3) + p4 exp(-t p5) + p6 + p7 t
- * x: count x n (in/out), lower/upper: n (shared), t: m values shared by all problems (t_stride = 0) or count x m
+ * x: count x n (in/out), lower/upper: n (shared; count x n through the _ex entries with MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM), t: m values shared by all problems (t_stride = 0) or count x m
  * (t_stride = m), data: count x m, results: count. All HOST pointers. The LM algorithm, statuses and counters are
  * those of mir_optimize_least_squares_s; problems whose step reaches a finite bound are completed by the general
  * solver (BOXCQP active set) transparently, one problem at a time -- or, with MIR_LSQ_BATCHED_DEVICE_BOUNDS in
@@ -505,11 +505,25 @@ int mir_lsq_batched_kernel_d(const mir_least_squares_settings_d* settings, size_
  *     s^2 = residual / (rows with a nonzero weight - n),  or 1 with MIR_LSQ_BATCHED_ABSOLUTE_SIGMA.
  * Every entry is +inf when J^T J is not positive definite to working precision or the degrees of freedom are <= 0, and NaN
  * when the problem's status is negative (including -100 from the kernel entry: finish the problem, then call
- * mir_lsq_batched_covariance_s / _d). */
+ * mir_lsq_batched_covariance_s / _d).
+ * PER-PROBLEM BOUNDS. With MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM in flags, `lower` and `upper` of the call hold count x n values,
+ * row k being the box of problem k (host pointers in the mir_optimize_* entries, device pointers in the kernel and covariance
+ * entries, as every other pointer); without it they hold n values shared by all problems, as always. Every entry that takes an
+ * extras pointer honours the bit (the batched16 entries without _ex too), and an extras that carries only this bit is valid.
+ * Each problem is validated against its own row (boundsError, -32, for that problem alone), the -100 problems of the host entry
+ * are completed by the general solver with their own rows, and a launch whose rows are all equal gives the bits of the shared
+ * launch. The struct keeps its size.
+ * FIXED PARAMETERS. A parameter with l_j == u_j in its problem's box is fixed (the `vary = False` of a curve-fit front end). The
+ * fit keeps it exactly at that value and minimises over the others. In the covariance its row and column are exactly 0, the
+ * other entries are the covariance of the reduced problem, and s^2 = residual / (rows with a nonzero weight - n_free), n_free
+ * the number of parameters that are not fixed: the rule of mir_lsq_covariance_gpu_* below. +inf then fills the FREE entries
+ * only, when the reduced J^T J is not positive definite or rows - n_free <= 0. A parameter that merely ends on a bound with
+ * l_j < u_j is not fixed. */
 enum { MIR_LSQ_BATCHED_ABSOLUTE_SIGMA = 1u };
+enum { MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM = 2u };
 typedef struct mir_lsq_batched_extras {
     uint32_t struct_size;     /* = sizeof(mir_lsq_batched_extras) */
-    uint32_t flags;           /* MIR_LSQ_BATCHED_ABSOLUTE_SIGMA */
+    uint32_t flags;           /* MIR_LSQ_BATCHED_ABSOLUTE_SIGMA, MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM */
     const void* weights;      /* values of the entry's type: m (weight_stride 0) or count x m (weight_stride m); NULL = unweighted */
     size_t weight_stride;     /* 0 or m */
     void* covariance;         /* out: count x n x n values of the entry's type; NULL = not wanted */
@@ -567,7 +581,7 @@ int mir_lsq_batched_covariance_d(const mir_least_squares_settings_d* settings, s
  * 0, 1 and 2. Arguments as mir_optimize_least_squares_batched_ex_d (HOST pointers) and mir_lsq_batched_kernel_ex_d (DEVICE
  * pointers, enqueued on options->stream, results in place, no synchronisation except for a basis table the call had to
  * allocate). extras must be NULL or carry neither weights nor covariance: anything else is -1 (weights and covariance have
- * entries of their own, the _ex entries below). options->variant: MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN is honoured (-1 for a
+ * entries of their own, the _ex entries below); its flags may carry MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM (lower / upper: count x n). options->variant: MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN is honoured (-1 for a
  * model without a derivative: GAUSS3_AFFINE); MIR_LSQ_BATCHED_NO_LADDER and MIR_LSQ_BATCHED_DEVICE_BOUNDS are accepted and
  * change nothing. Checks in the usual order: -1 for the model id, the options and the extras, then the pointers and t_stride,
  * then -2 for the device; -3: m = 0 or a problem does not fit its workgroup's LDS ((16 + 2) m + 272 doubles <= 160 KB - 512:

@@ -54,6 +54,16 @@
 // launch_batched_bounded, which leaves no such problem).
 // tests/user_model/user_model_weighted.hip is the example.
 //
+// Per-problem bounds and fixed parameters. With MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM in extras->flags (an extras with nothing else
+// is valid) `lower` and `upper` hold count x n values, row k being problem k's box; without it n values serve every problem.
+// Every launch_* of this file honours the bit: the kernels take `lower + prob * n` once at entry (k_lm_batched in instances of
+// their own, k_lm_batched<Model, WEIGHTED, Bounds, true>, so that a shared-bounds launch runs the code it always ran; the other
+// kernels through a run-time stride of 0 or n), so a launch whose rows are all equal gives the bits of the shared launch, and each problem is validated against its own row
+// (boundsError, -32, for that problem alone). A parameter with l_j == u_j in its problem's box is FIXED: the fit keeps it at
+// that value, and in the covariance its row and column are exactly 0, the other entries are the reduced problem's covariance
+// and s^2 divides by rows - n_free; +inf then fills the free entries only. One that ends on a bound with l_j < u_j is not fixed.
+// tests/user_model/user_model_problem_bounds.hip is the example.
+//
 // Models with 9 to 16 parameters (double only): launch_batched16<Model>, at the end of this file. The model contract is the one
 // above with `using value_type = double;`, 9 <= n <= 16 and 16 entries in x (x[n..16) = 0); the kernel is a different one
 // (mir_optim_amd/csrc/batched16_kernel.h: J^T J on the matrix unit, the n x n work in the 16-lane-row layout, bounds always
@@ -105,6 +115,11 @@ inline bool batched_extras(const mir_lsq_batched_extras* extras, size_t m, mir_l
     std::memcpy(&e, extras, extras->struct_size < sizeof e ? extras->struct_size : sizeof e);
     e.struct_size = sizeof e;
     return e.weight_stride == 0 || e.weight_stride == m;
+}
+// the stride of lower / upper in the kernels' arguments: n with MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM (count x n values), else 0
+template <class Model> constexpr int bound_stride(const mir_lsq_batched_extras& e)
+{
+    return (e.flags & MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM) ? Model::n : 0;
 }
 
 // The per-row basis table of a launch: the caller's (options->basis) or one of this call's own.
@@ -165,6 +180,7 @@ void enqueue_covariance(const batched_settings_t<Model>* S, size_t count, size_t
     c.weights = static_cast<const T*>(e.weights); c.w_stride = (int)e.weight_stride;
     c.variant = variant; c.flags = e.flags;
     c.cov = static_cast<T*>(e.covariance);
+    c.b_stride = bound_stride<Model>(e);
     hipLaunchKernelGGL(mirlsq::k_batched_covariance<Model>, dim3((unsigned)count), dim3(64), 0, stream, c);
 }
 }  // namespace detail
@@ -174,7 +190,9 @@ namespace detail {
 template <class Model, class Bounds>
 bool enqueue_fit(const mirlsq::BatchedArgs<batched_value_t<Model>>& a, bool weighted, size_t lds, hipStream_t stream)
 {
-    auto kern = weighted ? mirlsq::k_lm_batched<Model, true, Bounds> : mirlsq::k_lm_batched<Model, false, Bounds>;   // the host picks the instance
+    // the host picks the instance: weighted or not, one box for the batch or a row per problem
+    auto kern = a.b_stride ? (weighted ? mirlsq::k_lm_batched<Model, true, Bounds, true> : mirlsq::k_lm_batched<Model, false, Bounds, true>)
+                           : (weighted ? mirlsq::k_lm_batched<Model, true, Bounds> : mirlsq::k_lm_batched<Model, false, Bounds>);
     if (lds > 48 * 1024
         && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return false;
@@ -215,6 +233,7 @@ int launch_batched_with(const batched_settings_t<Model>* S, size_t count, size_t
     a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
     a.results = reinterpret_cast<BatchedResult<T>*>(results);
     a.weights = static_cast<const T*>(e.weights); a.w_stride = (int)e.weight_stride;
+    a.b_stride = detail::bound_stride<Model>(e);
     detail::BasisTable<Model> basis;
     if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
     a.basis = basis.table;
@@ -364,6 +383,7 @@ bool enqueue_covariance16(const mir_least_squares_settings_d* S, size_t count, s
     c.weights = static_cast<const double*>(e.weights); c.w_stride = (int)e.weight_stride;
     c.variant = variant; c.flags = e.flags;
     c.cov = static_cast<double*>(e.covariance);
+    c.b_stride = bound_stride<Model>(e);
     return Kernels::covariance(c, batched16_covariance_lds_bytes(m), stream);
 }
 
@@ -391,6 +411,7 @@ int launch_batched16_with(const mir_least_squares_settings_d* S, size_t count, s
     a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
     a.results = reinterpret_cast<BatchedResult<double>*>(results);
     a.weights = static_cast<const double*>(e.weights); a.w_stride = (int)e.weight_stride;
+    a.b_stride = bound_stride<Model>(e);
     BasisTable<Model> basis;
     if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
     a.basis = basis.table;

@@ -35,7 +35,7 @@ __all__ = [
     "fit_spline_residuals", "variant_lr_cap",
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
     "VARIANT_SOLVE_BOUNDED", "VARIANT_DEBUG_SOLVE", "VARIANT_HOST_PROFILE", "VARIANT_SOLVE_GENERIC", "VARIANT_SOLVE_ONE_WORKGROUP", "VARIANT_DEBUG_HELPERS_ABSENT", "VARIANT_FD_HOST_COLUMNS",
-    "VARIANT_NO_PIPELINE", "FD_BASE_POINT", "VARIANT_NO_FD_BASE_POINT", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA",
+    "VARIANT_NO_PIPELINE", "FD_BASE_POINT", "VARIANT_NO_FD_BASE_POINT", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA", "BATCHED_BOUNDS_PER_PROBLEM",
     "covariance", "spdInverse", "COVARIANCE_ABSOLUTE_SIGMA",
 ]
 
@@ -665,6 +665,22 @@ def _batched_suffix(dtype):
     raise ValueError(f"the batched entries exist in float32 and float64, not {np.dtype(dtype)}")
 
 
+def _batched_bounds(l, u, count, n, dtype):
+    """l / u of a batched call as contiguous arrays of `dtype`: (lo, up, per_problem). Each is None, n values (one box for the
+    batch) or count x n (row k the box of problem k); the two have one shape, a None takes its partner's (-inf / +inf)."""
+    lo = None if l is None else np.ascontiguousarray(l, dtype=dtype)
+    up = None if u is None else np.ascontiguousarray(u, dtype=dtype)
+    shape = lo.shape if lo is not None else up.shape if up is not None else (n,)
+    if shape not in ((n,), (count, n)) or (up is not None and up.shape != shape):
+        raise ValueError(f"l and u: {n} values each or {count} x {n} each, not {None if lo is None else lo.shape} and "
+                         f"{None if up is None else up.shape}")
+    if lo is None:
+        lo = np.full(shape, -np.inf, dtype=dtype)
+    if up is None:
+        up = np.full(shape, np.inf, dtype=dtype)
+    return lo, up, len(shape) == 2
+
+
 def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None, variant=0, dtype=np.float32, weights=None,
                                 covariance=False, absolute_sigma=False):
     """Many independent small fits, one wavefront per problem (mir_optimize_least_squares_batched_s, fp32, or with
@@ -675,6 +691,10 @@ def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None
     s^2 = residual / (rows with nonzero weight - n), or s^2 = 1 with absolute_sigma=True; +inf for a singular J^T J or no
     degrees of freedom, NaN for a problem with a negative status. Any of the three goes through the _ex entry
     (mir_optimize_least_squares_batched_ex_s / _d); a call without them is the call it always was.
+    l / u: n values (one box for the batch) or count x n (row k is the box of problem k; a None beside a 2-D partner is -inf /
+    +inf of that shape; anything else raises ValueError). 2-D bounds go through the _ex entry with BATCHED_BOUNDS_PER_PROBLEM;
+    1-D bounds make the call they always made. A parameter with l_j == u_j is fixed: the fit keeps it there, and its row and
+    column of the covariance are 0 (s^2 then divides by rows - the number of free parameters).
     A MODEL16_* id (9 to 16 parameters) goes to mir_optimize_least_squares_batched16_d: dtype must be float64, and weights,
     covariance and absolute_sigma raise ValueError (optimizeLeastSquaresBatched16 takes them)."""
     if int(model) in _MODELS16:
@@ -688,19 +708,18 @@ def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None
     m = data.shape[1]
     t = np.ascontiguousarray(t, dtype=dtype)
     t_stride = 0 if t.ndim == 1 else m
-    lo = np.full(n, -np.inf, dtype=dtype) if l is None else np.ascontiguousarray(l, dtype=dtype)
-    up = np.full(n, np.inf, dtype=dtype) if u is None else np.ascontiguousarray(u, dtype=dtype)
+    lo, up, per_problem = _batched_bounds(l, u, count, n, dtype)
     if settings is None:
         settings = LeastSquaresSettings(dtype)
     raw = ((_Rs if suf == "s" else _Rd) * count)()
-    if weights is None and not covariance and not absolute_sigma:
+    if weights is None and not covariance and not absolute_sigma and not per_problem:
         fn = getattr(L, "mir_optimize_least_squares_batched_" + suf)
         rc = fn(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data, up.ctypes.data, t.ctypes.data, t_stride,
                 data.ctypes.data, raw, C.byref(BatchedOptions(variant=variant)))
         if rc != 0:
             raise RuntimeError(f"mir_optimize_least_squares_batched_{suf} failed: {rc}")
         return [LeastSquaresResult(r) for r in raw], x
-    ex = BatchedExtras(flags=BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0)
+    ex = BatchedExtras(flags=(BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0) | (BATCHED_BOUNDS_PER_PROBLEM if per_problem else 0))
     if weights is not None:
         weights = np.ascontiguousarray(weights, dtype=dtype)
         if weights.shape not in ((m,), (count, m)):
@@ -732,14 +751,15 @@ def _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weigh
     m = data.shape[1]
     t = np.ascontiguousarray(t, dtype=np.float64)
     t_stride = 0 if t.ndim == 1 else m
-    lo = np.full(n, -np.inf) if l is None else np.ascontiguousarray(l, dtype=np.float64)
-    up = np.full(n, np.inf) if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    lo, up, per_problem = _batched_bounds(l, u, count, n, np.float64)
     if settings is None:
         settings = LeastSquaresSettings(np.float64)
     raw = (_Rd * count)()
+    # 2-D bounds: this entry with an extras that carries the flag and nothing else; 1-D: no extras, as always
+    ex = BatchedExtras(flags=BATCHED_BOUNDS_PER_PROBLEM) if per_problem else None
     rc = L.mir_optimize_least_squares_batched16_d(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data,
                                                   up.ctypes.data, t.ctypes.data, t_stride, data.ctypes.data, raw,
-                                                  C.byref(BatchedOptions(variant=variant)), None)
+                                                  C.byref(BatchedOptions(variant=variant)), C.byref(ex) if per_problem else None)
     if rc != 0:
         raise RuntimeError(f"mir_optimize_least_squares_batched16_d failed: {rc}")
     return [LeastSquaresResult(r) for r in raw], x
@@ -754,7 +774,8 @@ def optimizeLeastSquaresBatched16(model, x, t, data, l=None, u=None, settings=No
     lengths are padded to a common m that way). covariance=True: returns (results, x, cov), cov count x n x n =
     s^2 inv(J^T J) at the returned x with s^2 = residual / (rows with nonzero weight - n), or s^2 = 1 with absolute_sigma=True;
     +inf for a singular J^T J or no degrees of freedom, NaN for a problem with a negative status. Otherwise returns (results, x).
-    A call with none of the three is the call optimizeLeastSquaresBatched makes for these models."""
+    A call with none of the three is the call optimizeLeastSquaresBatched makes for these models.
+    l / u: n values or count x n (row k the box of problem k), as in optimizeLeastSquaresBatched; l_j == u_j fixes parameter j."""
     if int(model) not in _MODELS16:
         raise ValueError(f"optimizeLeastSquaresBatched16 takes a MODEL16_* id, not {model}")
     for name, a in (("x", x), ("t", t), ("data", data), ("weights", weights)):
@@ -774,13 +795,10 @@ def optimizeLeastSquaresBatched16(model, x, t, data, l=None, u=None, settings=No
     if t.shape not in ((m,), (count, m)):
         raise ValueError(f"t: {m} values or {count} x {m}, not {t.shape}")
     t_stride = 0 if t.ndim == 1 else m
-    lo = np.full(n, -np.inf) if l is None else np.ascontiguousarray(l, dtype=np.float64)
-    up = np.full(n, np.inf) if u is None else np.ascontiguousarray(u, dtype=np.float64)
-    if lo.shape != (n,) or up.shape != (n,):
-        raise ValueError(f"l and u: {n} values each, not {lo.shape} and {up.shape}")
+    lo, up, per_problem = _batched_bounds(l, u, count, n, np.float64)
     if settings is None:
         settings = LeastSquaresSettings(np.float64)
-    ex = BatchedExtras(flags=BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0)
+    ex = BatchedExtras(flags=(BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0) | (BATCHED_BOUNDS_PER_PROBLEM if per_problem else 0))
     if weights is not None:
         weights = np.ascontiguousarray(weights, dtype=np.float64)
         if weights.shape not in ((m,), (count, m)):
@@ -824,6 +842,7 @@ def batched16JtJ(J, y):
 BATCHED_NO_LADDER = 1
 BATCHED_DEVICE_BOUNDS = 4       # MIR_LSQ_BATCHED_DEVICE_BOUNDS: bounded steps are solved inside the wave kernel (no -100, no fallback)
 BATCHED_ABSOLUTE_SIGMA = 1      # mir_lsq_batched_extras.flags
+BATCHED_BOUNDS_PER_PROBLEM = 2  # mir_lsq_batched_extras.flags: lower / upper hold count x n values, row k the box of problem k
 
 
 def batchedPosvx(P, rhs, dtype=np.float32):

@@ -104,7 +104,8 @@ def build_user_model_example(force=False, verbose=False):
     The double model of user_model_f64.hip goes into a library of its own next to it (user_model_f64_lib()), and so does the
     weighted fit with covariance of user_model_weighted.hip (user_model_weighted_lib()) and the fit with binding bounds of
     user_model_bounded.hip (user_model_bounded_lib()), and the 9 and 13 parameter models of user_model_n16.hip
-    (user_model_n16_lib()) and their weighted fits with covariance of user_model_n16_weighted.hip (user_model_n16_weighted_lib())."""
+    (user_model_n16_lib()) and their weighted fits with covariance of user_model_n16_weighted.hip (user_model_n16_weighted_lib()),
+    and the fit with a box per problem of user_model_problem_bounds.hip (user_model_problem_bounds_lib())."""
     root = os.path.dirname(HERE)
     src = os.path.join(root, "tests", "user_model", "user_model.hip")
     out = os.path.join(root, "tests", "user_model", "libuser_model.so")
@@ -131,6 +132,9 @@ def build_user_model_example(force=False, verbose=False):
     src16w, out16w = user_model_n16_weighted_paths()
     if force or _stale(out16w, [src16w] + deps16):
         _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out16w, src16w], verbose)
+    srcp, outp = user_model_problem_bounds_paths()
+    if force or _stale(outp, [srcp] + deps[1:9]):
+        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", outp, srcp], verbose)
     return out
 
 
@@ -192,3 +196,15 @@ def user_model_n16_weighted_lib(force=False, verbose=False):
     """Builds (when stale) and returns the path of tests/user_model/libuser_model_n16_weighted.so."""
     build_user_model_example(force=force, verbose=verbose)
     return user_model_n16_weighted_paths()[1]
+
+
+def user_model_problem_bounds_paths():
+    """(source, library) of the caller's fit with a box per problem (tests/user_model/user_model_problem_bounds.hip)"""
+    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
+    return os.path.join(d, "user_model_problem_bounds.hip"), os.path.join(d, "libuser_model_problem_bounds.so")
+
+
+def user_model_problem_bounds_lib(force=False, verbose=False):
+    """Builds (when stale) and returns the path of tests/user_model/libuser_model_problem_bounds.so."""
+    build_user_model_example(force=force, verbose=verbose)
+    return user_model_problem_bounds_paths()[1]

@@ -10,11 +10,22 @@ using namespace mirlsq;
 namespace {
 
 // NULL, or a plausible struct that asks for neither weights nor covariance (those have entries of their own, the _ex entries of
-// batched16_ex_d.hip: these two answer -1, as they did before those existed)
+// batched16_ex_d.hip: these two answer -1, as they did before those existed). Its flags pass: MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM
+// needs no other kernel instance.
 bool extras16_acceptable(const mir_lsq_batched_extras* extras, size_t m)
 {
     mir_lsq_batched_extras e;
     return mir_optim_amd::detail::batched_extras(extras, m, e) && !e.weights && !e.covariance;
+}
+// what such an extras hands on to the launch: its per-problem-bounds bit and nothing else; false: nothing to hand on
+bool extras16_flags_only(const mir_lsq_batched_extras* extras, size_t m, mir_lsq_batched_extras& f)
+{
+    mir_lsq_batched_extras e;
+    (void)mir_optim_amd::detail::batched_extras(extras, m, e);
+    f = mir_lsq_batched_extras{};
+    f.struct_size = sizeof f;
+    f.flags = e.flags & MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM;
+    return f.flags != 0;
 }
 
 // the kernels of this unit: the unweighted fit and nothing else
@@ -47,8 +58,10 @@ int mir_lsq_batched16_kernel_d(const mir_least_squares_settings_d* S, size_t cou
         if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
         if (count != 0 && !device_available()) return -2;
         const mir_lsq_batched_options o = batched_options(options);
+        mir_lsq_batched_extras f;
+        const bool per_problem = extras16_flags_only(extras, m, f);
         return mir_optim_amd::detail::launch_batched16_with<decltype(mdl), Batched16PlainKernels<decltype(mdl)>>(
-            S, count, m, x, lower, upper, t, t_stride, data, results, &o, nullptr);
+            S, count, m, x, lower, upper, t, t_stride, data, results, &o, per_problem ? &f : nullptr);
     });
 }
 
@@ -61,8 +74,11 @@ int mir_optimize_least_squares_batched16_d(const mir_least_squares_settings_d* S
         if (!batched_options_plausible(options) || !extras16_acceptable(extras, m)) return -1;
         if (!batched_has_grad<decltype(mdl)>::value && (batched_options(options).variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN)) return -1;
         if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
+        mir_lsq_batched_extras f;
+        const bool per_problem = extras16_flags_only(extras, m, f);
         return batched16_host_model_entry<decltype(mdl), Batched16PlainKernels<decltype(mdl)>>(S, count, m, x, lower, upper, t, t_stride,
-                                                                                               data, results, options, nullptr);
+                                                                                               data, results, options,
+                                                                                               per_problem ? &f : nullptr);
     });
 }
 

@@ -68,10 +68,12 @@ int batched16_host_model_entry(const mir_least_squares_settings_d* S, size_t cou
     const size_t basis_b = mir_optim_amd::batched_basis_floats<Model>(count, m, t_stride) * sizeof(double);
     const size_t tb = (t_stride ? count : 1) * m * sizeof(double), db = count * m * sizeof(double), xb = count * n * sizeof(double);
     const size_t wb = wn * sizeof(double), cb = cov ? count * n * n * sizeof(double) : 0;
+    // MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM: lower / upper hold count x n values, row i the box of problem i
+    const size_t bb = ((e.flags & MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM) ? count : 1) * n * sizeof(double);
     char* base = nullptr;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o_ = off; off = align_up(off + bytes, 256); return o_; };
-    const size_t ot = take(tb), od = take(db), ox = take(xb), ol = take(n * sizeof(double)), ou = take(n * sizeof(double)),
+    const size_t ot = take(tb), od = take(db), ox = take(xb), ol = take(bb), ou = take(bb),
                  orr = take(count * sizeof(Result)), obasis = take(basis_b), ow = take(wb), oc = take(cb);
     if (hipMalloc((void**)&base, off) != hipSuccess) return -4;
     o.basis = basis_b ? (float*)(base + obasis) : nullptr;      // the C member is float*; it holds doubles here
@@ -82,8 +84,8 @@ int batched16_host_model_entry(const mir_least_squares_settings_d* S, size_t cou
     bool good = hipMemcpy(base + ot, t, tb, hipMemcpyHostToDevice) == hipSuccess
         && hipMemcpy(base + od, data, db, hipMemcpyHostToDevice) == hipSuccess
         && hipMemcpy(base + ox, x, xb, hipMemcpyHostToDevice) == hipSuccess
-        && hipMemcpy(base + ol, lower, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
-        && hipMemcpy(base + ou, upper, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess
+        && hipMemcpy(base + ol, lower, bb, hipMemcpyHostToDevice) == hipSuccess
+        && hipMemcpy(base + ou, upper, bb, hipMemcpyHostToDevice) == hipSuccess
         && (!wb || hipMemcpy(base + ow, weights, wb, hipMemcpyHostToDevice) == hipSuccess);
     good = good
         && mir_optim_amd::detail::launch_batched16_with<Model, Kernels>(

@@ -144,7 +144,8 @@ __global__ __launch_bounds__(64, 1) void k_lm_batched16(BatchedArgs<double> a)
 
     // component r of x and of the bounds in lane r of every 16-lane group; x replicated in every lane beside it
     T xr = a.x[(size_t)prob * N + (el ? r : 0)];
-    T lo_r = a.lower[el ? r : 0], up_r = a.upper[el ? r : 0];
+    const size_t bo = (size_t)prob * a.b_stride + (el ? r : 0);   // the problem's own box (b_stride n) or the shared one (0)
+    T lo_r = a.lower[bo], up_r = a.upper[bo];
     xr = el ? xr : T(0);
     lo_r = el ? lo_r : -Lim<T>::inf();
     up_r = el ? up_r : Lim<T>::inf();
@@ -353,7 +354,11 @@ __global__ __launch_bounds__(64, 1) void k_lm_batched16(BatchedArgs<double> a)
 // meet in LDS (where the tile was), and element (i, c) is s^2 (v_ic + v_ci) / 2: symmetric bit for bit. n x n values a problem,
 // row-major. Degenerate cases:
 //     status < 0                                                        every entry NaN
-//     a non-positive pivot in the factorization, or rows - n <= 0        every entry +inf
+//     a non-positive pivot in the factorization, or rows - n_free <= 0   every free entry +inf
+// The box is the problem's own (BatchedCovArgs::b_stride n) or the shared one (0). A parameter with l_j == u_j in it is FIXED,
+// as in k_batched_covariance: its column of J is zero, its row is not a live row
+// of posvx_rows16 (identity row and column: the system solved is the reduced one, of order n_free), row j and column j of the
+// result are exactly 0, and s^2 divides by rows - n_free. Without a fixed parameter every operation is the one it was.
 // LDS: J, one m-vector of zeros where jtj16_tile reads y, the tile: (16 + 1) m + 272 doubles -- less than the fit's.
 // Control flow is wave-uniform; lanes exchange data through LDS behind wave_lds_fence(), there is no barrier.
 template <class Model>
@@ -381,12 +386,18 @@ __global__ __launch_bounds__(64, 1) void k_batched16_covariance(BatchedCovArgs<d
     const T* wp = a.weights ? a.weights + (size_t)(a.w_stride ? prob : 0) * a.w_stride : nullptr;
 
     T xr = a.x[(size_t)prob * N + (el ? r : 0)];
-    T lo_r = a.lower[el ? r : 0], up_r = a.upper[el ? r : 0];
+    const size_t bo = (size_t)prob * a.b_stride + (el ? r : 0);   // the problem's own box (b_stride n) or the shared one (0)
+    T lo_r = a.lower[bo], up_r = a.upper[bo];
     xr = el ? xr : T(0);
     lo_r = el ? lo_r : -Lim<T>::inf();
     up_r = el ? up_r : Lim<T>::inf();
     T x[W];
     static_for<W>([&](auto K) { constexpr int k = decltype(K)::value; x[k] = dpp_row_bcast<k>(xr); });
+    // l_j == u_j: parameter j is fixed. Bit j of `fix` (wave-uniform); free_r: row r belongs to the system that is solved
+    const bool fixed_r = el && lo_r == up_r;
+    const unsigned fix = (unsigned)(__ballot(fixed_r) & 0xffffull);
+    const bool free_r = el && !fixed_r;
+    const int nfree = N - __builtin_popcount(fix);
 
     constexpr bool HAS_GRAD = batched_has_grad<Model>::value;
     const bool use_g = HAS_GRAD && (a.variant & kBatchedAnalytic) != 0;
@@ -407,14 +418,14 @@ __global__ __launch_bounds__(64, 1) void k_batched16_covariance(BatchedCovArgs<d
                     for (int j = 0; j < N; ++j) gi[j] = wi * gi[j];
                 }
 #pragma unroll
-                for (int j = 0; j < W; ++j) Jl[(size_t)i * W + j] = j < N ? gi[j] : T(0);
+                for (int j = 0; j < W; ++j) Jl[(size_t)i * W + j] = (j < N && !((fix >> j) & 1u)) ? gi[j] : T(0);   // no column for a fixed one
                 yv[i] = T(0);
             }
         }
     } else {
         const T xmh_r = vmax(xr - a.jacobianEpsilon, lo_r), xph_r = vmin(xr + a.jacobianEpsilon, up_r);
         const T twh_r = xph_r - xmh_r;
-        const T inv_r = twh_r != 0 ? T(1) / twh_r : T(0);
+        const T inv_r = (twh_r != 0 && !fixed_r) ? T(1) / twh_r : T(0);     // 0: the column is not formed
         T xph[W], xmh[W], inv[W];
         static_for<W>([&](auto K) {
             constexpr int k = decltype(K)::value;
@@ -444,7 +455,7 @@ __global__ __launch_bounds__(64, 1) void k_batched16_covariance(BatchedCovArgs<d
             yv[i] = T(0);
         }
     }
-    const T dof = wave_sum(rows) - T(N);                  // row counts are small integers: exact
+    const T dof = wave_sum(rows) - T(nfree);              // row counts are small integers: exact
     jtj16_tile(Jl, yv, m, tile);
     T JJrow[W];
 #pragma unroll
@@ -457,7 +468,8 @@ __global__ __launch_bounds__(64, 1) void k_batched16_covariance(BatchedCovArgs<d
     for (int q = 0; q < (N + 3) / 4; ++q) {
         const int c = 4 * q + g;
         T v_r;
-        info |= posvx_rows16<N>(JJrow, 0.0, djj, (r == c && el) ? T(1) : T(0), el, r, v_r, N);
+        // the rows of fixed parameters are not live: identity rows and columns, a zero right-hand side, a zero solution
+        info |= posvx_rows16<N>(JJrow, 0.0, djj, (r == c && free_r) ? T(1) : T(0), free_r, r, v_r, nfree);
         tile[r * W + c] = v_r;                            // c <= 15
     }
     info = __builtin_amdgcn_readfirstlane(info);          // the four groups factor the same matrix
@@ -467,7 +479,8 @@ __global__ __launch_bounds__(64, 1) void k_batched16_covariance(BatchedCovArgs<d
     for (int idx = lane; idx < N * N; idx += kWave) {
         const int i = idx / N, c = idx - i * N;
         const T v = s2 * ((tile[i * W + c] + tile[c * W + i]) / 2);
-        out[idx] = degenerate ? Lim<T>::inf() : v;
+        const bool fx = (((fix >> i) | (fix >> c)) & 1u) != 0;          // row and column of a fixed parameter: exactly 0
+        out[idx] = fx ? T(0) : (degenerate ? Lim<T>::inf() : v);
     }
 }
 

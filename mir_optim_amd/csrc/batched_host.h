@@ -178,7 +178,9 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o_ = off; off = align_up(off + bytes, 256); return o_; };
     const size_t wb = wn * sizeof(T), cb = cov ? count * n * n * sizeof(T) : 0;
-    const size_t ot = take(tb), od = take(db), ox = take(xb), ol = take(n * sizeof(T)), ou = take(n * sizeof(T)),
+    // MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM: lower / upper hold count x n values, row i the box of problem i
+    const size_t bstep = (e.flags & MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM) ? n : 0, bb = (bstep ? count : 1) * n * sizeof(T);
+    const size_t ot = take(tb), od = take(db), ox = take(xb), ol = take(bb), ou = take(bb),
                  orr = take(count * sizeof(Result)), obasis = take(basis_b), ow = take(wb), oc = take(cb);
     if (hipMalloc((void**)&base, off) != hipSuccess) return -4;
     o.basis = basis_b ? (float*)(base + obasis) : nullptr;      // the C member is float*; it holds doubles for a double model
@@ -186,8 +188,8 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
     bool good = hipMemcpy(base + ot, t, tb, hipMemcpyHostToDevice) == hipSuccess
         && hipMemcpy(base + od, data, db, hipMemcpyHostToDevice) == hipSuccess
         && hipMemcpy(base + ox, x, xb, hipMemcpyHostToDevice) == hipSuccess
-        && hipMemcpy(base + ol, lower, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess
-        && hipMemcpy(base + ou, upper, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess
+        && hipMemcpy(base + ol, lower, bb, hipMemcpyHostToDevice) == hipSuccess
+        && hipMemcpy(base + ou, upper, bb, hipMemcpyHostToDevice) == hipSuccess
         && (!wb || hipMemcpy(base + ow, weights, wb, hipMemcpyHostToDevice) == hipSuccess);
     // the device twin of the extras: the weights for the fit; the covariance comes after the fallback solves, below
     const T* dw = wb ? (const T*)(base + ow) : nullptr;
@@ -217,7 +219,7 @@ int batched_host_model_entry(const typename Abi<T>::Settings* S, size_t count, s
                 mir_lsq_gpu_options go{};
                 go.struct_size = sizeof go; go.flags = MIR_LSQ_DEVICE_CALLBACKS; go.stream = st;
                 std::memcpy(x + i * n, x0.data() + i * n, n * sizeof(T));
-                results[i] = solve_entry<T>(S, m, n, x + i * n, lower, upper, &go, &c, batched_fallback<Model>, nullptr, nullptr,
+                results[i] = solve_entry<T>(S, m, n, x + i * n, lower + i * bstep, upper + i * bstep, &go, &c, batched_fallback<Model>, nullptr, nullptr,
                                             nullptr, nullptr);
                 (void)hipStreamDestroy(st);
             }

@@ -169,14 +169,16 @@ template <class T> struct BatchedArgs {
     int t_stride;          // 0 = shared
     const T* data;         // count x m
     T* x;                  // count x n, in/out
-    const T* lower;        // n (shared)
-    const T* upper;        // n
+    const T* lower;        // n (shared: b_stride 0) or count x n (b_stride n: row k is problem k's box)
+    const T* upper;        // as lower
     BatchedResult<T>* results;
     const T* basis;        // (t_stride ? count : 1) x m x nb: the model's per-row basis (k_batched_basis), nullptr when nb == 0
     uint64_t* timing;      // profiling builds (MIRLSQ_BATCHED_TIMING): 10 x count cycle counters (mir_lsq_batched_options.timing), else unused
     uint32_t variant;      // kBatchedNoLadder: one damping value per solve (A/B and the test of the ladder against it)
     int w_stride;          // 0 = one vector of m weights shared by all problems, m = count x m
     const T* weights;      // the WEIGHTED instances only (k_lm_batched<Model, true>): the residual of row i is w_i (eval - data_i)
+    int b_stride;          // 0 = one box of n values for all problems, n = count x n (MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM): read by
+                           // k_lm_batched16; for k_lm_batched the host picks the OWN_BOX instance from it
 };
 constexpr uint32_t kBatchedNoLadder = 1u;
 constexpr uint32_t kBatchedAnalytic = 2u;      // MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN: Model::grad instead of finite differences
@@ -427,7 +429,13 @@ template <class Model> constexpr int batched_waves_per_simd()
 struct BatchedNoBoundedStep { static constexpr bool enabled = false; };
 constexpr uint32_t kBatchedDeviceBounds = 4u;  // MIR_LSQ_BATCHED_DEVICE_BOUNDS: the host launches a bounded instance (the kernel does not read the bit)
 
-template <class Model, bool WEIGHTED = false, class Bounds = BatchedNoBoundedStep>
+// OWN_BOX (MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM; the host picks the instance from BatchedArgs::b_stride, as it picks WEIGHTED):
+// lower / upper hold count x n values and the problem takes row `prob`, wave-uniform address arithmetic once at entry. A
+// compile-time parameter and not the run-time stride the other kernels read, because the shared-bounds launch of two families
+// (EXP_DECAY_PAD8 f32 default, f64 bounded) measured outside the spread of two runs of the parent with it
+// (profiles/r18/batched_problem_bounds.txt): the shared-bounds instances do not read b_stride and are, instruction for
+// instruction, what they were before per-problem bounds existed.
+template <class Model, bool WEIGHTED = false, class Bounds = BatchedNoBoundedStep, bool OWN_BOX = false>
 __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batched(BatchedArgs<batched_value_t<Model>> a)
 {
     // Nothing in this body is left to the compiler's choice of what to fuse: contraction is off and every multiply-add that is
@@ -455,13 +463,19 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
     const LmSettingsDev<T>& S = a.set;
     const T* wp = nullptr;
     if constexpr (WEIGHTED) wp = a.weights + (size_t)(a.w_stride ? prob : 0) * a.w_stride;
+    const T* lop = a.lower;
+    const T* upp = a.upper;
+    if constexpr (OWN_BOX) {                              // the problem's own row
+        lop += (size_t)prob * N;
+        upp += (size_t)prob * N;
+    }
 
     T x[NMAX], lo[NMAX], up[NMAX];
 #pragma unroll
     for (int j = 0; j < NMAX; ++j) {
         x[j] = j < N ? a.x[(size_t)prob * N + j] : T(0);
-        lo[j] = j < N ? a.lower[j] : -Lim<T>::inf();
-        up[j] = j < N ? a.upper[j] : Lim<T>::inf();
+        lo[j] = j < N ? lop[j] : -Lim<T>::inf();
+        up[j] = j < N ? upp[j] : Lim<T>::inf();
     }
 #ifdef MIRLSQ_BATCHED_TIMING
     uint64_t tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -800,7 +814,12 @@ __global__ __launch_bounds__(64, batched_waves_per_simd<Model>()) void k_lm_batc
 // groups take four columns a call. ||f(x)||^2 and the status are read from the fit's result record. The n x n values of a
 // problem are written row-major, symmetric (the mean of the two solves' mirror elements). Degenerate cases:
 //     status < 0 (also -100 from the kernel entry: that problem is not finished)   every entry NaN
-//     a non-positive minor in the factorization, or rows - n <= 0                   every entry +inf
+//     a non-positive minor in the factorization, or rows - n_free <= 0              every free entry +inf
+// The box is the problem's own (b_stride n) or the shared one (0). A parameter with l_j == u_j in it is FIXED (the rule of the
+// general solver's covariance, covariance.hip; one that merely sits on a bound with l_j < u_j is not): its Jacobian column is
+// not formed (zeroed on the grad path), its index is taken out of the system (unit diagonal, zero off-diagonal), row j and
+// column j of the result are exactly 0, and n above is n_free, the number of parameters that are not fixed. A problem without
+// a fixed parameter computes, operation for operation, what it computed before the rule existed.
 template <class T> struct BatchedCovArgs {
     T jacobianEpsilon;
     int count, m;
@@ -814,6 +833,7 @@ template <class T> struct BatchedCovArgs {
     uint32_t variant;      // kBatchedAnalytic
     uint32_t flags;        // kBatchedAbsoluteSigma
     T* cov;                // count x n x n
+    int b_stride;          // 0 = lower / upper hold n values for all problems, n = count x n
 };
 constexpr uint32_t kBatchedAbsoluteSigma = 1u;      // MIR_LSQ_BATCHED_ABSOLUTE_SIGMA
 
@@ -834,16 +854,22 @@ __global__ __launch_bounds__(64) void k_batched_covariance(BatchedCovArgs<batche
     const T* dp = a.data + (size_t)prob * m;
     const T* bp = NB ? a.basis + (size_t)(a.t_stride ? prob : 0) * a.t_stride * NB : nullptr;
     const T* wp = a.weights ? a.weights + (size_t)(a.w_stride ? prob : 0) * a.w_stride : nullptr;
+    const T* lop = a.lower + (size_t)prob * a.b_stride;   // the problem's own box, or the shared one (b_stride 0)
+    const T* upp = a.upper + (size_t)prob * a.b_stride;
     T x[NMAX], xph[NMAX], xmh[NMAX], inv[NMAX];
+    unsigned fix = 0;                                     // bit j: l_j == u_j, parameter j is fixed (wave-uniform)
 #pragma unroll
     for (int j = 0; j < NMAX; ++j) {
         x[j] = j < N ? a.x[(size_t)prob * N + j] : T(0);
-        const T lo = j < N ? a.lower[j] : -Lim<T>::inf(), up = j < N ? a.upper[j] : Lim<T>::inf();
+        const T lo = j < N ? lop[j] : -Lim<T>::inf(), up = j < N ? upp[j] : Lim<T>::inf();
+        const bool fixed_j = j < N && lo == up;
+        fix |= fixed_j ? 1u << j : 0u;
         xmh[j] = vmax(x[j] - a.jacobianEpsilon, lo);
         xph[j] = vmin(x[j] + a.jacobianEpsilon, up);
         const T twh = xph[j] - xmh[j];
-        inv[j] = twh != 0 ? T(1) / twh : T(0);
+        inv[j] = (twh != 0 && !fixed_j) ? T(1) / twh : T(0);        // 0: the column of a fixed parameter is not formed
     }
+    const int nfree = N - __builtin_popcount(fix);
     constexpr bool HAS_GRAD = batched_has_grad<Model>::value;
     const bool use_g = HAS_GRAD && (a.variant & kBatchedAnalytic) != 0;
     T accJ[NMAX][NMAX], rows = 0;
@@ -866,6 +892,8 @@ __global__ __launch_bounds__(64) void k_batched_covariance(BatchedCovArgs<batche
 #pragma unroll
                     for (int j = 0; j < N; ++j) row[j] = wi * row[j];
                 }
+#pragma unroll
+                for (int j = 0; j < N; ++j) row[j] = ((fix >> j) & 1u) ? T(0) : row[j];      // a fixed parameter has no column
             }
         } else {
             T p[NMAX];
@@ -899,7 +927,12 @@ __global__ __launch_bounds__(64) void k_batched_covariance(BatchedCovArgs<batche
             JJrow[k] = (r == j) ? s : JJrow[k];
             if (k != j) JJrow[j] = (r == k) ? s : JJrow[j];
         }
-    const T dof = wave_sum(rows) - T(N);                 // row counts are small integers: exact in T
+    // the index of a fixed parameter is taken out of the system: unit diagonal, zero off-diagonal (posvx_rows then factors an
+    // SPD matrix whose free part is the reduced problem's J^T J). Without a fixed parameter every select keeps its value.
+    const bool fixed_r = ((fix >> r) & 1u) != 0;
+#pragma unroll
+    for (int k = 0; k < NMAX; ++k) JJrow[k] = (fixed_r || ((fix >> k) & 1u)) ? (r == k ? T(1) : T(0)) : JJrow[k];
+    const T dof = wave_sum(rows) - T(nfree);             // row counts are small integers: exact in T
     // column c = 4 call + g of the inverse by group g = lane >> 4: the right-hand side is the unit vector e_c
     const int g = lane >> 4;
     T sol[2][NMAX];
@@ -920,7 +953,10 @@ __global__ __launch_bounds__(64) void k_batched_covariance(BatchedCovArgs<batche
             }
         });
     });
-    if (lane < N * N) out[lane] = degenerate ? Lim<T>::inf() : mine;
+    // row and column of a fixed parameter: exactly 0, in the degenerate case too
+    const int oi = lane / N, oc = lane - oi * N;
+    const bool fixed_out = (((fix >> oi) | (fix >> oc)) & 1u) != 0;
+    if (lane < N * N) out[lane] = fixed_out ? T(0) : (degenerate ? Lim<T>::inf() : mine);
 }
 
 // residual of one problem as a DEVICE callback body (used when a batched problem falls back to the general solver); w: the
