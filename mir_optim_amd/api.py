@@ -1042,7 +1042,12 @@ def solveBoxQPBatched(P, q, l, u, x=None, settings=None, dtype=np.float64, uncon
 
 def jtj(J, y, y_old=None, dx=None, dtype=np.float64):
     """Unit-level access to the J^T J + J^T y kernels (mir_lsq_jtj_*; with dx: the Broyden REWRITE kernels, the literal
-    restatement of LS:1003-1006). Returns (JJ full symmetric, Jy, J_after, kernel_ms)."""
+    restatement of LS:1003-1006). Returns (JJ full symmetric, Jy, J_after, kernel_ms).
+    J is uploaded to the start of an allocation, so it is always 16-byte aligned here. The C entries also take a J that is an
+    element-aligned view (jtj_resolve in csrc/jtj_plan.h reroutes the kernels that need 16-byte loads); y, y_old and dx must stay
+    16-byte aligned. tests/jtj_cases.run_jtj drives the entries that way, between NaN guard bands, for every instantiated kernel
+    class -- except the eight-wave ring (f64, 128 < n <= 256, n % 16 == 0, even m) at an offset J, which is not established to be
+    defined and is not run (see the header comment of jtj_plan.h)."""
     L = lib()
     J = np.ascontiguousarray(J, dtype=dtype)
     m, n = J.shape

@@ -17,6 +17,17 @@
 // (1) the flat producer (8-byte aligned loads) for odd n, for the difference panel with n % 16 != 0 and -- decided at the launch,
 //     jtj_resolve -- for a J that is not 16-byte aligned.  (2) n % 64 == 0 only (n = 192, 256), else none.
 // (3) k_broyden_wide (n <= 256) / k_broyden_rows in front.  (4) a J that is not 16-byte aligned: stream_fallback (jtj_resolve).
+//
+// Offset views. Only J (plain, rewrite) and the difference panel / Jout (fd_diff) may be element-aligned views handed to a unit
+// entry; y, y_old, dx, twh and the pair panel of `fd` are the library's own buffers and always 16-byte aligned. What is verified,
+// at kernel level (tests/jtj_cases.py, tests/test_gpu_jtj_cells.py; tests/test_jtj_cell_coverage.py proves that every instance
+// launch_jtj.hip compiles is in that list): with every buffer between NaN guard bands that must come back bit-identical, each
+// instance is bit-exact on exact-integer data, inside the forward bound gamma_m |J|^T |J| on random data, deterministic, keeps a
+// NaN of the last row to its row and column, and -- stream, fdp's flat producer, fdp8's plain flavour, wide and the two reroutings
+// of jtj_resolve -- gives the bits of the aligned run for a J one element off the 16-byte grid.
+// OPEN: ring8 at an offset pointer. k_jtj8 issues 16-byte global_load_lds from J, y and y_old, jtj_resolve keeps ring8 for an
+// unaligned J, and nothing in the code establishes that a 16-byte LDS-DMA from an 8-byte-aligned address is defined. It is not
+// run anywhere; rerouting it (fdp8's plain flavour / wide take any pointer) is the follow-up.
 #pragma once
 
 #include <initializer_list>
