@@ -840,6 +840,8 @@ const char* mir_lsq_version(void);
  * the reference's `alias d = "a - b"` (NULL = a - b); splineY (out, nx): fitted values, started from 0 (FS:56-57);
  * splineD (out, nx, optional): first derivatives. Returns MIR_FIT_SPLINE_*; the LM status is in *result (the D
  * function throws for result->status < 0 through `optimize`, LS:175-179, and for TOO_FEW_POINTS, FS:47-51).
+ * mir_fit_spline_d / _s run the fit through host callbacks (points in host memory, an optional `dist`);
+ * mir_fit_spline_gpu_d / _s, further down, take the points as a DEVICE array and evaluate the residuals in kernels.
  * ===================================================================================================== */
 enum { MIR_FIT_SPLINE_OK = 0, MIR_FIT_SPLINE_TOO_FEW_POINTS = 1, MIR_FIT_SPLINE_BAD_ARGUMENT = 2 };
 
@@ -857,6 +859,50 @@ void mir_spline_c2_derivatives_d(size_t n, const double* x, const double* y, dou
 void mir_spline_c2_derivatives_s(size_t n, const float* x, const float* y, float* d);
 void mir_spline_eval_d(size_t n, const double* x, const double* y, const double* d, double t, double* out3);
 void mir_spline_eval_s(size_t n, const float* x, const float* y, const float* d, float t, float* out3);
+
+/* fitSpline on DEVICE-RESIDENT points (csrc/fit_spline_gpu.hip): the same fit through the GPU-native contract of part 2. The
+ * residual function is a set of kernels (csrc/fit_spline_kernels.h) behind the library's own f, fb and -- double --
+ * fbRowMajorDiff callbacks with MIR_LSQ_DEVICE_CALLBACKS | MIR_LSQ_FD_BASE_POINT, instead of a single-threaded host pass over
+ * all points per evaluation: what a caller with 1e5 .. 1e6 scattered samples and 16 .. 256 knots uses. points: DEVICE,
+ * npoints x 2 row-major; x, l, u, splineY, splineD: HOST, as above. Same start (splineY = 0), same m, same quirks, same
+ * MIR_FIT_SPLINE_* codes and TOO_FEW_POINTS rule as mir_fit_spline_*; npoints == 0 is BAD_ARGUMENT. There is no `dist`
+ * (a host function cannot run in a kernel: callers who replace a - b keep mir_fit_spline_*). From `options` (may be NULL) the
+ * entry takes stream (NULL: a stream of its own), workspace, stats / stats_size, trace, variant and the MIR_LSQ_TIME_KERNELS
+ * flag; options with comm, fb, fbContext, fbRowMajor or fbRowMajorDiff set are BAD_ARGUMENT (the callbacks are the entry's own;
+ * row-sharded fits are out of scope: the penalty row belongs to one rank). Every argument check comes before the first HIP
+ * call. The residuals are, bit for bit, those of mir_fit_spline_residuals_d (one statement of the arithmetic for host and
+ * device, csrc/spline_c2.h). */
+int mir_fit_spline_gpu_d(const mir_least_squares_settings_d* settings, size_t npoints, const double* points, size_t nx,
+                         const double* x, const double* l, const double* u, double lambda, const mir_lsq_gpu_options* options,
+                         double* splineY, double* splineD, mir_least_squares_result_d* result);
+int mir_fit_spline_gpu_s(const mir_least_squares_settings_s* settings, size_t npoints, const float* points, size_t nx,
+                         const float* x, const float* l, const float* u, float lambda, const mir_lsq_gpu_options* options,
+                         float* splineY, float* splineD, mir_least_squares_result_s* result);
+/* Values of a spline in Hermite form (x, y, d: HOST, n >= 1 knots) at count abscissae t (DEVICE) -> out (DEVICE): the value
+ * mir_spline_eval_* gives, bit for bit; no derivatives. Enqueued on `stream` (NULL = default stream); the call owns its per-row
+ * scratch and synchronises the stream before it frees it. Returns 0, -1 (arguments), -2 (no device), -3 (allocation), -5
+ * (a copy or launch failed). */
+int mir_spline_eval_gpu_d(size_t n, const double* x, const double* y, const double* d, size_t count, const double* t,
+                          double* out, void* stream);
+int mir_spline_eval_gpu_s(size_t n, const float* x, const float* y, const float* d, size_t count, const float* t,
+                          float* out, void* stream);
+/* Unit-level access (tests): the per-fit setup of mir_fit_spline_gpu_* and then exactly the callback a solve would call, on the
+ * p value vectors X (HOST, p x nx; uploaded). mode 0: fb -> out (HOST) p x m point-major; mode 1: fbRowMajorDiff, p = 2 nx or
+ * 2 nx + 1 -> out m x nx row-major differences, then the m residuals of the last vector when p = 2 nx + 1 (the GPU entry:
+ * double only). m = npoints + (lambda == 0). _gpu_eval: points DEVICE; _eval_host: points HOST, the same statements of
+ * csrc/spline_c2.h on the CPU, no device needed. mir_fit_spline_factor_*: the factor of the knots the callbacks share,
+ * F[5 nx] = [di | up | up2 | f | swap], swap[i] = 1 where elimination step i exchanged rows (all 0 for nx < 4: closed forms).
+ * Return 0, -1 (arguments), -2 (no device), -3 (allocation), -5 (a copy or launch failed). */
+int mir_fit_spline_gpu_eval_d(size_t npoints, const double* points, size_t nx, const double* x, double lambda, size_t p,
+                              const double* X, int mode, double* out);
+int mir_fit_spline_gpu_eval_s(size_t npoints, const float* points, size_t nx, const float* x, float lambda, size_t p,
+                              const float* X, int mode, float* out);
+int mir_fit_spline_eval_host_d(size_t npoints, const double* points, size_t nx, const double* x, double lambda, size_t p,
+                               const double* X, int mode, double* out);
+int mir_fit_spline_eval_host_s(size_t npoints, const float* points, size_t nx, const float* x, float lambda, size_t p,
+                               const float* X, int mode, float* out);
+int mir_fit_spline_factor_d(size_t nx, const double* x, double* F);
+int mir_fit_spline_factor_s(size_t nx, const float* x, float* F);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ __all__ = [
     "VARIANT_SOLVE_BOUNDED", "VARIANT_DEBUG_SOLVE", "VARIANT_HOST_PROFILE", "VARIANT_SOLVE_GENERIC", "VARIANT_SOLVE_ONE_WORKGROUP", "VARIANT_DEBUG_HELPERS_ABSENT", "VARIANT_FD_HOST_COLUMNS",
     "VARIANT_NO_PIPELINE", "FD_BASE_POINT", "VARIANT_NO_FD_BASE_POINT", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA", "BATCHED_BOUNDS_PER_PROBLEM",
     "covariance", "spdInverse", "COVARIANCE_ABSOLUTE_SIGMA",
+    "fitSplineGpu", "splineEvalGpu", "fit_spline_eval_gpu", "fit_spline_eval_host", "fit_spline_factor",
 ]
 
 MODEL_EXP_DECAY = 0      # n = 3: p0 exp(-t p1) + p2
@@ -399,6 +400,21 @@ def lib():
             getattr(L, "mir_spline_c2_derivatives_" + suf).argtypes = [sz, C.c_void_p, C.c_void_p, C.c_void_p]
             getattr(L, "mir_spline_eval_" + suf).argtypes = [sz, C.c_void_p, C.c_void_p, C.c_void_p, ct, C.c_void_p]
         L.mir_fit_spline_residuals_d.argtypes = [sz, C.c_void_p, sz, C.c_void_p, C.c_double, C.c_void_p, sz, C.c_void_p]
+        for suf, S, R, ct in (("d", _Sd, _Rd, C.c_double), ("s", _Ss, _Rs, C.c_float)):
+            fn = getattr(L, "mir_fit_spline_gpu_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [C.POINTER(S), sz, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, ct, C.POINTER(GpuOptions),
+                           C.c_void_p, C.c_void_p, C.POINTER(R)]
+            fn = getattr(L, "mir_spline_eval_gpu_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [sz, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p]
+            for name in ("mir_fit_spline_gpu_eval_", "mir_fit_spline_eval_host_"):
+                fn = getattr(L, name + suf)
+                fn.restype = C.c_int
+                fn.argtypes = [sz, C.c_void_p, sz, C.c_void_p, ct, sz, C.c_void_p, C.c_int, C.c_void_p]
+            fn = getattr(L, "mir_fit_spline_factor_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [sz, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -1182,3 +1198,133 @@ def fitSpline(settings, points, x, l, u, lambda_=0.0, dtype=np.float64):
     if res.status < 0:
         raise LeastSquaresException(int(res.status), res)
     return FitSplineResult(res, Spline(x, y, dtype))
+
+
+# ---- fitSpline on device-resident points (csrc/fit_spline_gpu.hip): the residuals as kernels -------------------------
+
+def fitSplineGpu(settings, points, x, l, u, lambda_=0.0, dtype=np.float64, stats=None, variant=0, stream=None):
+    """fitSpline through the GPU-native contract (mir_fit_spline_gpu_*): `points` is a numpy array (k x 2, uploaded) or a
+    DeviceBuffer of that shape and dtype; everything else, the result and the exceptions are those of fitSpline. stats: an
+    optional Stats to fill (kernels are event-timed then), variant: MIR_LSQ_VARIANT_* bits, stream: an optional Stream."""
+    L = lib()
+    x = np.ascontiguousarray(x, dtype=dtype)
+    lo = np.ascontiguousarray(l, dtype=dtype)
+    up = np.ascontiguousarray(u, dtype=dtype)
+    if not lambda_ >= 0:
+        raise ValueError("fitSpline: lambda has to be non-negative")
+    own = not isinstance(points, DeviceBuffer)
+    if own:
+        points = np.ascontiguousarray(points, dtype=dtype)
+        if points.ndim != 2 or points.shape[1] != 2:
+            raise ValueError("fitSplineGpu: points has to be k x 2")
+        k = points.shape[0]
+        if k < x.size and lambda_ == 0:
+            raise Exception("fitSpline: points.length has to be greater or equal x.length when lambda is 0.0")
+        if k == 0:
+            raise ValueError("fitSpline: bad argument")
+        dev = DeviceBuffer(points)
+    else:
+        dev = points
+        if len(dev.shape) != 2 or dev.shape[1] != 2 or dev.dtype != np.dtype(dtype):
+            raise ValueError("fitSplineGpu: points has to be a k x 2 DeviceBuffer of the fit's dtype")
+        k = dev.shape[0]
+    opt = GpuOptions(variant=variant)
+    if stats is not None:
+        opt.stats = C.pointer(stats)
+        opt.flags = TIME_KERNELS
+    if stream is not None:
+        opt.stream = stream.handle
+    y = np.zeros(x.size, dtype=dtype)
+    d = np.zeros(x.size, dtype=dtype)
+    dbl = dtype == np.float64
+    raw = (_Rd if dbl else _Rs)()
+    fn = L.mir_fit_spline_gpu_d if dbl else L.mir_fit_spline_gpu_s
+    try:
+        rc = fn(C.byref(settings) if settings is not None else None, k, dev.ptr, x.size, x.ctypes.data, lo.ctypes.data,
+                up.ctypes.data, lambda_, C.byref(opt), y.ctypes.data, d.ctypes.data, C.byref(raw))
+    finally:
+        if own:
+            dev.free()
+    if rc == 1:
+        raise Exception("fitSpline: points.length has to be greater or equal x.length when lambda is 0.0")
+    if rc != 0:
+        raise ValueError("fitSpline: bad argument")
+    res = LeastSquaresResult(raw)
+    if res.status < 0:
+        raise LeastSquaresException(int(res.status), res)
+    return FitSplineResult(res, Spline(x, y, dtype))
+
+
+def splineEvalGpu(spline, t, stream=None):
+    """Values of a Spline at many abscissae on the device (mir_spline_eval_gpu_*): t is a numpy array (uploaded; a numpy array
+    of its shape comes back) or a 1-D DeviceBuffer of the spline's dtype (a DeviceBuffer comes back)."""
+    dtype = spline.dtype
+    suf = "d" if dtype == np.float64 else "s"
+    own = not isinstance(t, DeviceBuffer)
+    if own:
+        ta = np.ascontiguousarray(t, dtype=dtype)
+        shape = ta.shape
+        if ta.size == 0:
+            return np.zeros(shape, dtype=dtype)
+        dt = DeviceBuffer(ta.ravel())
+    else:
+        dt = t
+        if dt.dtype != np.dtype(dtype):
+            raise ValueError("splineEvalGpu: t has to have the spline's dtype")
+    count = int(np.prod(dt.shape))
+    out = DeviceBuffer(nbytes=count * np.dtype(dtype).itemsize, dtype=dtype, shape=(count,))
+    rc = getattr(lib(), "mir_spline_eval_gpu_" + suf)(spline.x.size, spline.x.ctypes.data, spline.values.ctypes.data,
+                                                       spline.derivatives.ctypes.data, count, dt.ptr, out.ptr,
+                                                       stream.handle if stream is not None else None)
+    if rc != 0:
+        raise RuntimeError(f"mir_spline_eval_gpu_{suf} failed: {rc}")
+    if not own:
+        return out
+    v = out.download().reshape(shape)
+    out.free()
+    dt.free()
+    return v
+
+
+def _fit_spline_eval(name, points_ptr, npoints, x, lambda_, X, mode, dtype):
+    x = np.ascontiguousarray(x, dtype=dtype)
+    X = np.ascontiguousarray(X, dtype=dtype).reshape(-1, x.size)
+    p, nx = X.shape
+    m = npoints + (1 if lambda_ == 0 else 0)
+    out = np.zeros(p * m if mode == 0 else m * nx + (m if p == 2 * nx + 1 else 0), dtype=dtype)
+    suf = "d" if dtype == np.float64 else "s"
+    rc = getattr(lib(), name + suf)(npoints, points_ptr, nx, x.ctypes.data, lambda_, p, X.ctypes.data, mode, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"{name}{suf} failed: {rc}")
+    return out.reshape(p, m) if mode == 0 else out
+
+
+def fit_spline_eval_host(points, x, lambda_, X, mode=0, dtype=np.float64):
+    """mir_fit_spline_eval_host_*: the residual callbacks of fitSplineGpu on the CPU (the shared arithmetic of
+    csrc/spline_c2.h). X: p value vectors. mode 0: the p x m residual vectors; mode 1 (p = 2 nx or 2 nx + 1): the flat
+    m x nx difference panel, followed by the m residuals of the last vector when p = 2 nx + 1."""
+    points = np.ascontiguousarray(points, dtype=dtype)
+    return _fit_spline_eval("mir_fit_spline_eval_host_", points.ctypes.data, points.shape[0], x, lambda_, X, mode, dtype)
+
+
+def fit_spline_eval_gpu(points, x, lambda_, X, mode=0, dtype=np.float64):
+    """mir_fit_spline_gpu_eval_*: the per-fit setup of fitSplineGpu and then exactly the callback a solve would call (mode 0:
+    fb, mode 1: fbRowMajorDiff, double). points: numpy (uploaded) or a k x 2 DeviceBuffer. Results as fit_spline_eval_host."""
+    own = not isinstance(points, DeviceBuffer)
+    dev = DeviceBuffer(np.ascontiguousarray(points, dtype=dtype)) if own else points
+    try:
+        return _fit_spline_eval("mir_fit_spline_gpu_eval_", dev.ptr, dev.shape[0], x, lambda_, X, mode, dtype)
+    finally:
+        if own:
+            dev.free()
+
+
+def fit_spline_factor(x, dtype=np.float64):
+    """mir_fit_spline_factor_*: the factor of the knots' not-a-knot system as a dict of its five arrays (di, up, up2, f after
+    the elimination; swap[i] = 1 where step i exchanged rows)."""
+    x = np.ascontiguousarray(x, dtype=dtype)
+    F = np.zeros(5 * x.size, dtype=dtype)
+    rc = getattr(lib(), "mir_fit_spline_factor_" + ("d" if dtype == np.float64 else "s"))(x.size, x.ctypes.data, F.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"mir_fit_spline_factor failed: {rc}")
+    return dict(zip(("di", "up", "up2", "f", "swap"), F.reshape(5, x.size)))

@@ -15,6 +15,7 @@
 //   covariance.hip       Solver<T>::covariance(): one refresh at x, J^T J, its inverse (launch_spd_inverse.hip) -> covariance
 //   batched.hip, batched_d.hip   one-wavefront-per-problem batched fits in float / double: the two instances of batched_host.h
 //   comm.hip             row-shard communicators;  unit_entries.hip
+//   fit_spline.cpp, fit_spline_gpu.hip   fitSpline, a caller of the path: host callbacks / its residuals as kernels (device points)
 //
 // There is NO CPU fallback: without a usable HIP device the solve entry points print a diagnostic and return
 // status = numericError.

@@ -1,7 +1,8 @@
 // unit_entries.hip -- unit-level access to the kernels of the path (parity tests, micro-benchmarks) and the standalone
 // BOXCQP entry: mir_solve_box_qp_gpu_* (boxcqp.d:85-102 is D-only), mir_lsq_jtj_*, mir_lsq_fd_jtj_d, mir_lsq_fd_diff_jtj_d,
-// mir_lsq_selftest_reductions. Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
+// mir_lsq_selftest_reductions, mir_fit_spline_gpu_eval_* / _eval_host_* / _factor_* (fit_spline_gpu.hip). Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
 #include "driver.h"
+#include "fit_spline_gpu.h"
 #include "misc_kernels.h"
 
 using namespace mirlsq;
@@ -210,5 +211,29 @@ int mir_lsq_selftest_reductions(int rounds, int mismatches[4])
     (void)hipFree(d);
     return ok ? 0 : -4;
 }
+
+// the callbacks of mir_fit_spline_gpu_* one call at a time, their host twins and the knots' factor (fit_spline_gpu.hip)
+int mir_fit_spline_gpu_eval_d(size_t npoints, const double* points, size_t nx, const double* x, double lambda, size_t p,
+                              const double* X, int mode, double* out)
+{
+    return spline_gpu::callback_eval<double>(npoints, points, nx, x, lambda, p, X, mode, out);
+}
+int mir_fit_spline_gpu_eval_s(size_t npoints, const float* points, size_t nx, const float* x, float lambda, size_t p,
+                              const float* X, int mode, float* out)
+{
+    return spline_gpu::callback_eval<float>(npoints, points, nx, x, lambda, p, X, mode, out);
+}
+int mir_fit_spline_eval_host_d(size_t npoints, const double* points, size_t nx, const double* x, double lambda, size_t p,
+                               const double* X, int mode, double* out)
+{
+    return spline_gpu::host_eval<double>(npoints, points, nx, x, lambda, p, X, mode, out);
+}
+int mir_fit_spline_eval_host_s(size_t npoints, const float* points, size_t nx, const float* x, float lambda, size_t p,
+                               const float* X, int mode, float* out)
+{
+    return spline_gpu::host_eval<float>(npoints, points, nx, x, lambda, p, X, mode, out);
+}
+int mir_fit_spline_factor_d(size_t nx, const double* x, double* F) { return spline_gpu::factor<double>(nx, x, F); }
+int mir_fit_spline_factor_s(size_t nx, const float* x, float* F) { return spline_gpu::factor<float>(nx, x, F); }
 
 }  // extern "C"
