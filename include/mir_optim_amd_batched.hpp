@@ -165,157 +165,18 @@ template <class Model> struct BasisTable {
     }
 };
 
-template <class Model>
-void enqueue_covariance(const batched_settings_t<Model>* S, size_t count, size_t m, const batched_value_t<Model>* x,
-                        const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
-                        size_t t_stride, const batched_value_t<Model>* data, const batched_result_t<Model>* results,
-                        const batched_value_t<Model>* table, uint32_t variant, const mir_lsq_batched_extras& e, hipStream_t stream)
+// THE launch of a kernel with `lds` bytes of dynamic LDS: above the 48 KB a kernel may take by default its limit is raised first
+// (at or below it no attribute call is made). false: the limit could not be raised and nothing was launched.
+template <class Kernel, class... Args>
+bool launch_kernel(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args)
 {
-    using T = batched_value_t<Model>;
-    mirlsq::BatchedCovArgs<T> c{};
-    c.jacobianEpsilon = S->jacobianEpsilon;
-    c.count = (int)count; c.m = (int)m; c.t = t; c.t_stride = (int)t_stride; c.data = data; c.x = x; c.lower = lower; c.upper = upper;
-    c.results = reinterpret_cast<const mirlsq::BatchedResult<T>*>(results);
-    c.basis = table;
-    c.weights = static_cast<const T*>(e.weights); c.w_stride = (int)e.weight_stride;
-    c.variant = variant; c.flags = e.flags;
-    c.cov = static_cast<T*>(e.covariance);
-    c.b_stride = bound_stride<Model>(e);
-    hipLaunchKernelGGL(mirlsq::k_batched_covariance<Model>, dim3((unsigned)count), dim3(64), 0, stream, c);
-}
-}  // namespace detail
-
-namespace detail {
-// the k_lm_batched instance of a model: weighted or not, with the bounded step or without
-template <class Model, class Bounds>
-bool enqueue_fit(const mirlsq::BatchedArgs<batched_value_t<Model>>& a, bool weighted, size_t lds, hipStream_t stream)
-{
-    // the host picks the instance: weighted or not, one box for the batch or a row per problem
-    auto kern = a.b_stride ? (weighted ? mirlsq::k_lm_batched<Model, true, Bounds, true> : mirlsq::k_lm_batched<Model, false, Bounds, true>)
-                           : (weighted ? mirlsq::k_lm_batched<Model, true, Bounds> : mirlsq::k_lm_batched<Model, false, Bounds>);
     if (lds > 48 * 1024
         && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return false;
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.count), dim3(64), lds, stream, a);
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
     return true;
 }
-
-// launch_batched and launch_batched_bounded but for the fit kernel itself: enqueue(args, weighted, lds, stream) -> false when
-// the launch could not be made (the C entries of the library hand in the instances of another translation unit)
-template <class Model, class Enqueue>
-int launch_batched_with(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
-                        const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
-                        size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
-                        const mir_lsq_batched_options* opt, const mir_lsq_batched_extras* extras, Enqueue&& enqueue)
-{
-    using namespace mirlsq;
-    using T = batched_value_t<Model>;
-    static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "Model::value_type: float or double");
-    static_assert(Model::n >= 1 && Model::n <= kBatchedNMax, "1 <= n <= 8: one matrix row per lane of a group of eight");
-    static_assert(Model::nb >= 0, "nb: number of per-row basis values");
-    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
-    static_assert(sizeof(BatchedResult<T>) == sizeof(batched_result_t<Model>), "the kernel writes the C result records in place");
-    static_assert(offsetof(BatchedResult<T>, residual) == offsetof(batched_result_t<Model>, residual)
-                  && offsetof(BatchedResult<T>, lambda) == offsetof(batched_result_t<Model>, lambda), "same layout as the C record");
-    mir_lsq_batched_extras e;
-    if (!detail::batched_extras(extras, m, e)) return -1;
-    if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
-    if (count == 0) return 0;
-    const size_t lds = batched_lds_bytes<Model>(m);
-    if (m == 0 || lds > kBatchedLdsLimit) return -3;
-    hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
-    BatchedArgs<T> a{};
-    a.set = lm_settings_dev(S);
-    a.maxIterations = S->maxIterations; a.maxAge = S->maxAge;
-    a.count = (int)count; a.m = (int)m; a.t_stride = (int)t_stride;
-    a.variant = opt ? opt->variant : 0;
-    a.timing = opt ? opt->timing : nullptr;
-    a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
-    a.results = reinterpret_cast<BatchedResult<T>*>(results);
-    a.weights = static_cast<const T*>(e.weights); a.w_stride = (int)e.weight_stride;
-    a.b_stride = detail::bound_stride<Model>(e);
-    detail::BasisTable<Model> basis;
-    if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
-    a.basis = basis.table;
-    if (!enqueue(a, e.weights != nullptr, lds, stream)) {
-        (void)basis.release(stream, hipSuccess);
-        return -5;
-    }
-    if (e.covariance)
-        detail::enqueue_covariance<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, a.variant, e, stream);
-    const hipError_t err = basis.release(stream, hipGetLastError());
-    return err == hipSuccess ? 0 : -5;
-}
 }  // namespace detail
-
-// Returns 0, or: -1 bad arguments, -3 a problem does not fit its workgroup's LDS, -4 allocation of the basis table failed,
-// -5 the launch failed. Does not synchronise (except in the documented hipMalloc fallback of the basis table).
-// A float model takes the _s records and float arrays, a double model the _d records and double arrays.
-// extras (optional): per-row weights and / or the covariance of the fitted parameters, DEVICE pointers (see the top of this file).
-// It instantiates the default kernels of the model only: with MIR_LSQ_BATCHED_DEVICE_BOUNDS in options->variant it returns -1
-// (call launch_batched_bounded).
-template <class Model>
-int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
-                   const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
-                   size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
-                   const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
-{
-    if (opt && (opt->variant & MIR_LSQ_BATCHED_DEVICE_BOUNDS)) return -1;
-    return detail::launch_batched_with<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, opt, extras,
-                                              detail::enqueue_fit<Model, mirlsq::BatchedNoBoundedStep>);
-}
-
-// launch_batched with the BOUNDED instance of the model's kernel (csrc/batched_bounded.h): a damped step that leaves the box is
-// replaced, inside the kernel, by the solution of the reference's box QP (least_squares.d:1074-1085, boxcqp.d:122-379 with
-// settings->qpSettings), so no problem returns -100; a QP that does not end as solved ends its fit with numericError (-26), as
-// in the reference. Same arguments and return codes; MIR_LSQ_BATCHED_DEVICE_BOUNDS in options->variant is accepted and not
-// needed. A problem whose steps stay inside the box takes the steps, bit for bit, of launch_batched.
-template <class Model>
-int launch_batched_bounded(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
-                           const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
-                           size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
-                           const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
-{
-    return detail::launch_batched_with<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, opt, extras,
-                                              detail::enqueue_fit<Model, mirlsq::BatchedBoxQpStep>);
-}
-
-// The covariance of the fitted parameters on its own: x (count x n) and results (the fit's records: status and residual are
-// read) as a launch_batched left them -- or as the caller completed them for the -100 problems -- give extras->covariance
-// (required; count x n x n values). Device pointers, enqueued on options->stream; the same return codes as launch_batched.
-template <class Model>
-int launch_batched_covariance(const batched_settings_t<Model>* S, size_t count, size_t m, const batched_value_t<Model>* x,
-                              const batched_value_t<Model>* lower, const batched_value_t<Model>* upper,
-                              const batched_value_t<Model>* t, size_t t_stride, const batched_value_t<Model>* data,
-                              const batched_result_t<Model>* results, const mir_lsq_batched_options* opt,
-                              const mir_lsq_batched_extras* extras)
-{
-    using namespace mirlsq;
-    static_assert(Model::n >= 1 && Model::n <= kBatchedNMax, "1 <= n <= 8: one matrix row per lane of a group of eight");
-    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
-    mir_lsq_batched_extras e;
-    if (!extras || !detail::batched_extras(extras, m, e) || !e.covariance) return -1;
-    if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
-    if (count == 0) return 0;
-    if (m == 0) return -3;
-    hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
-    detail::BasisTable<Model> basis;
-    if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
-    detail::enqueue_covariance<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, opt ? opt->variant : 0, e, stream);
-    const hipError_t err = basis.release(stream, hipGetLastError());
-    return err == hipSuccess ? 0 : -5;
-}
-
-// the residual vector of ONE problem, y_i = eval(t_i, basis_i, x) - data_i -- times w_i when `weights` (the problem's m values)
-// is given -- as a kernel launch on device pointers: what a caller hands to the general solver as its device callback when a
-// batched problem comes back with status -100 (float or double, as the model is: mir_optimize_least_squares_gpu_s / _d)
-template <class Model>
-void launch_model_residual(const batched_value_t<Model>* t, const batched_value_t<Model>* data, const batched_value_t<Model>* x,
-                           batched_value_t<Model>* y, size_t m, hipStream_t stream, const batched_value_t<Model>* weights = nullptr)
-{
-    hipLaunchKernelGGL(mirlsq::k_batched_model_eval<Model>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, t, data, x, y, (int)m,
-                       weights);
-}
 
 // ---- 9 <= n <= 16, double: k_lm_batched16 (mir_optim_amd/csrc/batched16_kernel.h) --------------------------------------------
 // LDS bytes one problem needs at m rows: J with a row stride of 16, y, the trial residual, the 16 x 16 J^T J tile and J^T y.
@@ -334,99 +195,229 @@ constexpr size_t batched16_covariance_lds_bytes(size_t m)
 }
 
 namespace detail {
-// The kernels a launch_batched16 may enqueue: every instance of the model. (The library's entries without extras hand in a
-// set with the unweighted fit alone, so that their translation unit compiles the device code it always compiled.)
+// A launch takes its kernel instances from a policy class `Kernels`:
+//     static bool fit(const BatchedArgs<T>&, bool weighted, size_t lds, hipStream_t);      false: the launch could not be made
+//     static bool covariance(const BatchedCovArgs<T>&, size_t lds, hipStream_t);
+// These two are every instance of a model; the library's translation units have policies of their own, which forward what they
+// do not compile to the unit that does (mir_optim_amd/csrc/batched_host.h), so that each unit compiles the device code it
+// always compiled.
+// n <= 8: k_lm_batched, weighted or not, with the bounded step (Bounds = BatchedBoxQpStep) or without
+template <class Model, class Bounds> struct BatchedKernels {
+    using T = batched_value_t<Model>;
+    static bool fit(const mirlsq::BatchedArgs<T>& a, bool weighted, size_t lds, hipStream_t stream)
+    {
+        // the host picks the instance: weighted or not, one box for the batch or a row per problem
+        auto kern = a.b_stride ? (weighted ? mirlsq::k_lm_batched<Model, true, Bounds, true> : mirlsq::k_lm_batched<Model, false, Bounds, true>)
+                               : (weighted ? mirlsq::k_lm_batched<Model, true, Bounds> : mirlsq::k_lm_batched<Model, false, Bounds>);
+        return launch_kernel(kern, dim3((unsigned)a.count), dim3(64), lds, stream, a);
+    }
+    static bool covariance(const mirlsq::BatchedCovArgs<T>& c, size_t lds, hipStream_t stream)
+    {
+        return launch_kernel(mirlsq::k_batched_covariance<Model>, dim3((unsigned)c.count), dim3(64), lds, stream, c);
+    }
+};
+// 9 <= n <= 16: k_lm_batched16 (bounds always handled in the kernel)
 template <class Model> struct Batched16Kernels {
     static bool fit(const mirlsq::BatchedArgs<double>& a, bool weighted, size_t lds, hipStream_t stream)
     {
         auto kern = weighted ? mirlsq::k_lm_batched16<Model, true> : mirlsq::k_lm_batched16<Model, false>;   // the host picks the instance
-        if (lds > 48 * 1024
-            && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return false;
-        hipLaunchKernelGGL(kern, dim3((unsigned)a.count), dim3(64), lds, stream, a);
-        return true;
+        return launch_kernel(kern, dim3((unsigned)a.count), dim3(64), lds, stream, a);
     }
     static bool covariance(const mirlsq::BatchedCovArgs<double>& c, size_t lds, hipStream_t stream)
     {
-        auto kern = mirlsq::k_batched16_covariance<Model>;
-        if (lds > 48 * 1024
-            && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return false;
-        hipLaunchKernelGGL(kern, dim3((unsigned)c.count), dim3(64), lds, stream, c);
-        return true;
+        return launch_kernel(mirlsq::k_batched16_covariance<Model>, dim3((unsigned)c.count), dim3(64), lds, stream, c);
     }
 };
 
-template <class Model> constexpr void batched16_model_checks()
-{
-    using namespace mirlsq;
-    static_assert(std::is_same<batched_value_t<Model>, double>::value, "launch_batched16: Model::value_type must be double");
-    static_assert(Model::n >= kBatched16NMin && Model::n <= kBatched16NMax, "9 <= n <= 16 (launch_batched takes n <= 8)");
-    static_assert(Model::nb >= 0, "nb: number of per-row basis values");
-    static_assert(sizeof(BatchedResult<double>) == sizeof(mir_least_squares_result_d)
-                  && offsetof(BatchedResult<double>, residual) == offsetof(mir_least_squares_result_d, residual)
-                  && offsetof(BatchedResult<double>, lambda) == offsetof(mir_least_squares_result_d, lambda),
-                  "the kernel writes the C result records in place");
-}
+// The kernel family ("layout") a model belongs to, by its n: what differs between the two in the host code of a launch.
+template <class Model, bool kWide = (Model::n > mirlsq::kBatchedNMax)> struct BatchedLayout;
+template <class Model> struct BatchedLayout<Model, false> {        // n <= 8: one matrix row per lane of a group of eight
+    using Kernels = BatchedKernels<Model, mirlsq::BatchedNoBoundedStep>;        // the default set: launch_batched
+    // a problem whose step reaches a finite bound may come back with status -100 (unless the bounded instances run), and
+    // k_lm_batched reads mir_lsq_batched_options.timing
+    static constexpr bool needs_general = true, has_timing = true;
+    static constexpr void checks()
+    {
+        using namespace mirlsq;
+        using T = batched_value_t<Model>;
+        static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "Model::value_type: float or double");
+        static_assert(Model::n >= 1 && Model::n <= kBatchedNMax, "1 <= n <= 8: one matrix row per lane of a group of eight");
+        static_assert(Model::nb >= 0, "nb: number of per-row basis values");
+        static_assert(sizeof(BatchedResult<T>) == sizeof(batched_result_t<Model>), "the kernel writes the C result records in place");
+        static_assert(offsetof(BatchedResult<T>, residual) == offsetof(batched_result_t<Model>, residual)
+                      && offsetof(BatchedResult<T>, lambda) == offsetof(batched_result_t<Model>, lambda), "same layout as the C record");
+    }
+    static constexpr size_t fit_lds_bytes(size_t m) { return batched_lds_bytes<Model>(m); }
+    static constexpr size_t covariance_lds_bytes(size_t) { return 0; }
+    static constexpr bool covariance_fits(size_t m) { return m != 0; }
+};
+template <class Model> struct BatchedLayout<Model, true> {         // 9 <= n <= 16, double: the 16-lane-row layout
+    using Kernels = Batched16Kernels<Model>;
+    static constexpr bool needs_general = false, has_timing = false;
+    static constexpr void checks()
+    {
+        using namespace mirlsq;
+        static_assert(std::is_same<batched_value_t<Model>, double>::value, "launch_batched16: Model::value_type must be double");
+        static_assert(Model::n >= kBatched16NMin && Model::n <= kBatched16NMax, "9 <= n <= 16 (launch_batched takes n <= 8)");
+        static_assert(Model::nb >= 0, "nb: number of per-row basis values");
+        static_assert(sizeof(BatchedResult<double>) == sizeof(mir_least_squares_result_d)
+                      && offsetof(BatchedResult<double>, residual) == offsetof(mir_least_squares_result_d, residual)
+                      && offsetof(BatchedResult<double>, lambda) == offsetof(mir_least_squares_result_d, lambda),
+                      "the kernel writes the C result records in place");
+    }
+    static constexpr size_t fit_lds_bytes(size_t m) { return batched16_lds_bytes<Model>(m); }
+    static constexpr size_t covariance_lds_bytes(size_t m) { return batched16_covariance_lds_bytes(m); }
+    static constexpr bool covariance_fits(size_t m) { return m != 0 && fit_lds_bytes(m) <= kBatchedLdsLimit; }   // the fit's limit: the records come from one
+};
 
-template <class Model, class Kernels>
-bool enqueue_covariance16(const mir_least_squares_settings_d* S, size_t count, size_t m, const double* x, const double* lower,
-                          const double* upper, const double* t, size_t t_stride, const double* data,
-                          const mir_least_squares_result_d* results, const double* table, uint32_t variant,
-                          const mir_lsq_batched_extras& e, hipStream_t stream)
+// the arguments of the fit kernel; timing: mir_lsq_batched_options.timing where the kernel reads it (k_lm_batched), else nullptr
+template <class Model, class T = batched_value_t<Model>>
+mirlsq::BatchedArgs<T> fit_args(const batched_settings_t<Model>* S, size_t count, size_t m, T* x, const T* lower, const T* upper, const T* t,
+                                size_t t_stride, const T* data, batched_result_t<Model>* results, const T* table, uint32_t variant,
+                                uint64_t* timing, const mir_lsq_batched_extras& e)
 {
-    mirlsq::BatchedCovArgs<double> c{};
+    mirlsq::BatchedArgs<T> a{};
+    a.set = mirlsq::lm_settings_dev(S);
+    a.maxIterations = S->maxIterations; a.maxAge = S->maxAge;
+    a.count = (int)count; a.m = (int)m; a.t_stride = (int)t_stride;
+    a.variant = variant;
+    a.timing = timing;
+    a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
+    a.results = reinterpret_cast<mirlsq::BatchedResult<T>*>(results);
+    a.weights = static_cast<const T*>(e.weights); a.w_stride = (int)e.weight_stride;
+    a.b_stride = bound_stride<Model>(e);
+    a.basis = table;
+    return a;
+}
+// the arguments of the covariance kernel
+template <class Model, class T = batched_value_t<Model>>
+mirlsq::BatchedCovArgs<T> cov_args(const batched_settings_t<Model>* S, size_t count, size_t m, const T* x, const T* lower, const T* upper,
+                                   const T* t, size_t t_stride, const T* data, const batched_result_t<Model>* results, const T* table,
+                                   uint32_t variant, const mir_lsq_batched_extras& e)
+{
+    mirlsq::BatchedCovArgs<T> c{};
     c.jacobianEpsilon = S->jacobianEpsilon;
     c.count = (int)count; c.m = (int)m; c.t = t; c.t_stride = (int)t_stride; c.data = data; c.x = x; c.lower = lower; c.upper = upper;
-    c.results = reinterpret_cast<const mirlsq::BatchedResult<double>*>(results);
+    c.results = reinterpret_cast<const mirlsq::BatchedResult<T>*>(results);
     c.basis = table;
-    c.weights = static_cast<const double*>(e.weights); c.w_stride = (int)e.weight_stride;
+    c.weights = static_cast<const T*>(e.weights); c.w_stride = (int)e.weight_stride;
     c.variant = variant; c.flags = e.flags;
-    c.cov = static_cast<double*>(e.covariance);
+    c.cov = static_cast<T*>(e.covariance);
     c.b_stride = bound_stride<Model>(e);
-    return Kernels::covariance(c, batched16_covariance_lds_bytes(m), stream);
+    return c;
 }
 
-// launch_batched16 but for the kernels themselves (Kernels::fit / ::covariance -> false when the launch could not be made)
-template <class Model, class Kernels>
-int launch_batched16_with(const mir_least_squares_settings_d* S, size_t count, size_t m, double* x, const double* lower,
-                          const double* upper, const double* t, size_t t_stride, const double* data,
-                          mir_least_squares_result_d* results, const mir_lsq_batched_options* opt, const mir_lsq_batched_extras* extras)
+// THE launch of a fit, for the kernels of `Kernels`: the checks, the stream, the basis table, the fit, with extras->covariance the
+// covariance behind it, the release and the return code. The public launch_* below are this with a layout and a kernel set.
+template <class Model, class Kernels, class Layout = BatchedLayout<Model>, class T = batched_value_t<Model>>
+int launch_fit_with(const batched_settings_t<Model>* S, size_t count, size_t m, T* x, const T* lower, const T* upper, const T* t,
+                    size_t t_stride, const T* data, batched_result_t<Model>* results, const mir_lsq_batched_options* opt,
+                    const mir_lsq_batched_extras* extras)
 {
-    using namespace mirlsq;
-    batched16_model_checks<Model>();
-    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
+    Layout::checks();
+    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !mirlsq::batched_has_grad<Model>::value) return -1;
     mir_lsq_batched_extras e;
     if (!batched_extras(extras, m, e)) return -1;
     if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
     if (count == 0) return 0;
-    const size_t lds = batched16_lds_bytes<Model>(m);
+    const size_t lds = Layout::fit_lds_bytes(m);
     if (m == 0 || lds > kBatchedLdsLimit) return -3;
     hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
-    BatchedArgs<double> a{};
-    a.set = lm_settings_dev(S);
-    a.maxIterations = S->maxIterations; a.maxAge = S->maxAge;
-    a.count = (int)count; a.m = (int)m; a.t_stride = (int)t_stride;
-    a.variant = opt ? opt->variant : 0;
-    a.t = t; a.data = data; a.x = x; a.lower = lower; a.upper = upper;
-    a.results = reinterpret_cast<BatchedResult<double>*>(results);
-    a.weights = static_cast<const double*>(e.weights); a.w_stride = (int)e.weight_stride;
-    a.b_stride = bound_stride<Model>(e);
+    const uint32_t variant = opt ? opt->variant : 0;
     BasisTable<Model> basis;
     if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
-    a.basis = basis.table;
-    bool launched = Kernels::fit(a, e.weights != nullptr, lds, stream);
+    bool launched = Kernels::fit(fit_args<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, variant,
+                                                 Layout::has_timing && opt ? opt->timing : nullptr, e),
+                                 e.weights != nullptr, lds, stream);
     if (launched && e.covariance)
-        launched = enqueue_covariance16<Model, Kernels>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, a.variant, e,
-                                                        stream);
-    if (!launched) {
-        (void)basis.release(stream, hipSuccess);
-        return -5;
-    }
-    const hipError_t err = basis.release(stream, hipGetLastError());
+        launched = Kernels::covariance(cov_args<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table, variant, e),
+                                       Layout::covariance_lds_bytes(m), stream);
+    const hipError_t err = basis.release(stream, launched ? hipGetLastError() : hipErrorLaunchFailure);
+    return err == hipSuccess ? 0 : -5;
+}
+
+// THE launch of the covariance kernel on its own, at the x and the records a fit left
+template <class Model, class Kernels, class Layout = BatchedLayout<Model>, class T = batched_value_t<Model>>
+int launch_covariance_with(const batched_settings_t<Model>* S, size_t count, size_t m, const T* x, const T* lower, const T* upper,
+                           const T* t, size_t t_stride, const T* data, const batched_result_t<Model>* results,
+                           const mir_lsq_batched_options* opt, const mir_lsq_batched_extras* extras)
+{
+    Layout::checks();
+    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !mirlsq::batched_has_grad<Model>::value) return -1;
+    mir_lsq_batched_extras e;
+    if (!batched_extras(extras, m, e) || !e.covariance) return -1;          // (no extras: no covariance)
+    if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
+    if (count == 0) return 0;
+    if (!Layout::covariance_fits(m)) return -3;
+    hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
+    BasisTable<Model> basis;
+    if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
+    const bool launched = Kernels::covariance(cov_args<Model>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table,
+                                                              opt ? opt->variant : 0, e),
+                                              Layout::covariance_lds_bytes(m), stream);
+    const hipError_t err = basis.release(stream, launched ? hipGetLastError() : hipErrorLaunchFailure);
     return err == hipSuccess ? 0 : -5;
 }
 }  // namespace detail
+
+// Returns 0, or: -1 bad arguments, -3 a problem does not fit its workgroup's LDS, -4 allocation of the basis table failed,
+// -5 the launch failed. Does not synchronise (except in the documented hipMalloc fallback of the basis table).
+// A float model takes the _s records and float arrays, a double model the _d records and double arrays.
+// extras (optional): per-row weights and / or the covariance of the fitted parameters, DEVICE pointers (see the top of this file).
+// It instantiates the default kernels of the model only: with MIR_LSQ_BATCHED_DEVICE_BOUNDS in options->variant it returns -1
+// (call launch_batched_bounded).
+template <class Model>
+int launch_batched(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
+                   const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
+                   size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
+                   const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
+{
+    if (opt && (opt->variant & MIR_LSQ_BATCHED_DEVICE_BOUNDS)) return -1;
+    using Layout = detail::BatchedLayout<Model, false>;
+    return detail::launch_fit_with<Model, typename Layout::Kernels, Layout>(S, count, m, x, lower, upper, t, t_stride, data, results, opt, extras);
+}
+
+// launch_batched with the BOUNDED instance of the model's kernel (csrc/batched_bounded.h): a damped step that leaves the box is
+// replaced, inside the kernel, by the solution of the reference's box QP (least_squares.d:1074-1085, boxcqp.d:122-379 with
+// settings->qpSettings), so no problem returns -100; a QP that does not end as solved ends its fit with numericError (-26), as
+// in the reference. Same arguments and return codes; MIR_LSQ_BATCHED_DEVICE_BOUNDS in options->variant is accepted and not
+// needed. A problem whose steps stay inside the box takes the steps, bit for bit, of launch_batched.
+template <class Model>
+int launch_batched_bounded(const batched_settings_t<Model>* S, size_t count, size_t m, batched_value_t<Model>* x,
+                           const batched_value_t<Model>* lower, const batched_value_t<Model>* upper, const batched_value_t<Model>* t,
+                           size_t t_stride, const batched_value_t<Model>* data, batched_result_t<Model>* results,
+                           const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
+{
+    return detail::launch_fit_with<Model, detail::BatchedKernels<Model, mirlsq::BatchedBoxQpStep>, detail::BatchedLayout<Model, false>>(
+        S, count, m, x, lower, upper, t, t_stride, data, results, opt, extras);
+}
+
+// The covariance of the fitted parameters on its own: x (count x n) and results (the fit's records: status and residual are
+// read) as a launch_batched left them -- or as the caller completed them for the -100 problems -- give extras->covariance
+// (required; count x n x n values). Device pointers, enqueued on options->stream; the same return codes as launch_batched
+// (-3: m = 0 only).
+template <class Model>
+int launch_batched_covariance(const batched_settings_t<Model>* S, size_t count, size_t m, const batched_value_t<Model>* x,
+                              const batched_value_t<Model>* lower, const batched_value_t<Model>* upper,
+                              const batched_value_t<Model>* t, size_t t_stride, const batched_value_t<Model>* data,
+                              const batched_result_t<Model>* results, const mir_lsq_batched_options* opt,
+                              const mir_lsq_batched_extras* extras)
+{
+    using Layout = detail::BatchedLayout<Model, false>;
+    return detail::launch_covariance_with<Model, typename Layout::Kernels, Layout>(S, count, m, x, lower, upper, t, t_stride, data, results, opt,
+                                                                                   extras);
+}
+
+// the residual vector of ONE problem, y_i = eval(t_i, basis_i, x) - data_i -- times w_i when `weights` (the problem's m values)
+// is given -- as a kernel launch on device pointers: what a caller hands to the general solver as its device callback when a
+// batched problem comes back with status -100 (float or double, as the model is: mir_optimize_least_squares_gpu_s / _d)
+template <class Model>
+void launch_model_residual(const batched_value_t<Model>* t, const batched_value_t<Model>* data, const batched_value_t<Model>* x,
+                           batched_value_t<Model>* y, size_t m, hipStream_t stream, const batched_value_t<Model>* weights = nullptr)
+{
+    hipLaunchKernelGGL(mirlsq::k_batched_model_eval<Model>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, t, data, x, y, (int)m,
+                       weights);
+}
 
 // launch_batched for a double model with 9 to 16 parameters. Same contract: every pointer a DEVICE pointer, enqueued on
 // options->stream, results in place, no synchronisation except in the hipMalloc fallback of the basis table. Returns 0, or -1
@@ -443,8 +434,8 @@ int launch_batched16(const mir_least_squares_settings_d* S, size_t count, size_t
                      const double* t, size_t t_stride, const double* data, mir_least_squares_result_d* results,
                      const mir_lsq_batched_options* opt = nullptr, const mir_lsq_batched_extras* extras = nullptr)
 {
-    return detail::launch_batched16_with<Model, detail::Batched16Kernels<Model>>(S, count, m, x, lower, upper, t, t_stride, data, results,
-                                                                                 opt, extras);
+    using Layout = detail::BatchedLayout<Model, true>;
+    return detail::launch_fit_with<Model, typename Layout::Kernels, Layout>(S, count, m, x, lower, upper, t, t_stride, data, results, opt, extras);
 }
 
 // The covariance of the fitted parameters on its own, the counterpart of launch_batched_covariance: x (count x n) and results
@@ -456,21 +447,8 @@ int launch_batched16_covariance(const mir_least_squares_settings_d* S, size_t co
                                 const mir_least_squares_result_d* results, const mir_lsq_batched_options* opt,
                                 const mir_lsq_batched_extras* extras)
 {
-    using namespace mirlsq;
-    detail::batched16_model_checks<Model>();
-    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !batched_has_grad<Model>::value) return -1;
-    mir_lsq_batched_extras e;
-    if (!extras || !detail::batched_extras(extras, m, e) || !e.covariance) return -1;
-    if (!S || !x || !lower || !upper || !t || !data || !results || (t_stride != 0 && t_stride != m)) return -1;
-    if (count == 0) return 0;
-    if (m == 0 || batched16_lds_bytes<Model>(m) > kBatchedLdsLimit) return -3;       // the fit's limit: the records come from one
-    hipStream_t stream = opt ? static_cast<hipStream_t>(opt->stream) : nullptr;
-    detail::BasisTable<Model> basis;
-    if (const int rc = basis.acquire(opt, t, count, m, t_stride, stream)) return rc;
-    const bool launched = detail::enqueue_covariance16<Model, Kernels>(S, count, m, x, lower, upper, t, t_stride, data, results, basis.table,
-                                                                       opt ? opt->variant : 0, e, stream);
-    const hipError_t err = basis.release(stream, launched ? hipGetLastError() : hipErrorLaunchFailure);
-    return err == hipSuccess ? 0 : -5;
+    return detail::launch_covariance_with<Model, Kernels, detail::BatchedLayout<Model, true>>(S, count, m, x, lower, upper, t, t_stride, data,
+                                                                                              results, opt, extras);
 }
 
 }  // namespace mir_optim_amd

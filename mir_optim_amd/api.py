@@ -19,6 +19,7 @@ import time, and a missing GPU makes every solve return status numericError (nev
 import ctypes as C
 import enum
 import os
+import types
 
 import numpy as np
 
@@ -716,42 +717,56 @@ def optimizeLeastSquaresBatched(model, x, t, data, l=None, u=None, settings=None
     if int(model) in _MODELS16:
         return _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weights, covariance, absolute_sigma)
     suf = _batched_suffix(dtype)
-    dtype = np.float32 if suf == "s" else np.float64
-    L = lib()
+    p = _batched_pack(x, t, data, l, u, settings, np.float32 if suf == "s" else np.float64)
+    if weights is None and not covariance and not absolute_sigma and not p.per_problem:
+        return _batched_call("mir_optimize_least_squares_batched_" + suf, model, p, variant)        # no extras argument: the old entry
+    ex, cov = _batched_extras(p, weights, covariance, absolute_sigma)
+    return _batched_call("mir_optimize_least_squares_batched_ex_" + suf, model, p, variant, C.byref(ex), cov=cov)
+
+
+def _batched_pack(x, t, data, l, u, settings, dtype, check_shapes=False):
+    """The arguments of a batched call as the C entries take them: x (a copy), t, data and the bounds as contiguous arrays of
+    `dtype`, the settings and the result records. check_shapes: x, data and t must agree (ValueError)."""
     x = np.array(x, dtype=dtype, order="C")
-    count, n = x.shape
     data = np.ascontiguousarray(data, dtype=dtype)
-    m = data.shape[1]
     t = np.ascontiguousarray(t, dtype=dtype)
-    t_stride = 0 if t.ndim == 1 else m
+    if check_shapes and (x.ndim != 2 or data.ndim != 2 or data.shape[0] != x.shape[0]):
+        raise ValueError(f"x: count x n and data: count x m, not {x.shape} and {data.shape}")
+    count, n = x.shape
+    m = data.shape[1]
+    if check_shapes and t.shape not in ((m,), (count, m)):
+        raise ValueError(f"t: {m} values or {count} x {m}, not {t.shape}")
     lo, up, per_problem = _batched_bounds(l, u, count, n, dtype)
-    if settings is None:
-        settings = LeastSquaresSettings(dtype)
-    raw = ((_Rs if suf == "s" else _Rd) * count)()
-    if weights is None and not covariance and not absolute_sigma and not per_problem:
-        fn = getattr(L, "mir_optimize_least_squares_batched_" + suf)
-        rc = fn(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data, up.ctypes.data, t.ctypes.data, t_stride,
-                data.ctypes.data, raw, C.byref(BatchedOptions(variant=variant)))
-        if rc != 0:
-            raise RuntimeError(f"mir_optimize_least_squares_batched_{suf} failed: {rc}")
-        return [LeastSquaresResult(r) for r in raw], x
-    ex = BatchedExtras(flags=(BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0) | (BATCHED_BOUNDS_PER_PROBLEM if per_problem else 0))
+    return types.SimpleNamespace(dtype=dtype, x=x, t=t, data=data, count=count, n=n, m=m, t_stride=0 if t.ndim == 1 else m, lo=lo, up=up,
+                                 per_problem=per_problem, settings=LeastSquaresSettings(dtype) if settings is None else settings,
+                                 raw=((_Rs if dtype == np.float32 else _Rd) * count)())
+
+
+def _batched_extras(p, weights, covariance, absolute_sigma):
+    """(BatchedExtras, cov) of a packed call: the flags, the weights (m values or count x m) and the covariance to fill, or None.
+    The extras keep their arrays alive."""
+    ex = BatchedExtras(flags=(BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0) | (BATCHED_BOUNDS_PER_PROBLEM if p.per_problem else 0))
     if weights is not None:
-        weights = np.ascontiguousarray(weights, dtype=dtype)
-        if weights.shape not in ((m,), (count, m)):
-            raise ValueError(f"weights: {m} values or {count} x {m}, not {weights.shape}")
+        ex._weights = weights = np.ascontiguousarray(weights, dtype=p.dtype)
+        if weights.shape not in ((p.m,), (p.count, p.m)):
+            raise ValueError(f"weights: {p.m} values or {p.count} x {p.m}, not {weights.shape}")
         ex.weights = weights.ctypes.data
-        ex.weight_stride = 0 if weights.ndim == 1 else m
-    cov = np.empty((count, n, n), dtype=dtype) if covariance else None
+        ex.weight_stride = 0 if weights.ndim == 1 else p.m
+    cov = np.empty((p.count, p.n, p.n), dtype=p.dtype) if covariance else None
     if covariance:
         ex.covariance = cov.ctypes.data
-    fn = getattr(L, "mir_optimize_least_squares_batched_ex_" + suf)
-    rc = fn(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data, up.ctypes.data, t.ctypes.data, t_stride,
-            data.ctypes.data, raw, C.byref(BatchedOptions(variant=variant)), C.byref(ex))
+    return ex, cov
+
+
+def _batched_call(name, model, p, variant, *extras, cov=None):
+    """Calls the host-pointer entry `name` on a packed call. extras: nothing for an entry without that argument, else the argument
+    (None: a null pointer); cov: the array its covariance points to. Returns (results, x), with cov (results, x, cov)."""
+    rc = getattr(lib(), name)(C.byref(p.settings), p.count, p.m, int(model), p.x.ctypes.data, p.lo.ctypes.data, p.up.ctypes.data,
+                              p.t.ctypes.data, p.t_stride, p.data.ctypes.data, p.raw, C.byref(BatchedOptions(variant=variant)), *extras)
     if rc != 0:
-        raise RuntimeError(f"mir_optimize_least_squares_batched_ex_{suf} failed: {rc}")
-    res = [LeastSquaresResult(r) for r in raw]
-    return (res, x, cov) if covariance else (res, x)
+        raise RuntimeError(f"{name} failed: {rc}")
+    res = [LeastSquaresResult(r) for r in p.raw]
+    return (res, p.x) if cov is None else (res, p.x, cov)
 
 
 def _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weights, covariance, absolute_sigma):
@@ -760,25 +775,10 @@ def _optimize_batched16(model, x, t, data, l, u, settings, variant, dtype, weigh
         raise ValueError(f"the MODEL16_* models are fitted in float64 only, not {np.dtype(dtype)}: pass dtype=np.float64")
     if weights is not None or covariance or absolute_sigma:
         raise ValueError("the MODEL16_* models take neither weights nor covariance here: call optimizeLeastSquaresBatched16")
-    L = lib()
-    x = np.array(x, dtype=np.float64, order="C")
-    count, n = x.shape
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    m = data.shape[1]
-    t = np.ascontiguousarray(t, dtype=np.float64)
-    t_stride = 0 if t.ndim == 1 else m
-    lo, up, per_problem = _batched_bounds(l, u, count, n, np.float64)
-    if settings is None:
-        settings = LeastSquaresSettings(np.float64)
-    raw = (_Rd * count)()
+    p = _batched_pack(x, t, data, l, u, settings, np.float64)
     # 2-D bounds: this entry with an extras that carries the flag and nothing else; 1-D: no extras, as always
-    ex = BatchedExtras(flags=BATCHED_BOUNDS_PER_PROBLEM) if per_problem else None
-    rc = L.mir_optimize_least_squares_batched16_d(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data,
-                                                  up.ctypes.data, t.ctypes.data, t_stride, data.ctypes.data, raw,
-                                                  C.byref(BatchedOptions(variant=variant)), C.byref(ex) if per_problem else None)
-    if rc != 0:
-        raise RuntimeError(f"mir_optimize_least_squares_batched16_d failed: {rc}")
-    return [LeastSquaresResult(r) for r in raw], x
+    ex = BatchedExtras(flags=BATCHED_BOUNDS_PER_PROBLEM) if p.per_problem else None
+    return _batched_call("mir_optimize_least_squares_batched16_d", model, p, variant, C.byref(ex) if p.per_problem else None)
 
 
 def optimizeLeastSquaresBatched16(model, x, t, data, l=None, u=None, settings=None, variant=0, weights=None, covariance=False,
@@ -800,38 +800,9 @@ def optimizeLeastSquaresBatched16(model, x, t, data, l=None, u=None, settings=No
             raise ValueError(f"the MODEL16_* models are fitted in float64 only: {name} is {dt}")
     if weights is None and not covariance and not absolute_sigma:
         return _optimize_batched16(model, x, t, data, l, u, settings, variant, np.float64, None, False, False)
-    L = lib()
-    x = np.array(x, dtype=np.float64, order="C")
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    t = np.ascontiguousarray(t, dtype=np.float64)
-    if x.ndim != 2 or data.ndim != 2 or data.shape[0] != x.shape[0]:
-        raise ValueError(f"x: count x n and data: count x m, not {x.shape} and {data.shape}")
-    count, n = x.shape
-    m = data.shape[1]
-    if t.shape not in ((m,), (count, m)):
-        raise ValueError(f"t: {m} values or {count} x {m}, not {t.shape}")
-    t_stride = 0 if t.ndim == 1 else m
-    lo, up, per_problem = _batched_bounds(l, u, count, n, np.float64)
-    if settings is None:
-        settings = LeastSquaresSettings(np.float64)
-    ex = BatchedExtras(flags=(BATCHED_ABSOLUTE_SIGMA if absolute_sigma else 0) | (BATCHED_BOUNDS_PER_PROBLEM if per_problem else 0))
-    if weights is not None:
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        if weights.shape not in ((m,), (count, m)):
-            raise ValueError(f"weights: {m} values or {count} x {m}, not {weights.shape}")
-        ex.weights = weights.ctypes.data
-        ex.weight_stride = 0 if weights.ndim == 1 else m
-    cov = np.empty((count, n, n), dtype=np.float64) if covariance else None
-    if covariance:
-        ex.covariance = cov.ctypes.data
-    raw = (_Rd * count)()
-    rc = L.mir_optimize_least_squares_batched16_ex_d(C.byref(settings), count, m, int(model), x.ctypes.data, lo.ctypes.data,
-                                                     up.ctypes.data, t.ctypes.data, t_stride, data.ctypes.data, raw,
-                                                     C.byref(BatchedOptions(variant=variant)), C.byref(ex))
-    if rc != 0:
-        raise RuntimeError(f"mir_optimize_least_squares_batched16_ex_d failed: {rc}")
-    res = [LeastSquaresResult(r) for r in raw]
-    return (res, x, cov) if covariance else (res, x)
+    p = _batched_pack(x, t, data, l, u, settings, np.float64, check_shapes=True)
+    ex, cov = _batched_extras(p, weights, covariance, absolute_sigma)
+    return _batched_call("mir_optimize_least_squares_batched16_ex_d", model, p, variant, C.byref(ex), cov=cov)
 
 
 def batched16JtJ(J, y):

@@ -8,6 +8,7 @@ build/obj/ -- in parallel, and only when it or one of the headers IT includes (t
 is newer -- and the objects are linked. A kernel edit costs the translation units that include that kernel's header
 (usually one launch_*.hip), not the library.
 """
+import functools
 import os
 import shutil
 import subprocess
@@ -43,20 +44,20 @@ def _stale(target, sources):
     return any((not os.path.exists(s)) or os.path.getmtime(s) > t for s in sources)
 
 
-def _deps(obj):
-    """The files an object was compiled from, as the compiler recorded them (`-MMD -MF obj.d`): the translation unit and
-    exactly the headers it includes -- an edit of a kernel header recompiles the units that include it and no others."""
-    d = obj[:-2] + ".d"
+def _deps(d, base=""):
+    """The files an object or library was compiled from, as the compiler recorded them (`-MMD -MF d`): the translation unit and
+    exactly the headers it includes -- an edit of a kernel header recompiles what includes it and nothing else. None: no record.
+    base: the directory the compiler ran in, for the relative paths of the record."""
     if not os.path.exists(d):
         return None
     toks = open(d).read().replace("\\\n", " ").split()
-    return [t for t in toks[1:] if not t.endswith(":") and not t.startswith("/opt/") and not t.startswith("/usr/")]
+    return [os.path.join(base, t) for t in toks[1:] if not t.endswith(":") and not t.startswith("/opt/") and not t.startswith("/usr/")]
 
 
-def _run(cmd, verbose):
+def _run(cmd, verbose, cwd=None):
     if verbose:
         print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
+    subprocess.check_call(cmd, cwd=cwd)
 
 
 def _compile_units(units, extra, force, verbose, jobs):
@@ -65,7 +66,7 @@ def _compile_units(units, extra, force, verbose, jobs):
         src = os.path.join(CSRC, u)
         obj = os.path.join(OBJDIR, os.path.splitext(u)[0] + ".o")
         objs.append(obj)
-        deps = _deps(obj)
+        deps = _deps(obj[:-2] + ".d")
         if force or deps is None or _stale(obj, [src] + deps):
             todo.append([_hipcc()] + _FLAGS + extra + ["-MMD", "-MF", obj[:-2] + ".d", "-c", src, "-o", obj])
     if todo:
@@ -98,113 +99,49 @@ if __name__ == "__main__":
     build(force=True, verbose=True)
 
 
+# tests/user_model/<name>.hip: a caller's own residual models, each compiled into tests/user_model/lib<name>.so
+USER_MODEL_DIR = os.path.join(os.path.dirname(HERE), "tests", "user_model")
+USER_MODELS = [
+    "user_model",                 # float models on the batched path and one on the resident-J path
+    "user_model_f64",             # a double model on the batched path
+    "user_model_weighted",        # a weighted fit with covariance
+    "user_model_bounded",         # a fit with binding bounds
+    "user_model_n16",             # models of 9 and 13 parameters on the batched path
+    "user_model_n16_weighted",    # their weighted fits with covariance
+    "user_model_problem_bounds",  # a fit with a box per problem
+]
+
+
+def example_paths(name):
+    """(source, library) of the example tests/user_model/<name>.hip"""
+    return os.path.join(USER_MODEL_DIR, name + ".hip"), os.path.join(USER_MODEL_DIR, "lib" + name + ".so")
+
+
 def build_user_model_example(force=False, verbose=False):
-    """tests/user_model/: a caller's own residual models compiled against include/mir_optim_amd_batched.hpp and
-    include/mir_optim_amd_resident.hpp (the device headers of the batched fit and of the resident-J path) into a library of its own -- what a user of that header does. Built here so that it travels prebuilt.
-    The double model of user_model_f64.hip goes into a library of its own next to it (user_model_f64_lib()), and so does the
-    weighted fit with covariance of user_model_weighted.hip (user_model_weighted_lib()) and the fit with binding bounds of
-    user_model_bounded.hip (user_model_bounded_lib()), and the 9 and 13 parameter models of user_model_n16.hip
-    (user_model_n16_lib()) and their weighted fits with covariance of user_model_n16_weighted.hip (user_model_n16_weighted_lib()),
-    and the fit with a box per problem of user_model_problem_bounds.hip (user_model_problem_bounds_lib())."""
+    """tests/user_model/: a caller's own residual models compiled against the public device headers (include/) into libraries of
+    their own, one per source of USER_MODELS -- what a user of those headers does. Built here so that they travel prebuilt. A
+    library is rebuilt when its source or a header it includes (the compiler's own dependency file, as for the solver's units)
+    is newer. The compiler runs in the repository's root on relative paths, so that the record holds for the tree wherever it
+    lies. Returns the path of libuser_model.so."""
     root = os.path.dirname(HERE)
-    src = os.path.join(root, "tests", "user_model", "user_model.hip")
-    out = os.path.join(root, "tests", "user_model", "libuser_model.so")
-    deps = [src, os.path.join(root, "include", "mir_optim_amd_batched.hpp"), os.path.join(root, "include", "mir_optim_amd.h"),
-            os.path.join(CSRC, "batched_kernel.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "solve_types.h"),
-            os.path.join(CSRC, "lm_rules.h"), os.path.join(CSRC, "batched_bounded.h"), os.path.join(CSRC, "boxqp_rows.h"),
-            os.path.join(root, "include", "mir_optim_amd_resident.hpp"), os.path.join(CSRC, "resident_kernel.h"),
-            os.path.join(CSRC, "solve_wave16.h"), os.path.join(CSRC, "solve_kernel.h"), os.path.join(CSRC, "solve_lds.h")]
-    if force or _stale(out, deps):
-        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out, src], verbose)
-    src64, out64 = user_model_f64_paths()
-    if force or _stale(out64, [src64] + deps[1:9]):
-        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out64, src64], verbose)
-    srcw, outw = user_model_weighted_paths()
-    if force or _stale(outw, [srcw] + deps[1:9]):
-        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", outw, srcw], verbose)
-    srcb, outb = user_model_bounded_paths()
-    if force or _stale(outb, [srcb] + deps[1:9]):
-        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", outb, srcb], verbose)
-    src16, out16 = user_model_n16_paths()
-    deps16 = deps[1:9] + [os.path.join(CSRC, "batched16_kernel.h"), os.path.join(CSRC, "solve_wave16.h")]
-    if force or _stale(out16, [src16] + deps16):
-        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out16, src16], verbose)
-    src16w, out16w = user_model_n16_weighted_paths()
-    if force or _stale(out16w, [src16w] + deps16):
-        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", out16w, src16w], verbose)
-    srcp, outp = user_model_problem_bounds_paths()
-    if force or _stale(outp, [srcp] + deps[1:9]):
-        _run([_hipcc()] + _FLAGS + ["-shared", "-I", os.path.join(root, "include"), "-o", outp, srcp], verbose)
-    return out
+    os.makedirs(OBJDIR, exist_ok=True)
+    for name in USER_MODELS:
+        src, out = example_paths(name)
+        dep = os.path.join(OBJDIR, name + ".d")
+        deps = _deps(dep, root)
+        if force or deps is None or _stale(out, [src] + deps):
+            _run([_hipcc()] + _FLAGS + ["-shared", "-I", "include", "-MMD", "-MF", dep, "-o", out, os.path.relpath(src, root)], verbose,
+                 cwd=root)
+    return example_paths("user_model")[1]
 
 
-def user_model_f64_paths():
-    """(source, library) of the caller's double model on the batched path (tests/user_model/user_model_f64.hip)"""
-    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
-    return os.path.join(d, "user_model_f64.hip"), os.path.join(d, "libuser_model_f64.so")
-
-
-def user_model_f64_lib(force=False, verbose=False):
-    """Builds (when stale) and returns the path of tests/user_model/libuser_model_f64.so."""
+def example_lib(name, force=False, verbose=False):
+    """Builds (when stale) and returns the path of tests/user_model/lib<name>.so."""
     build_user_model_example(force=force, verbose=verbose)
-    return user_model_f64_paths()[1]
+    return example_paths(name)[1]
 
 
-def user_model_weighted_paths():
-    """(source, library) of the caller's weighted fit with covariance (tests/user_model/user_model_weighted.hip)"""
-    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
-    return os.path.join(d, "user_model_weighted.hip"), os.path.join(d, "libuser_model_weighted.so")
-
-
-def user_model_weighted_lib(force=False, verbose=False):
-    """Builds (when stale) and returns the path of tests/user_model/libuser_model_weighted.so."""
-    build_user_model_example(force=force, verbose=verbose)
-    return user_model_weighted_paths()[1]
-
-
-def user_model_bounded_paths():
-    """(source, library) of the caller's fit with binding bounds (tests/user_model/user_model_bounded.hip)"""
-    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
-    return os.path.join(d, "user_model_bounded.hip"), os.path.join(d, "libuser_model_bounded.so")
-
-
-def user_model_bounded_lib(force=False, verbose=False):
-    """Builds (when stale) and returns the path of tests/user_model/libuser_model_bounded.so."""
-    build_user_model_example(force=force, verbose=verbose)
-    return user_model_bounded_paths()[1]
-
-
-def user_model_n16_paths():
-    """(source, library) of the caller's 9 and 13 parameter models on the batched path (tests/user_model/user_model_n16.hip)"""
-    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
-    return os.path.join(d, "user_model_n16.hip"), os.path.join(d, "libuser_model_n16.so")
-
-
-def user_model_n16_lib(force=False, verbose=False):
-    """Builds (when stale) and returns the path of tests/user_model/libuser_model_n16.so."""
-    build_user_model_example(force=force, verbose=verbose)
-    return user_model_n16_paths()[1]
-
-
-def user_model_n16_weighted_paths():
-    """(source, library) of the caller's weighted 9 and 13 parameter fits with covariance (tests/user_model/user_model_n16_weighted.hip)"""
-    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
-    return os.path.join(d, "user_model_n16_weighted.hip"), os.path.join(d, "libuser_model_n16_weighted.so")
-
-
-def user_model_n16_weighted_lib(force=False, verbose=False):
-    """Builds (when stale) and returns the path of tests/user_model/libuser_model_n16_weighted.so."""
-    build_user_model_example(force=force, verbose=verbose)
-    return user_model_n16_weighted_paths()[1]
-
-
-def user_model_problem_bounds_paths():
-    """(source, library) of the caller's fit with a box per problem (tests/user_model/user_model_problem_bounds.hip)"""
-    d = os.path.join(os.path.dirname(HERE), "tests", "user_model")
-    return os.path.join(d, "user_model_problem_bounds.hip"), os.path.join(d, "libuser_model_problem_bounds.so")
-
-
-def user_model_problem_bounds_lib(force=False, verbose=False):
-    """Builds (when stale) and returns the path of tests/user_model/libuser_model_problem_bounds.so."""
-    build_user_model_example(force=force, verbose=verbose)
-    return user_model_problem_bounds_paths()[1]
+# user_model_f64_paths(), user_model_f64_lib(force=False, verbose=False), ...: the two functions above for each example by name
+for _name in USER_MODELS:
+    globals()[_name + "_paths"] = functools.partial(example_paths, _name)
+    globals()[_name + "_lib"] = functools.partial(example_lib, _name)

@@ -11,7 +11,7 @@ int mir_lsq_batched_kernel_s(const mir_least_squares_settings_s* S, size_t count
                              const float* lower, const float* upper, const float* t, size_t t_stride, const float* data,
                              mir_least_squares_result_s* results, const mir_lsq_batched_options* options)
 {
-    return batched_kernel_entry<float>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options);
+    return batched_kernel_entry<BuiltinModels<float>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options);
 }
 
 int mir_optimize_least_squares_batched_s(const mir_least_squares_settings_s* S, size_t count, size_t m, int model,
@@ -19,7 +19,7 @@ int mir_optimize_least_squares_batched_s(const mir_least_squares_settings_s* S, 
                                          const float* t, size_t t_stride, const float* data,
                                          mir_least_squares_result_s* results, const mir_lsq_batched_options* options)
 {
-    return batched_host_entry<float>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options);
+    return batched_host_entry<BuiltinModels<float>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options);
 }
 
 int mir_lsq_batched_posvx_s(size_t count, size_t n, const float* P, const float* rhs, float* x, int* info, void* stream)
@@ -32,7 +32,7 @@ int mir_lsq_batched_kernel_ex_s(const mir_least_squares_settings_s* S, size_t co
                                 mir_least_squares_result_s* results, const mir_lsq_batched_options* options,
                                 const mir_lsq_batched_extras* extras)
 {
-    return batched_kernel_entry<float>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
+    return batched_kernel_entry<BuiltinModels<float>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
 }
 
 int mir_optimize_least_squares_batched_ex_s(const mir_least_squares_settings_s* S, size_t count, size_t m, int model,
@@ -41,7 +41,7 @@ int mir_optimize_least_squares_batched_ex_s(const mir_least_squares_settings_s* 
                                             mir_least_squares_result_s* results, const mir_lsq_batched_options* options,
                                             const mir_lsq_batched_extras* extras)
 {
-    return batched_host_entry<float>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
+    return batched_host_entry<BuiltinModels<float>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
 }
 
 int mir_lsq_batched_covariance_s(const mir_least_squares_settings_s* S, size_t count, size_t m, int model, const float* x,
@@ -49,7 +49,7 @@ int mir_lsq_batched_covariance_s(const mir_least_squares_settings_s* S, size_t c
                                  const mir_least_squares_result_s* results, const mir_lsq_batched_options* options,
                                  const mir_lsq_batched_extras* extras)
 {
-    return batched_covariance_entry<float>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
+    return batched_covariance_entry<BuiltinModels<float>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
 }
 
 }  // extern "C"

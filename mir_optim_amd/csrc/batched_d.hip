@@ -11,7 +11,7 @@ int mir_lsq_batched_kernel_d(const mir_least_squares_settings_d* S, size_t count
                              const double* lower, const double* upper, const double* t, size_t t_stride, const double* data,
                              mir_least_squares_result_d* results, const mir_lsq_batched_options* options)
 {
-    return batched_kernel_entry<double>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options);
+    return batched_kernel_entry<BuiltinModels<double>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options);
 }
 
 int mir_optimize_least_squares_batched_d(const mir_least_squares_settings_d* S, size_t count, size_t m, int model,
@@ -19,7 +19,7 @@ int mir_optimize_least_squares_batched_d(const mir_least_squares_settings_d* S, 
                                          const double* t, size_t t_stride, const double* data,
                                          mir_least_squares_result_d* results, const mir_lsq_batched_options* options)
 {
-    return batched_host_entry<double>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options);
+    return batched_host_entry<BuiltinModels<double>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options);
 }
 
 int mir_lsq_batched_posvx_d(size_t count, size_t n, const double* P, const double* rhs, double* x, int* info, void* stream)
@@ -32,7 +32,7 @@ int mir_lsq_batched_kernel_ex_d(const mir_least_squares_settings_d* S, size_t co
                                 mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
                                 const mir_lsq_batched_extras* extras)
 {
-    return batched_kernel_entry<double>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
+    return batched_kernel_entry<BuiltinModels<double>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
 }
 
 int mir_optimize_least_squares_batched_ex_d(const mir_least_squares_settings_d* S, size_t count, size_t m, int model,
@@ -41,7 +41,7 @@ int mir_optimize_least_squares_batched_ex_d(const mir_least_squares_settings_d* 
                                             mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
                                             const mir_lsq_batched_extras* extras)
 {
-    return batched_host_entry<double>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
+    return batched_host_entry<BuiltinModels<double>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
 }
 
 int mir_lsq_batched_covariance_d(const mir_least_squares_settings_d* S, size_t count, size_t m, int model, const double* x,
@@ -49,7 +49,7 @@ int mir_lsq_batched_covariance_d(const mir_least_squares_settings_d* S, size_t c
                                  const mir_least_squares_result_d* results, const mir_lsq_batched_options* options,
                                  const mir_lsq_batched_extras* extras)
 {
-    return batched_covariance_entry<double>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
+    return batched_covariance_entry<BuiltinModels<double>>(S, count, m, model, x, lower, upper, t, t_stride, data, results, options, extras);
 }
 
 }  // extern "C"

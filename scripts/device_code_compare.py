@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel comparison of the gfx950 device code of two trees (profiles/r08, r09: device_code_compare.txt).
+"""Per-kernel comparison of the gfx950 device code of two trees (profiles/r08, r09, r20: device_code_compare.txt).
 
     python scripts/device_code_compare.py PARENT_TREE BRANCH_TREE OUT_DIR
 
@@ -9,25 +9,28 @@ block as text after local labels are normalised, and prints VGPR / AGPR / scratc
 a kernel that differs also whether the instruction counts per opcode agree. A kernel whose parameter type was renamed is paired
 through RENAMES, applied to the demangled name; its own symbol is blanked in the compared text."""
 import collections
+import glob
 import os
 import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mir_optim_amd import build as hipbuild  # noqa: E402
+
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only", "-S"]
-UNITS = ["solver_loop", "launch_solve_d", "launch_solve_s", "unit_entries", "batched", "batched_d", "workloads_resident", "workloads",
-         "workloads_gemm", "solver_jacobian", "launch_jtj", "launch_broyden", "comm", "launch_boxqp", "launch_boxqp16_s", "launch_boxqp16_d"]
-# (a defaulted template parameter that the parent did not have is dropped from the name: k_lm_batched's Bounds, profiles/r13)
-RENAMES = {"BoxQpRows16Args": "BoxQpRowsArgs", ", mirlsq::BatchedNoBoundedStep>": ">"}
-USER = ["user_model", "user_model_f64", "user_model_weighted"]
-NEW_UNITS = ["batched_bounded", "batched_bounded_d"]        # in the branch only: their kernels are listed, not compared
-NEW_USER = ["user_model_bounded"]
+# every unit of the two libraries that can carry kernels, and every example of tests/user_model/
+UNITS = [u[:-4] for u in hipbuild.SOLVER_UNITS + hipbuild.WORKLOAD_UNITS if u.endswith(".hip")]
+USER = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(os.path.dirname(hipbuild.HERE), "tests", "user_model", "*.hip")))
+RENAMES = {}        # demangled-name substitutions that pair a kernel whose parameter type was renamed: none
+NEW_UNITS = []      # units and examples of the branch only, whose kernels are listed and not compared: none
+NEW_USER = []
 
 
 def compile_tree(tree, out):
     os.makedirs(out, exist_ok=True)
-    cmds = [["hipcc"] + FLAGS + (["-fopenmp"] if u.startswith("workloads") else []) + ["mir_optim_amd/csrc/%s.hip" % u, "-o", "%s/%s.s" % (out, u)]
+    cmds = [["hipcc"] + FLAGS + (["-fopenmp"] if u + ".hip" in hipbuild.WORKLOAD_UNITS else []) + ["mir_optim_amd/csrc/%s.hip" % u, "-o", "%s/%s.s" % (out, u)]
             for u in UNITS]
     cmds += [["hipcc"] + FLAGS + ["-I", "include", "tests/user_model/%s.hip" % u, "-o", "%s/%s.s" % (out, u)] for u in USER]
     cmds += [["hipcc"] + FLAGS + ["mir_optim_amd/csrc/%s.hip" % u, "-o", "%s/%s.s" % (out, u)]
@@ -82,7 +85,7 @@ def main(parent, branch, out):
     pd, bd = os.path.join(out, "parent"), os.path.join(out, "branch")
     compile_tree(parent, pd)
     compile_tree(branch, bd)
-    tot = same = 0
+    tot = same = alone = 0
     for u in UNITS + USER + NEW_UNITS + NEW_USER:
         pk, pr, bk, br = by_demangled_name(*kernels("%s/%s.s" % (pd, u)), *kernels("%s/%s.s" % (bd, u)))
         print("== %s: %d kernels in the parent, %d in the branch" % (u, len(pk), len(bk)))
@@ -90,6 +93,7 @@ def main(parent, branch, out):
             print("  " + k)
             if k not in bk:
                 print("      only in the parent")
+                alone += 1
                 continue
             tot += 1
             ident = pk[k] == bk[k]
@@ -102,9 +106,10 @@ def main(parent, branch, out):
                   % (("yes" if ident else "NO",) + tuple(v for pair in zip(pr[k], br[k]) for v in pair) + (extra,)))
         for k in bk:
             if k not in pk:
+                alone += 1
                 print("  " + k + "\n      only in the branch   VGPR %d  AGPR %d  scratch %d  static LDS %d" % br[k])
-    print("== total: %d kernels present in both trees, %d text-identical" % (tot, same))
-    return 0 if tot == same else 1
+    print("== total: %d kernels present in both trees, %d text-identical, %d in one tree only" % (tot, same, alone))
+    return 0 if tot == same and not alone else 1
 
 
 if __name__ == "__main__":

@@ -126,6 +126,32 @@ def test_python_wrapper_refuses_what_the_entry_does_not_have(monkeypatch):
     assert xo.dtype == np.float64 and len(res) == 2
 
 
+def test_an_example_is_rebuilt_for_a_header_it_includes_and_for_nothing_else(monkeypatch):
+    """staleness comes from the compiler's record of what the example includes: solve_wave16.h reaches user_model_n16.hip only
+    through the public header and batched16_kernel.h; driver.h is the library's own"""
+    lib = hipbuild.user_model_n16_lib()         # up to date from here on
+    src = open(hipbuild.user_model_n16_paths()[0]).read()
+    assert "solve_wave16.h" not in src and "driver.h" not in src
+    ran = []
+    monkeypatch.setattr(hipbuild, "_run", lambda cmd, verbose, cwd=None: ran.append(cmd))
+    assert hipbuild.user_model_n16_lib() == lib and ran == []
+    newer = os.path.getmtime(lib) + 10
+
+    def touched(header):
+        path = os.path.join(hipbuild.CSRC, header)
+        st = os.stat(path)
+        os.utime(path, (newer, newer))
+        try:
+            hipbuild.user_model_n16_lib()
+        finally:
+            os.utime(path, ns=(st.st_atime_ns, st.st_mtime_ns))
+        out, ran[:] = [c for c in ran if any(a.endswith("user_model_n16.hip") for a in c)], []
+        return out
+    assert len(touched("solve_wave16.h")) == 1
+    assert touched("driver.h") == []
+    assert hipbuild.user_model_n16_lib() == lib and ran == []
+
+
 def test_n16_user_models_build_against_the_public_header_and_export_their_entries():
     path = hipbuild.user_model_n16_lib()        # hipcc --offload-arch=gfx950 cross-compiles without a GPU
     L = C.CDLL(path)

@@ -106,6 +106,39 @@ def test_no_problems_is_no_work(entry, suffix, dtype, R):
         assert fn(C.byref(s), 0, 16, M.MODEL_EXP_DECAY, p(x), p(lo), p(up), p(t), 0, p(d), raw, None, None) == 0
 
 
+@pytest.mark.parametrize("suffix, dtype, R", PRECISIONS)
+def test_no_problems_whatever_m_is_and_the_covariance_entry_still_needs_its_output(suffix, dtype, R):
+    """count = 0 is answered 0 before m is looked at (m = 10^6 fits no LDS) and without a device, by the entries with and
+    without extras; the covariance entry answers -1 without extras or without a covariance even then"""
+    L = api.lib()
+    s = M.LeastSquaresSettings(dtype)
+    x, lo, up, t, d, raw, w, cov = _args(dtype, R)
+    p = lambda a: a.ctypes.data
+    none = [C.byref(s), 0, 10 ** 6, M.MODEL_EXP_DECAY_PAD8, p(x), p(lo), p(up), p(t), 0, p(d), raw, None]
+    for entry in ("mir_optimize_least_squares_batched", "mir_lsq_batched_kernel"):
+        assert getattr(L, entry + suffix)(*none) == 0, entry
+    ex = api.BatchedExtras(covariance=p(cov))
+    for entry in ENTRIES:
+        assert getattr(L, entry + suffix)(*(none + [C.byref(ex)])) == 0, entry
+    fn = getattr(L, "mir_lsq_batched_covariance" + suffix)
+    assert fn(*(none + [None])) == -1
+    assert fn(*(none + [C.byref(api.BatchedExtras(weights=p(w)))])) == -1
+
+
+@pytest.mark.parametrize("suffix, dtype, R", PRECISIONS)
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_the_analytic_jacobian_of_a_model_without_grad_is_refused_after_the_device_check(entry, suffix, dtype, R):
+    """none of the built-in models of up to 8 parameters has grad: the launch refuses (-1 from the device-pointer entries, -5
+    from the host-pointer one, which folds it into its launch) -- behind the device check, so -2 without a device"""
+    fn = getattr(api.lib(), entry + suffix)
+    s = M.LeastSquaresSettings(dtype)
+    x, lo, up, t, d, raw, w, cov = _args(dtype, R)
+    p = lambda a: a.ctypes.data
+    ex = api.BatchedExtras(covariance=p(cov))
+    rc = fn(C.byref(s), 4, 16, M.MODEL_EXP_DECAY, p(x), p(lo), p(up), p(t), 0, p(d), raw, C.byref(api.BatchedOptions(variant=2)), C.byref(ex))
+    assert rc == (-2 if M.device_count() == 0 else -5 if entry.startswith("mir_optimize") else -1)
+
+
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_python_with_no_problems_returns_empty_arrays(dtype):
     x = np.zeros((0, 8)); t = np.linspace(0, 1, 32); d = np.zeros((0, 32))
