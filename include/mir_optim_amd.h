@@ -713,6 +713,42 @@ int mir_lsq_fd_diff_jtj_d(size_t m, size_t n, const double* Drm, const double* t
  * the slab reduction is given (0: the tile pairs' own reduction), slab elements a workspace holds }. Returns 0, or -1 (arguments). */
 int mir_lsq_jtj_plan(size_t elem_size, size_t m, size_t n, int num_cu, int op, int aligned16, size_t out[10]);
 
+/* Unit-level access to the n x n part of one round of the general solver (csrc/launch_solve.inc: the gradient test LS:1053, the
+ * lambda_0 rule LS:1067-1072, P = J^T J + lambda I and the shifted box, solveBoxQP, the rounded step, the step guard, the clamped
+ * trial point LS:1087-1110, the predicted reduction LS:1141-1142 and ||trial||_2 LS:1164): ONE launch for the ladder lam[0 .. ks),
+ * 1 <= ks <= 8, entry k solving with lam[k]. All pointers are HOST pointers; the call owns its device memory and synchronises.
+ * JJ n x n row-major, full symmetric, undamped; Jy, x, lower, upper n values. state_lambda: the lambda of the device-resident
+ * state, which entry 0 takes instead of lam[0] with MIR_LSQ_LM_SOLVE_LAMBDA_FROM_STATE (below minLambda: the lambda_0 rule).
+ * mode: MIR_LSQ_LM_SOLVE_* bits. FORCE_BOUNDED: the kernel with the BOXCQP loop although every bound is infinite (otherwise the
+ * driver's rule: some bound finite); GENERIC: the any-n kernel below n = 257; ONE_WORKGROUP: the any-n kernel without helper
+ * workgroups (otherwise the driver's width for n and this device). Fused rounds are not reachable here.
+ * Out: rec[0 .. ks): the records the round's decision reads; dx, trial: 8 x n each, rows the kernel did not write hold
+ * MIR_LSQ_LM_SOLVE_SENTINEL; *jy_inf: the state's ||J^T y||_inf (written with CHECK_GRAD); JJ, Jy, x, lower, upper: as they are
+ * on the device AFTER the launch; info = { kernel class as mir_lsq_lm_solve_class's out[0 .. 2], workgroups per ladder entry
+ * (1: no helpers), the first guard band that is not intact or -1, the number of guard bands }. Every device region the kernels
+ * are handed (the inputs, dx, trial, the records, the state and each ladder entry's scratch at the workspace's sizes) lies
+ * between bands of at least 4 KiB of 0xFF bytes; band b is in front of region b in that order.
+ * Returns 0, -1 (arguments), -2 (no device), -3 (allocation / upload), -4 (launch), -5 (synchronisation / download). */
+enum { MIR_LSQ_LM_SOLVE_CHECK_GRAD = 1u, MIR_LSQ_LM_SOLVE_LAMBDA_FROM_STATE = 2u, MIR_LSQ_LM_SOLVE_FORCE_BOUNDED = 4u,
+       MIR_LSQ_LM_SOLVE_GENERIC = 8u, MIR_LSQ_LM_SOLVE_ONE_WORKGROUP = 16u };
+#define MIR_LSQ_LM_SOLVE_SENTINEL (-123456.0)
+/* record flags: 1 NaN in the step, 2 NaN in the trial point, 4 step guard LS:1101, 16 gradient test LS:1053 (every other field 0),
+ * 32 null step (trial == x bit for bit), 64 the entry's helper workgroups timed out and one workgroup solved it again */
+typedef struct { double lambda, new_dx_dot, predicted, trial_xnorm; int32_t qp_status, qp_iterations, flags, reserved; } mir_lsq_lm_solve_record_d;
+typedef struct { float  lambda, new_dx_dot, predicted, trial_xnorm; int32_t qp_status, qp_iterations, flags, reserved; } mir_lsq_lm_solve_record_s;
+int mir_lsq_lm_solve_d(const mir_least_squares_settings_d* settings, size_t n, double* JJ, double* Jy, double* x, double* lower,
+                       double* upper, int ks, const double* lam, double state_lambda, unsigned mode, mir_lsq_lm_solve_record_d* rec,
+                       double* dx, double* trial, double* jy_inf, int info[6]);
+int mir_lsq_lm_solve_s(const mir_least_squares_settings_s* settings, size_t n, float* JJ, float* Jy, float* x, float* lower,
+                       float* upper, int ks, const float* lam, float state_lambda, unsigned mode, mir_lsq_lm_solve_record_s* rec,
+                       float* dx, float* trial, float* jy_inf, int info[6]);
+/* Which kernel launch_lm_solve runs (host code, no device needed): element size 4 / 8; bounded: some bound finite (or forced);
+ * generic: the any-n kernel asked for; diagnostic: the phase-stamp buffer is attached. out = { 0 one wave per ladder entry
+ * (k_lm_solve_wave: f64, n <= 16) / 1 one 256-thread workgroup (k_lm_solve) / 2 the any-n kernel (k_lm_solve_big), the 16-row LDS
+ * blocks a side the workgroup kernel is compiled for (1, 2, 4, 8; 0: factor in global memory), 1 = the instance with the BOXCQP
+ * loop (always 1 for the any-n kernel) }. Returns 0, or -1 (arguments). */
+int mir_lsq_lm_solve_class(size_t elem_size, size_t n, int bounded, int generic, int diagnostic, int out[3]);
+
 /* Covariance of the fitted parameters of the general solver: cov = s^2 inv(J^T J) at x (usually the x a solve returned), from
  * ONE full Jacobian refresh made exactly as a refresh of the solve makes it (g if given, else finite differences through the
  * same callbacks, options->fb / fbRowMajor / fbRowMajorDiff, fd_batch and clipping of x +- jacobianEpsilon to [l, u]), the J^T J

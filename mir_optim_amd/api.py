@@ -39,6 +39,7 @@ __all__ = [
     "VARIANT_NO_PIPELINE", "FD_BASE_POINT", "VARIANT_NO_FD_BASE_POINT", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA", "BATCHED_BOUNDS_PER_PROBLEM",
     "covariance", "spdInverse", "COVARIANCE_ABSOLUTE_SIGMA",
     "fitSplineGpu", "splineEvalGpu", "fit_spline_eval_gpu", "fit_spline_eval_host", "fit_spline_factor",
+    "lmSolve", "lm_solve_class",
 ]
 
 MODEL_EXP_DECAY = 0      # n = 3: p0 exp(-t p1) + p2
@@ -321,6 +322,13 @@ def lib():
         L.mir_lsq_jtj_plan.argtypes = [sz, sz, sz, C.c_int, C.c_int, C.c_int, C.POINTER(sz * 10)]
         L.mir_lsq_selftest_reductions.restype = C.c_int
         L.mir_lsq_selftest_reductions.argtypes = [C.c_int, C.POINTER(C.c_int * 4)]
+        for suf, S, ct in (("d", _Sd, C.c_double), ("s", _Ss, C.c_float)):
+            fn = getattr(L, "mir_lsq_lm_solve_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [C.POINTER(S), sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, ct,
+                           C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int * 6)]
+        L.mir_lsq_lm_solve_class.restype = C.c_int
+        L.mir_lsq_lm_solve_class.argtypes = [sz, sz, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int * 3)]
         L.mir_lsq_batched_posvx_s.restype = C.c_int
         L.mir_lsq_batched_posvx_s.argtypes = [sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mir_optimize_least_squares_batched_d.restype = C.c_int
@@ -946,6 +954,62 @@ def solveBoxQP(P, q, l, u, x=None, settings=None, dtype=np.float64, unconstraine
 
 
 BOX_QP_UNCONSTRAINED_SOLUTION = 1      # MIR_LSQ_BOX_QP_UNCONSTRAINED_SOLUTION
+
+LM_SOLVE_KINDS = ("wave", "workgroup", "big")      # mir_lsq_lm_solve_class: out[0]
+LM_SOLVE_SENTINEL = -123456.0                      # MIR_LSQ_LM_SOLVE_SENTINEL
+LM_SOLVE_CHAIN = 8                                 # ladder entries of one launch, rows of dx / trial
+LM_FLAG_DX_NAN, LM_FLAG_X_NAN, LM_FLAG_STEP_TOO_LONG, LM_FLAG_GRAD_SMALL, LM_FLAG_NULL_STEP, LM_FLAG_COOP_RESCUED = 1, 2, 4, 16, 32, 64
+
+
+def lm_solve_class(elem_size, n, bounded, generic=False, diagnostic=False):
+    """The kernel one LM solve launch runs (mir_lsq_lm_solve_class; host code, no GPU): (kind of LM_SOLVE_KINDS, LDS blocks a side
+    the workgroup kernel is compiled for -- 0: factor in global memory --, True: the instance with the BOXCQP loop)."""
+    out = (C.c_int * 3)()
+    rc = lib().mir_lsq_lm_solve_class(elem_size, n, int(bool(bounded)), int(bool(generic)), int(bool(diagnostic)), C.byref(out))
+    if rc != 0:
+        raise ValueError(f"mir_lsq_lm_solve_class: {rc}")
+    return LM_SOLVE_KINDS[out[0]], int(out[1]), bool(out[2])
+
+
+def lm_solve_record_dtype(dtype):
+    f = np.dtype(dtype)
+    return np.dtype([("lambda", f), ("new_dx_dot", f), ("predicted", f), ("trial_xnorm", f), ("qp_status", np.int32),
+                     ("qp_iterations", np.int32), ("flags", np.int32), ("reserved", np.int32)])
+
+
+def lmSolve(JJ, Jy, x, lower, upper, lam, settings=None, dtype=np.float64, state_lambda=0.0, check_grad=False,
+            lambda_from_state=False, force_bounded=False, generic=False, one_workgroup=False):
+    """One launch of the LM solve kernels (mir_lsq_lm_solve_d / _s): the n x n part of a round for the ladder `lam` (1 .. 8 values).
+    Returns a dict: rec (structured array, one record a ladder entry), dx, trial (8 x n; rows nobody wrote hold LM_SOLVE_SENTINEL),
+    jy_inf, cls (as lm_solve_class), helpers (workgroups per ladder entry), guard (first damaged guard band or -1), bands, and
+    inputs: (JJ, Jy, x, lower, upper) as they are on the device after the launch."""
+    JJ = np.array(JJ, dtype=dtype, order="C")
+    n = JJ.shape[0]
+    if JJ.shape != (n, n):
+        raise ValueError(f"JJ: n x n, not {JJ.shape}")
+    vecs = [np.array(v, dtype=dtype, order="C") for v in (Jy, x, lower, upper)]
+    if any(v.shape != (n,) for v in vecs):
+        raise ValueError(f"Jy, x, lower, upper: {n} values each")
+    lam = np.array(lam, dtype=dtype, order="C").reshape(-1)
+    ks = lam.size
+    if not 1 <= ks <= LM_SOLVE_CHAIN:
+        raise ValueError(f"lam: 1 .. {LM_SOLVE_CHAIN} values, not {ks}")
+    if settings is None:
+        settings = LeastSquaresSettings(dtype)
+    rec = np.zeros(ks, dtype=lm_solve_record_dtype(dtype))
+    dx = np.zeros((LM_SOLVE_CHAIN, n), dtype=dtype)
+    trial = np.zeros((LM_SOLVE_CHAIN, n), dtype=dtype)
+    jy_inf = np.zeros(1, dtype=dtype)
+    info = (C.c_int * 6)()
+    mode = (1 if check_grad else 0) | (2 if lambda_from_state else 0) | (4 if force_bounded else 0) | (8 if generic else 0) \
+        | (16 if one_workgroup else 0)
+    fn = lib().mir_lsq_lm_solve_d if dtype == np.float64 else lib().mir_lsq_lm_solve_s
+    rc = fn(C.byref(settings), n, JJ.ctypes.data, *(v.ctypes.data for v in vecs), ks, lam.ctypes.data, float(state_lambda), mode,
+            rec.ctypes.data, dx.ctypes.data, trial.ctypes.data, jy_inf.ctypes.data, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_lm_solve failed: {rc}")
+    return {"rec": rec, "dx": dx, "trial": trial, "jy_inf": jy_inf[0], "cls": (LM_SOLVE_KINDS[info[0]], int(info[1]), bool(info[2])),
+            "helpers": int(info[3]), "guard": int(info[4]), "bands": int(info[5]), "inputs": (JJ, *vecs)}
 
 
 def _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution):

@@ -39,7 +39,9 @@ hipError_t launch_lm_solve(const LmSolveArgs<T>& a, int ks, bool bounded, bool g
 {
     if (ks < 1 || ks > kChainMax) return hipErrorInvalidValue;
     if (a.fused && (generic || a.n > kSolveMaxN || ks != 1)) return hipErrorInvalidValue;   // fused rounds: the one-workgroup kernels
-    if (generic || a.n > kSolveMaxN) {
+    static_assert(kSolveWaveMaxN == kW16, "lm_solve_class sends n <= kSolveWaveMaxN to the kernel compiled for kW16 rows");
+    const LmSolveClass cls = lm_solve_class((int)sizeof(T), a.n, bounded, generic, a.sc[0].dbg != nullptr);
+    if (cls.kind == kLmSolveBig) {
         // any n: one 512-thread workgroup per ladder entry, matrices in global memory (solve_big.h)
         // (a.coop_w > 1: coop_w workgroups per entry, the first of each group is the entry's own -- solve_coop.h)
         auto kern = k_lm_solve_big<T>;
@@ -68,14 +70,14 @@ hipError_t launch_lm_solve(const LmSolveArgs<T>& a, int ks, bool bounded, bool g
     if constexpr (std::is_same<T, double>::value) {
         // n <= 16: one wave per ladder entry, a matrix row per lane (solve_wave16.h). (The phase stamps of DEBUG_SOLVE belong to
         // the workgroup kernel: a diagnostic run keeps it.)
-        if (a.n <= kW16 && !a.sc[0].dbg) {
+        if (cls.kind == kLmSolveWave) {
             if (bounded) MIRLSQ_LAUNCH(k_lm_solve_wave<true>, dim3(ks), dim3(kWave), 0, s, a);
             else MIRLSQ_LAUNCH(k_lm_solve_wave<false>, dim3(ks), dim3(kWave), 0, s, a);
             return hipGetLastError();
         }
     }
     const size_t lds = solve_lds_bytes(a.n, (int)sizeof(T));
-    switch (solve_nb(a.n, (int)sizeof(T))) {
+    switch (cls.nb) {
     case 1: return lm_solve_nb<T, 1>(a, ks, bounded, lds, s);
     case 2: return lm_solve_nb<T, 2>(a, ks, bounded, lds, s);
     case 4: return lm_solve_nb<T, 4>(a, ks, bounded, lds, s);

@@ -1131,7 +1131,9 @@ __global__ __launch_bounds__(kWave) void k_lm_solve_wave(LmSolveArgs<double> a)
     if (g == 0 && el && !(lv.flags & kFlagGradSmall)) { a.dx[(size_t)kc * n + r] = d; a.trial[(size_t)kc * n + r] = t; }
     if (lane == 0) {
         ChainRec<double> rec{};
-        rec.lambda = lv.lambda; rec.new_dx_dot = lv.ndd; rec.predicted = lv.pred; rec.trial_xnorm = lv.xnorm;
+        // (a failed gradient test leaves the record the workgroup kernels leave: the flag and zeros -- the level still carries
+        // the lambda it was handed)
+        rec.lambda = (lv.flags & kFlagGradSmall) ? 0.0 : lv.lambda; rec.new_dx_dot = lv.ndd; rec.predicted = lv.pred; rec.trial_xnorm = lv.xnorm;
         rec.qp_status = lv.qp_status; rec.qp_iterations = lv.qp_iters; rec.flags = lv.flags;
         a.rec[kc] = rec;
     }

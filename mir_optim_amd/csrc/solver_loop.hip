@@ -312,11 +312,8 @@ LmSolveArgs<T> Solver<T>::solve_args(int ks, const T* lam, bool check_grad, bool
     a.check_grad = check_grad ? 1 : 0;
     a.lambda_from_state = lambda_from_state ? 1 : 0;
     if (!dbg_solve) a.sc[0].dbg = nullptr;
-    // n > 256: every ladder entry's workgroup gets helpers (solve_coop.h)
-    a.coop_w = (big_solve && n > (uint32_t)kSolveMaxN && !(variant & MIR_LSQ_VARIANT_SOLVE_ONE_WORKGROUP) && !coop_disabled) ? coop_peers((int)n) : 1;
-    // an entry's workgroups hold a CU each (150 KB of LDS) and wait for one another: never more of them than half the device
-    // (a partitioned or masked GPU), or a group could never be resident at once
-    if (a.coop_w > ws->num_cu / 2) a.coop_w = ws->num_cu / 2 >= 2 ? ws->num_cu / 2 : 1;
+    // n > 256: every ladder entry's workgroup gets helpers (solve_coop.h), at most half the device's CUs of them (coop_width)
+    a.coop_w = coop_width((int)n, ws->num_cu, big_solve && !(variant & MIR_LSQ_VARIANT_SOLVE_ONE_WORKGROUP) && !coop_disabled);
     a.coop_epoch = a.coop_w > 1 ? ++ws->solve_epoch : 0;
     a.coop_absent = (variant & MIR_LSQ_VARIANT_DEBUG_HELPERS_ABSENT) ? 1 : 0;
     return a;

@@ -1,6 +1,10 @@
 // unit_entries.hip -- unit-level access to the kernels of the path (parity tests, micro-benchmarks) and the standalone
 // BOXCQP entry: mir_solve_box_qp_gpu_* (boxcqp.d:85-102 is D-only), mir_lsq_jtj_*, mir_lsq_fd_jtj_d, mir_lsq_fd_diff_jtj_d,
-// mir_lsq_selftest_reductions, mir_fit_spline_gpu_eval_* / _eval_host_* / _factor_* (fit_spline_gpu.hip). Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
+// mir_lsq_lm_solve_* (one launch of the LM solve kernels; mir_lsq_lm_solve_class is host code), mir_lsq_selftest_reductions, mir_fit_spline_gpu_eval_* / _eval_host_* / _factor_* (fit_spline_gpu.hip). Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
+#include <cstring>
+#include <memory>
+#include <vector>
+
 #include "driver.h"
 #include "fit_spline_gpu.h"
 #include "misc_kernels.h"
@@ -80,6 +84,114 @@ int box_qp_entry(const QS* settings, size_t n_, const T* P, const T* q, const T*
     if (!good) return mir_box_qp_numericError;
     if (iterations) *iterations = out[1];
     return out[0];
+}
+
+// mir_lsq_lm_solve_*: ONE launch_lm_solve (one round's n x n part, ks ladder entries) on operands of the caller's, every device
+// region the kernels are handed -- the five inputs, dx, trial, rec, the state, and each ladder entry's Pm, A, Fg, vec, ivec, coop,
+// cS, at workspace.hip's sizes -- inside one allocation with at least kLmGuardBytes of 0xFF bytes (a NaN in both types) in front
+// of it and behind it: a band starts at the last byte of the region before it and ends where the next region starts (256-byte
+// aligned, as the workspace's). The scratch regions start as that pattern too (a read of scratch nobody wrote shows as a NaN), the
+// helpers' sync words as zero with epoch 1 (a fresh workspace's first solve), dx / trial as MIR_LSQ_LM_SOLVE_SENTINEL.
+constexpr size_t kLmGuardBytes = 4096;
+template <typename T, typename S, typename R>
+int lm_solve_entry(const S* settings, size_t n_, T* JJ, T* Jy, T* x, T* lower, T* upper, int ks, const T* lam, T state_lambda,
+                   unsigned mode, R* rec, T* dx, T* trial, T* jy_inf, int info[6])
+{
+    if (!settings || !JJ || !Jy || !x || !lower || !upper || !lam || !rec || !dx || !trial || !jy_inf || !info) return -1;
+    if (n_ == 0 || n_ > 4096 || ks < 1 || ks > kChainMax || (mode & ~31u)) return -1;
+    if (!device_available()) return -2;
+    const int n = (int)n_;
+    const size_t nn = (size_t)n * n;
+    struct Region { size_t off, bytes; };
+    std::vector<Region> reg;
+    size_t off = 0;
+    auto take = [&](size_t count, size_t elem) {
+        off = align_up(off + kLmGuardBytes, 256);
+        reg.push_back({off, count * elem});
+        off += count * elem;
+        return reg.size() - 1;
+    };
+    const size_t rJJ = take(nn, sizeof(T)), rJy = take(n, sizeof(T)), rx = take(n, sizeof(T)), rlo = take(n, sizeof(T)),
+                 rup = take(n, sizeof(T)), rdx = take((size_t)kChainMax * n, sizeof(T)), rtr = take((size_t)kChainMax * n, sizeof(T)),
+                 rrec = take(kChainMax, sizeof(ChainRec<T>)), rst = take(1, sizeof(LmState<T>));
+    size_t rsc[kChainMax][7];
+    for (int k = 0; k < kChainMax; ++k) {
+        rsc[k][0] = take(nn, sizeof(T)); rsc[k][1] = take(nn, sizeof(T)); rsc[k][2] = take((size_t)n * (n | 1), sizeof(T));
+        rsc[k][3] = take((size_t)12 * n, sizeof(T)); rsc[k][4] = take((size_t)2 * n, sizeof(int32_t));
+        rsc[k][5] = take(n > kSolveMaxN ? kCoopWords : 0, sizeof(unsigned long long));
+        rsc[k][6] = take(coop_scratch_elems(n), sizeof(T));
+    }
+    const size_t total = align_up(off + kLmGuardBytes, 256);
+    char* base = nullptr;
+    if (hipMalloc((void**)&base, total) != hipSuccess) return -3;
+    auto at = [&](size_t r) { return base + reg[r].off; };
+    LmSolveArgs<T> a{};
+    a.JJ = (T*)at(rJJ); a.Jy = (T*)at(rJy); a.x = (T*)at(rx); a.lower = (T*)at(rlo); a.upper = (T*)at(rup);
+    a.dx = (T*)at(rdx); a.trial = (T*)at(rtr); a.rec = (ChainRec<T>*)at(rrec); a.st = (LmState<T>*)at(rst);
+    a.set = lm_settings_dev(settings); a.n = n;
+    for (int k = 0; k < kChainMax; ++k) {
+        a.sc[k].Pm = (T*)at(rsc[k][0]); a.sc[k].A = (T*)at(rsc[k][1]); a.sc[k].Fg = (T*)at(rsc[k][2]); a.sc[k].vec = (T*)at(rsc[k][3]);
+        a.sc[k].ivec = (int32_t*)at(rsc[k][4]); a.sc[k].dbg = nullptr; a.sc[k].coop = (unsigned long long*)at(rsc[k][5]);
+        a.sc[k].cS = (T*)at(rsc[k][6]);
+        a.lam[k] = k < ks ? lam[k] : T(0);
+    }
+    a.f_in_lds = solve_nb(n, (int)sizeof(T)) > 0;
+    a.check_grad = (mode & 1u) ? 1 : 0;
+    a.lambda_from_state = (mode & 2u) ? 1 : 0;
+    bool bounded = (mode & 4u) != 0;
+    for (int i = 0; i < n; ++i)
+        if (lower[i] > -Lim<T>::inf() || upper[i] < Lim<T>::inf()) bounded = true;
+    const bool generic = (mode & 8u) != 0;
+    a.coop_w = coop_width(n, query_num_cu(), !(mode & 16u));
+    a.coop_epoch = a.coop_w > 1 ? 1u : 0u;
+    const LmSolveClass cls = lm_solve_class((int)sizeof(T), n, bounded, generic, false);
+    info[0] = cls.kind; info[1] = cls.nb; info[2] = cls.bounded; info[3] = a.coop_w; info[4] = -1; info[5] = (int)reg.size() + 1;
+
+    LmState<T> st{};
+    st.lambda = state_lambda;
+    std::vector<T> sentinel((size_t)kChainMax * n, T(MIR_LSQ_LM_SOLVE_SENTINEL));
+    bool good = hipMemset(base, 0xFF, total) == hipSuccess;
+    auto up_ = [&](size_t r, const void* src) { good = good && hipMemcpy(at(r), src, reg[r].bytes, hipMemcpyHostToDevice) == hipSuccess; };
+    up_(rJJ, JJ); up_(rJy, Jy); up_(rx, x); up_(rlo, lower); up_(rup, upper); up_(rdx, sentinel.data()); up_(rtr, sentinel.data());
+    up_(rst, &st);
+    for (int k = 0; k < kChainMax; ++k)
+        if (reg[rsc[k][5]].bytes) good = good && hipMemset(at(rsc[k][5]), 0, reg[rsc[k][5]].bytes) == hipSuccess;
+    if (!good) { (void)hipFree(base); return -3; }
+    if (launch_lm_solve<T>(a, ks, bounded, generic, nullptr) != hipSuccess) { (void)hipDeviceSynchronize(); (void)hipFree(base); return -4; }
+    // host image of the allocation: everything up to the first scratch region in one copy, behind it the bands alone (the scratch
+    // is 3 n^2 elements a ladder entry and nobody reads it here). Band b lies in front of region b, the last one behind the last.
+    std::unique_ptr<unsigned char[]> img(new unsigned char[total]);
+    auto band = [&](size_t b, size_t& lo, size_t& hi) {
+        lo = b ? reg[b - 1].off + reg[b - 1].bytes : 0; hi = b < reg.size() ? reg[b].off : total;
+    };
+    good = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess
+        && hipMemcpy(img.get(), base, reg[rsc[0][0]].off, hipMemcpyDeviceToHost) == hipSuccess;
+    for (size_t b = rsc[0][0] + 1; b <= reg.size() && good; ++b) {
+        size_t lo, hi;
+        band(b, lo, hi);
+        good = hipMemcpy(img.get() + lo, base + lo, hi - lo, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(base);
+    if (!good) return -5;
+    for (size_t b = 0; b <= reg.size() && info[4] < 0; ++b) {
+        size_t lo, hi;
+        band(b, lo, hi);
+        for (size_t i = lo; i < hi; ++i)
+            if (img[i] != 0xFF) { info[4] = (int)b; break; }
+    }
+    auto down = [&](size_t r, void* dst, size_t bytes) { std::memcpy(dst, img.get() + reg[r].off, bytes); };
+    down(rJJ, JJ, reg[rJJ].bytes); down(rJy, Jy, reg[rJy].bytes); down(rx, x, reg[rx].bytes); down(rlo, lower, reg[rlo].bytes);
+    down(rup, upper, reg[rup].bytes); down(rdx, dx, reg[rdx].bytes); down(rtr, trial, reg[rtr].bytes);
+    std::vector<ChainRec<T>> rh(kChainMax);
+    down(rrec, rh.data(), reg[rrec].bytes);
+    for (int k = 0; k < ks; ++k) {
+        rec[k].lambda = rh[k].lambda; rec[k].new_dx_dot = rh[k].new_dx_dot; rec[k].predicted = rh[k].predicted;
+        rec[k].trial_xnorm = rh[k].trial_xnorm; rec[k].qp_status = rh[k].qp_status; rec[k].qp_iterations = rh[k].qp_iterations;
+        rec[k].flags = rh[k].flags; rec[k].reserved = 0;
+    }
+    down(rst, &st, sizeof st);
+    *jy_inf = st.jy_inf;
+    return 0;
 }
 
 template <typename T>
@@ -189,6 +301,25 @@ int mir_lsq_jtj_plan(size_t elem_size, size_t m, size_t n, int num_cu, int op, i
     const size_t v[10] = {(size_t)l.kernel, (size_t)l.ncb, (size_t)l.flat, (size_t)l.nblk, (size_t)l.njobs, l.lds,
                           (size_t)l.nblk * l.njobs, (size_t)l.slab_len, wide ? 0 : (size_t)l.ncb, jtj_slab_elems(p)};
     for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return 0;
+}
+int mir_lsq_lm_solve_d(const mir_least_squares_settings_d* settings, size_t n, double* JJ, double* Jy, double* x, double* lower,
+                       double* upper, int ks, const double* lam, double state_lambda, unsigned mode, mir_lsq_lm_solve_record_d* rec,
+                       double* dx, double* trial, double* jy_inf, int info[6])
+{
+    return lm_solve_entry<double>(settings, n, JJ, Jy, x, lower, upper, ks, lam, state_lambda, mode, rec, dx, trial, jy_inf, info);
+}
+int mir_lsq_lm_solve_s(const mir_least_squares_settings_s* settings, size_t n, float* JJ, float* Jy, float* x, float* lower,
+                       float* upper, int ks, const float* lam, float state_lambda, unsigned mode, mir_lsq_lm_solve_record_s* rec,
+                       float* dx, float* trial, float* jy_inf, int info[6])
+{
+    return lm_solve_entry<float>(settings, n, JJ, Jy, x, lower, upper, ks, lam, state_lambda, mode, rec, dx, trial, jy_inf, info);
+}
+int mir_lsq_lm_solve_class(size_t elem_size, size_t n, int bounded, int generic, int diagnostic, int out[3])
+{
+    if ((elem_size != 4 && elem_size != 8) || n == 0 || n > (size_t)1 << 20 || !out) return -1;
+    const LmSolveClass c = lm_solve_class((int)elem_size, (int)n, bounded != 0, generic != 0, diagnostic != 0);
+    out[0] = c.kind; out[1] = c.nb; out[2] = c.bounded;
     return 0;
 }
 int mir_lsq_jtj_s(size_t m, size_t n, float* J, const float* y, const float* y_old, const float* dx, int broyden,
