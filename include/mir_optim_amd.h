@@ -749,6 +749,40 @@ int mir_lsq_lm_solve_s(const mir_least_squares_settings_s* settings, size_t n, f
  * loop (always 1 for the any-n kernel) }. Returns 0, or -1 (arguments). */
 int mir_lsq_lm_solve_class(size_t elem_size, size_t n, int bounded, int generic, int diagnostic, int out[3]);
 
+/* Unit-level access to the read-only Broyden sweep (the default path's Broyden pass for n <= 512). J (m x n row-major), U (16
+ * columns of length m), D (16 x n), dx (n), dx_dot (one value: dx.dx), y (count vectors of length m, m apart; vector 0 is the
+ * new residual), y_old (m), JJ (n x n), Jy (n) are DEVICE pointers of the caller's; partials, reduced, sums, jy_inf are HOST
+ * pointers. The call owns the rest of its device memory, keeps no state and synchronises before it returns.
+ * mir_lsq_lr_pass_*: the launches of one pass with k pending terms (0 <= k < 16), in the solver's order and on the solver's
+ * workgroup count nblk = mir_lsq_lr_blocks(m, 0): the sweep (writes column k of U and nblk partial vectors of
+ * len = 2 n + 35 values [ v0 (n) | g0 (n) | w (16) | h (16) | uu | uy | yy ]), their fixed-order sum (`reduced`, len values), the
+ * n x n side (JJ += v dx^T + dx v^T + uu dx dx^T, Jy, row k of D = dx, the state's ||J^T y||_inf -> *jy_inf); then the two-stage
+ * sums of squares of the `count` vectors at y (1 <= count <= 8) -> sums, whose entry 0 has the bits of reduced[len - 1].
+ * spec != NULL: the speculative sweep of a fused round on that record with the two tolerances -- a record after which no Broyden
+ * pass can follow makes the sweep write ||y||^2 and zeros only; the n x n side is NOT run in this mode (it lives in the solve
+ * kernel), JJ, Jy, D and *jy_inf stay as they were.
+ * info = { column-pair chunks a lane (1, 2, 4, 8, 16), 1 = vector loads, nblk, the first guard band that is not intact or -1
+ * (band b in front of: 0 the partials, 1 the reduced vector, 2 the stage-1 partials of the sums, 3 the sums, 4 the state, 5 the
+ * record; 6 behind it), the number of bands, 1: a state field other than jy_inf was written | 2: the record changed }.
+ * mir_lsq_lr_flush_*: J += u_0 dx_0^T + ... + u_{k-1} dx_{k-1}^T in place (1 <= k <= 16); info = { chunks, vector loads }.
+ * Returns 0, -1 (arguments), -2 (no device), -3 (allocation / upload), -4 (launch), -5 (synchronisation / download). */
+int mir_lsq_lr_pass_d(size_t m, size_t n, int k, const double* J, double* U, double* D, const double* dx, const double* dx_dot,
+                      const double* y, int count, const double* y_old, double* JJ, double* Jy, const mir_lsq_lm_solve_record_d* spec,
+                      double absTolerance, double relTolerance, double* partials, double* reduced, double* sums, double* jy_inf,
+                      int info[6]);
+int mir_lsq_lr_pass_s(size_t m, size_t n, int k, const float* J, float* U, float* D, const float* dx, const float* dx_dot,
+                      const float* y, int count, const float* y_old, float* JJ, float* Jy, const mir_lsq_lm_solve_record_s* spec,
+                      float absTolerance, float relTolerance, float* partials, float* reduced, float* sums, float* jy_inf,
+                      int info[6]);
+int mir_lsq_lr_flush_d(size_t m, size_t n, int k, double* J, const double* U, const double* D, int info[2]);
+int mir_lsq_lr_flush_s(size_t m, size_t n, int k, float* J, const float* U, const float* D, int info[2]);
+/* The kernel instance the sweep and the flush run (host code, no device needed): element size 4 / 8, n <= 512, aligned: J lies on
+ * the grid of two elements. out = { chunks a lane, 1 = vector loads (even n and aligned) }. Returns 0, or -1 (arguments). */
+int mir_lsq_lr_class(size_t elem_size, size_t n, int aligned, int out[2]);
+/* Workgroups of the sweep for m rows on num_cu compute units (num_cu <= 0: the current device's). Returns the count (1 .. 1024),
+ * -1 (arguments) or -2 (no device). */
+int mir_lsq_lr_blocks(size_t m, int num_cu);
+
 /* Covariance of the fitted parameters of the general solver: cov = s^2 inv(J^T J) at x (usually the x a solve returned), from
  * ONE full Jacobian refresh made exactly as a refresh of the solve makes it (g if given, else finite differences through the
  * same callbacks, options->fb / fbRowMajor / fbRowMajorDiff, fd_batch and clipping of x +- jacobianEpsilon to [l, u]), the J^T J

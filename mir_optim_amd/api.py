@@ -40,6 +40,7 @@ __all__ = [
     "covariance", "spdInverse", "COVARIANCE_ABSOLUTE_SIGMA",
     "fitSplineGpu", "splineEvalGpu", "fit_spline_eval_gpu", "fit_spline_eval_host", "fit_spline_factor",
     "lmSolve", "lm_solve_class",
+    "lrPass", "lrFlush", "lr_class", "lr_blocks", "lr_len",
 ]
 
 MODEL_EXP_DECAY = 0      # n = 3: p0 exp(-t p1) + p2
@@ -329,6 +330,18 @@ def lib():
                            C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int * 6)]
         L.mir_lsq_lm_solve_class.restype = C.c_int
         L.mir_lsq_lm_solve_class.argtypes = [sz, sz, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int * 3)]
+        for suf, ct in (("d", C.c_double), ("s", C.c_float)):
+            fn = getattr(L, "mir_lsq_lr_pass_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [sz, sz, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 + [ct, ct] + [C.c_void_p] * 4 \
+                + [C.POINTER(C.c_int * 6)]
+            fn = getattr(L, "mir_lsq_lr_flush_" + suf)
+            fn.restype = C.c_int
+            fn.argtypes = [sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int * 2)]
+        L.mir_lsq_lr_class.restype = C.c_int
+        L.mir_lsq_lr_class.argtypes = [sz, sz, C.c_int, C.POINTER(C.c_int * 2)]
+        L.mir_lsq_lr_blocks.restype = C.c_int
+        L.mir_lsq_lr_blocks.argtypes = [sz, C.c_int]
         L.mir_lsq_batched_posvx_s.restype = C.c_int
         L.mir_lsq_batched_posvx_s.argtypes = [sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mir_optimize_least_squares_batched_d.restype = C.c_int
@@ -1010,6 +1023,70 @@ def lmSolve(JJ, Jy, x, lower, upper, lam, settings=None, dtype=np.float64, state
         raise RuntimeError(f"mir_lsq_lm_solve failed: {rc}")
     return {"rec": rec, "dx": dx, "trial": trial, "jy_inf": jy_inf[0], "cls": (LM_SOLVE_KINDS[info[0]], int(info[1]), bool(info[2])),
             "helpers": int(info[3]), "guard": int(info[4]), "bands": int(info[5]), "inputs": (JJ, *vecs)}
+
+
+LR_MAX = 16                 # kLrMax: pending rank-one terms of the read-only Broyden sweep (columns of U, rows of D)
+LR_MAX_N = 512              # kLrMaxN
+LR_MAX_BLOCKS = 1024        # kLrMaxBlocks
+
+
+def lr_len(n):
+    """length of a sweep's partial / reduced vector [ v0 (n) | g0 (n) | w (16) | h (16) | uu | uy | yy ]"""
+    return 2 * n + 2 * LR_MAX + 3
+
+
+def lr_class(elem_size, n, aligned=True):
+    """The instance of the sweep and the flush kernels for n columns (mir_lsq_lr_class; host code, no GPU): (column-pair chunks a
+    lane, True: vector loads)."""
+    out = (C.c_int * 2)()
+    rc = lib().mir_lsq_lr_class(elem_size, n, int(bool(aligned)), C.byref(out))
+    if rc != 0:
+        raise ValueError(f"mir_lsq_lr_class: {rc}")
+    return int(out[0]), bool(out[1])
+
+
+def lr_blocks(m, num_cu=0):
+    """workgroups of the sweep for m rows (mir_lsq_lr_blocks); num_cu = 0: the current device's compute units (needs a GPU)"""
+    rc = lib().mir_lsq_lr_blocks(m, num_cu)
+    if rc < 1:
+        raise ValueError(f"mir_lsq_lr_blocks: {rc}")
+    return rc
+
+
+def lrPass(m, n, k, J, U, D, dx, dx_dot, y, y_old, JJ, Jy, dtype=np.float64, count=1, spec=None, absTolerance=0.0, relTolerance=0.0):
+    """One Broyden pass of the read-only sweep on DEVICE pointers (mir_lsq_lr_pass_d / _s; the header has the contract). spec: None,
+    or a dict with fields of lm_solve_record_dtype (the others zero). Returns a dict: partials (nblk x lr_len(n)), reduced, sums
+    (count), jy_inf, cls (as lr_class), nblk, guard (first damaged band of the call's own regions or -1), bands, touched."""
+    dtype = np.dtype(dtype)
+    nblk, ln = lr_blocks(m), lr_len(n)
+    partials, reduced = np.zeros((nblk, ln), dtype=dtype), np.zeros(ln, dtype=dtype)
+    sums, jy_inf = np.zeros(count, dtype=dtype), np.zeros(1, dtype=dtype)
+    rec = None
+    if spec is not None:
+        rec = np.zeros(1, dtype=lm_solve_record_dtype(dtype))
+        for key, v in spec.items():
+            rec[key] = v
+    info = (C.c_int * 6)()
+    fn = lib().mir_lsq_lr_pass_d if dtype == np.float64 else lib().mir_lsq_lr_pass_s
+    rc = fn(m, n, k, J, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, rec.ctypes.data if rec is not None else None,
+            float(absTolerance), float(relTolerance), partials.ctypes.data, reduced.ctypes.data, sums.ctypes.data, jy_inf.ctypes.data,
+            C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_lr_pass failed: {rc}")
+    if info[2] != nblk:
+        raise RuntimeError(f"mir_lsq_lr_pass ran {info[2]} workgroups, mir_lsq_lr_blocks said {nblk}")
+    return {"partials": partials, "reduced": reduced, "sums": sums, "jy_inf": jy_inf[0], "cls": (int(info[0]), bool(info[1])),
+            "nblk": nblk, "guard": int(info[3]), "bands": int(info[4]), "touched": int(info[5])}
+
+
+def lrFlush(m, n, k, J, U, D, dtype=np.float64):
+    """J += the k pending terms, in place, on DEVICE pointers (mir_lsq_lr_flush_d / _s). Returns the class as lr_class."""
+    info = (C.c_int * 2)()
+    fn = lib().mir_lsq_lr_flush_d if np.dtype(dtype) == np.float64 else lib().mir_lsq_lr_flush_s
+    rc = fn(m, n, k, J, U, D, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_lr_flush failed: {rc}")
+    return int(info[0]), bool(info[1])
 
 
 def _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution):

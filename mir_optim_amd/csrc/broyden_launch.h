@@ -43,6 +43,22 @@ inline int lr_blocks(size_t m, int num_cu)
     return (int)(want ? want : 1);
 }
 
+// The instance of k_broyden_lr / k_lr_flush a launch runs (host code; lr_sweep and lr_flush both switch on it, and
+// mir_lsq_lr_class exports it): NCP column-pair chunks of 32 a lane -- 1, 2, 4, 8, 16 for n <= 32, 64, 128, 256, 512 -- and
+// the 2-element vector loads, which need an even n (every row then starts on a pair) and a J on the grid of 2 elements.
+struct LrClass { int ncp; bool vec; };
+inline LrClass lr_class(int n, bool aligned)
+{
+    const int chunks = (n + 31) / 32;
+    int ncp = 1;
+    while (ncp < chunks) ncp *= 2;
+    return {ncp, n % 2 == 0 && aligned};
+}
+template <typename T> inline LrClass lr_class_of(int n, const T* J)
+{
+    return lr_class(n, reinterpret_cast<uintptr_t>(J) % (2 * sizeof(T)) == 0);
+}
+
 // the sweep: per-workgroup partial vectors -> a.partials (nblk x lr_len(n)); column a.k of U is written
 template <typename T> hipError_t lr_sweep(const LrArgs<T>& a, int nblk, hipStream_t s);
 // fixed-order sum of the partial vectors -> out (lr_len(n)): the all-reduce payload of a Broyden pass

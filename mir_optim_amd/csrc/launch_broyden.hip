@@ -2,6 +2,8 @@
 // (broyden_lr.h) and defines the launch entry points declared in broyden_launch.h.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "broyden_launch.h"
 #include "launch_util.h"
 #include "broyden_lr.h"
@@ -9,37 +11,34 @@
 namespace mirlsq {
 
 namespace {
-template <typename T, int NCP>
-hipError_t lr_sweep_ncp(const LrArgs<T>& a, int nblk, bool vec, hipStream_t s)
+// the one switch over lr_class(): f is called with the NCP and VEC of the instance as compile-time constants
+template <typename F>
+hipError_t lr_dispatch(LrClass c, F&& f)
 {
-    if (vec) MIRLSQ_LAUNCH((k_broyden_lr<T, NCP, true>), dim3(nblk), dim3(256), 0, s, a);
-    else MIRLSQ_LAUNCH((k_broyden_lr<T, NCP, false>), dim3(nblk), dim3(256), 0, s, a);
-    return hipGetLastError();
+#define MIRLSQ_LR_CASE(NCP)                                                                               \
+    case NCP:                                                                                             \
+        return c.vec ? f(std::integral_constant<int, NCP>{}, std::true_type{}) : f(std::integral_constant<int, NCP>{}, std::false_type{});
+    switch (c.ncp) {
+        MIRLSQ_LR_CASE(1)
+        MIRLSQ_LR_CASE(2)
+        MIRLSQ_LR_CASE(4)
+        MIRLSQ_LR_CASE(8)
+        MIRLSQ_LR_CASE(16)    // 256 < n <= 512: one workgroup a CU by registers, still one sweep over J
+    }
+#undef MIRLSQ_LR_CASE
+    return hipErrorInvalidValue;
 }
 }  // namespace
 template <typename T>
 hipError_t lr_sweep(const LrArgs<T>& a, int nblk, hipStream_t s)
 {
     if (a.n > kLrMaxN || a.k < 0 || a.k >= kLrMax) return hipErrorInvalidValue;
-    const bool vec = (a.n % 2 == 0) && (reinterpret_cast<uintptr_t>(a.J) % (2 * sizeof(T)) == 0);
-    const int ncp = (a.n + 31) / 32;
-    if (ncp <= 1) return lr_sweep_ncp<T, 1>(a, nblk, vec, s);
-    if (ncp <= 2) return lr_sweep_ncp<T, 2>(a, nblk, vec, s);
-    if (ncp <= 4) return lr_sweep_ncp<T, 4>(a, nblk, vec, s);
-    if (ncp <= 8) return lr_sweep_ncp<T, 8>(a, nblk, vec, s);
-    return lr_sweep_ncp<T, 16>(a, nblk, vec, s);            // 256 < n <= 512: one workgroup a CU by registers, still one sweep over J
+    return lr_dispatch(lr_class_of<T>(a.n, a.J), [&](auto ncp, auto vec) {
+        MIRLSQ_LAUNCH((k_broyden_lr<T, decltype(ncp)::value, decltype(vec)::value>), dim3(nblk), dim3(256), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
-namespace {
-template <typename T, int NCP>
-hipError_t lr_flush_ncp(T* J, const T* U, const T* D, int k, size_t m, int n, int nblk, bool vec, hipStream_t s)
-{
-    const size_t lds = (size_t)k * n * sizeof(T);
-    if (vec) MIRLSQ_LAUNCH((k_lr_flush<T, NCP, true>), dim3(nblk), dim3(256), lds, s, J, U, D, k, m, n);
-    else MIRLSQ_LAUNCH((k_lr_flush<T, NCP, false>), dim3(nblk), dim3(256), lds, s, J, U, D, k, m, n);
-    return hipGetLastError();
-}
-}  // namespace
 template <typename T>
 hipError_t lr_flush(T* J, const T* U, const T* D, int k, size_t m, int n, int num_cu, hipStream_t s)
 {
@@ -49,13 +48,11 @@ hipError_t lr_flush(T* J, const T* U, const T* D, int k, size_t m, int n, int nu
     size_t blocks = (G + 3) / 4;
     if (blocks > (size_t)num_cu * 8) blocks = (size_t)num_cu * 8;
     if (blocks < 1) blocks = 1;
-    const bool vec = (n % 2 == 0) && (reinterpret_cast<uintptr_t>(J) % (2 * sizeof(T)) == 0);
-    const int ncp = (n + 31) / 32;
-    if (ncp <= 1) return lr_flush_ncp<T, 1>(J, U, D, k, m, n, (int)blocks, vec, s);
-    if (ncp <= 2) return lr_flush_ncp<T, 2>(J, U, D, k, m, n, (int)blocks, vec, s);
-    if (ncp <= 4) return lr_flush_ncp<T, 4>(J, U, D, k, m, n, (int)blocks, vec, s);
-    if (ncp <= 8) return lr_flush_ncp<T, 8>(J, U, D, k, m, n, (int)blocks, vec, s);
-    return lr_flush_ncp<T, 16>(J, U, D, k, m, n, (int)blocks, vec, s);
+    const size_t lds = (size_t)k * n * sizeof(T);
+    return lr_dispatch(lr_class_of<T>(n, J), [&](auto ncp, auto vec) {
+        MIRLSQ_LAUNCH((k_lr_flush<T, decltype(ncp)::value, decltype(vec)::value>), dim3((unsigned)blocks), dim3(256), lds, s, J, U, D, k, m, n);
+        return hipGetLastError();
+    });
 }
 
 template <typename T>

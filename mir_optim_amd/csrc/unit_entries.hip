@@ -1,10 +1,13 @@
 // unit_entries.hip -- unit-level access to the kernels of the path (parity tests, micro-benchmarks) and the standalone
 // BOXCQP entry: mir_solve_box_qp_gpu_* (boxcqp.d:85-102 is D-only), mir_lsq_jtj_*, mir_lsq_fd_jtj_d, mir_lsq_fd_diff_jtj_d,
-// mir_lsq_lm_solve_* (one launch of the LM solve kernels; mir_lsq_lm_solve_class is host code), mir_lsq_selftest_reductions, mir_fit_spline_gpu_eval_* / _eval_host_* / _factor_* (fit_spline_gpu.hip). Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
+// mir_lsq_lm_solve_* (one launch of the LM solve kernels; mir_lsq_lm_solve_class is host code), mir_lsq_lr_pass_* / mir_lsq_lr_flush_*
+// (the read-only Broyden sweep's launches; mir_lsq_lr_class and mir_lsq_lr_blocks are host code), mir_lsq_selftest_reductions, mir_fit_spline_gpu_eval_* / _eval_host_* / _factor_* (fit_spline_gpu.hip). Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
+#include <cstddef>
 #include <cstring>
 #include <memory>
 #include <vector>
 
+#include "broyden_launch.h"
 #include "driver.h"
 #include "fit_spline_gpu.h"
 #include "misc_kernels.h"
@@ -194,6 +197,94 @@ int lm_solve_entry(const S* settings, size_t n_, T* JJ, T* Jy, T* x, T* lower, T
     return 0;
 }
 
+// mir_lsq_lr_pass_*: the launches of Solver::broyden_lowrank behind its flush, without a communicator -- lr_sweep, lr_reduce,
+// lr_finish (not in speculation mode: the fused round's n x n side lives in the solve kernel) on the solver's lr_blocks(m, num_cu)
+// workgroups -- and then lr_sumsq + lr_sumsq_final over `count` m-vectors at y (vector 0 is the sweep's y). J, U, D, dx, dx_dot, y,
+// y_old, JJ, Jy are DEVICE pointers of the caller's; what the solver keeps in its workspace -- the partials, the reduced vector,
+// the stage-1 partials of the sums (pstride = the workgroup count, so that the region ends with the last partial), the sums, the
+// state and the record -- lies in one allocation of the call's, banded as lm_solve_entry's and preset to the same 0xFF bytes.
+template <typename T, typename R>
+int lr_pass_entry(size_t m, size_t n_, int k, const T* J, T* U, T* D, const T* dx, const T* dx_dot, const T* y, int count,
+                  const T* y_old, T* JJ, T* Jy, const R* spec, T absTolerance, T relTolerance, T* partials, T* reduced, T* sums,
+                  T* jy_inf, int info[6])
+{
+    if (!J || !U || !D || !dx || !dx_dot || !y || !y_old || !JJ || !Jy || !partials || !reduced || !sums || !jy_inf || !info) return -1;
+    if (m == 0 || n_ == 0 || n_ > (size_t)kLrMaxN || k < 0 || k >= kLrMax || count < 1 || count > kChainMax) return -1;
+    if (!device_available()) return -2;
+    const int n = (int)n_, len = lr_len(n);
+    const int nblk = lr_blocks(m, query_num_cu());
+    struct Region { size_t off, bytes; };
+    std::vector<Region> reg;
+    size_t off = 0;
+    auto take = [&](size_t cnt, size_t elem) {
+        off = align_up(off + kLmGuardBytes, 256);
+        reg.push_back({off, cnt * elem});
+        off += cnt * elem;
+        return reg.size() - 1;
+    };
+    const size_t rpart = take((size_t)nblk * len, sizeof(T)), rvec = take(len, sizeof(T)), rsp = take((size_t)count * nblk, sizeof(T)),
+                 rsum = take(count, sizeof(T)), rst = take(1, sizeof(LmState<T>)), rrec = take(1, sizeof(ChainRec<T>));
+    const size_t total = align_up(off + kLmGuardBytes, 256);
+    char* base = nullptr;
+    if (hipMalloc((void**)&base, total) != hipSuccess) return -3;
+    auto at = [&](size_t r) { return base + reg[r].off; };
+    const LrClass cls = lr_class_of<T>(n, J);
+    info[0] = cls.ncp; info[1] = cls.vec; info[2] = nblk; info[3] = -1; info[4] = (int)reg.size() + 1; info[5] = 0;
+    ChainRec<T> rec{};
+    if (spec) {
+        rec.lambda = spec->lambda; rec.new_dx_dot = spec->new_dx_dot; rec.predicted = spec->predicted; rec.trial_xnorm = spec->trial_xnorm;
+        rec.qp_status = spec->qp_status; rec.qp_iterations = spec->qp_iterations; rec.flags = spec->flags; rec.pad = spec->reserved;
+    }
+    bool good = hipMemset(base, 0xFF, total) == hipSuccess;
+    if (spec) good = good && hipMemcpy(at(rrec), &rec, sizeof rec, hipMemcpyHostToDevice) == hipSuccess;
+    if (!good) { (void)hipFree(base); return -3; }
+    LrArgs<T> a{};
+    a.J = J; a.U = U; a.D = D; a.dx = dx; a.dx_dot = dx_dot; a.y = y; a.y_old = y_old;
+    a.partials = (T*)at(rpart); a.m = m; a.n = n; a.k = k;
+    a.spec_rec = spec ? (const ChainRec<T>*)at(rrec) : nullptr;
+    a.absTolerance = absTolerance; a.relTolerance = relTolerance;
+    good = lr_sweep<T>(a, nblk, nullptr) == hipSuccess
+        && lr_reduce<T>((const T*)at(rpart), nblk, n, (T*)at(rvec), nullptr) == hipSuccess
+        && (spec || lr_finish<T>((const T*)at(rvec), D, dx, k, n, JJ, Jy, (LmState<T>*)at(rst), nullptr) == hipSuccess)
+        && lr_sumsq<T>(y, m, count, m, (T*)at(rsp), nblk, nblk, nullptr) == hipSuccess
+        && lr_sumsq_final<T>((const T*)at(rsp), nblk, nblk, count, (T*)at(rsum), nullptr) == hipSuccess;
+    if (!good) { (void)hipDeviceSynchronize(); (void)hipFree(base); return -4; }
+    std::unique_ptr<unsigned char[]> img(new unsigned char[total]);
+    good = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess
+        && hipMemcpy(img.get(), base, total, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(base);
+    if (!good) return -5;
+    for (size_t b = 0; b <= reg.size() && info[3] < 0; ++b) {
+        const size_t lo = b ? reg[b - 1].off + reg[b - 1].bytes : 0, hi = b < reg.size() ? reg[b].off : total;
+        for (size_t i = lo; i < hi; ++i)
+            if (img[i] != 0xFF) { info[3] = (int)b; break; }
+    }
+    // the state but for jy_inf, and the record: nobody writes them (info[5]: 1 the state, 2 the record, 3 both)
+    const size_t jlo = offsetof(LmState<T>, jy_inf), jhi = jlo + sizeof(T);
+    for (size_t i = 0; i < sizeof(LmState<T>); ++i)
+        if ((i < jlo || i >= jhi || spec) && img[reg[rst].off + i] != 0xFF) info[5] |= 1;
+    std::vector<unsigned char> want(sizeof rec, 0xFF);
+    if (spec) std::memcpy(want.data(), &rec, sizeof rec);
+    if (std::memcmp(img.get() + reg[rrec].off, want.data(), sizeof rec) != 0) info[5] |= 2;
+    std::memcpy(partials, img.get() + reg[rpart].off, reg[rpart].bytes);
+    std::memcpy(reduced, img.get() + reg[rvec].off, reg[rvec].bytes);
+    std::memcpy(sums, img.get() + reg[rsum].off, reg[rsum].bytes);
+    std::memcpy(jy_inf, img.get() + reg[rst].off + jlo, sizeof(T));
+    return 0;
+}
+
+// mir_lsq_lr_flush_*: one lr_flush on device pointers of the caller's
+template <typename T>
+int lr_flush_entry(size_t m, size_t n, int k, T* J, const T* U, const T* D, int info[2])
+{
+    if (!J || !U || !D || !info || m == 0 || n == 0 || n > (size_t)kLrMaxN || k < 1 || k > kLrMax) return -1;
+    if (!device_available()) return -2;
+    const LrClass cls = lr_class_of<T>((int)n, J);
+    info[0] = cls.ncp; info[1] = cls.vec;
+    if (lr_flush<T>(J, U, D, k, m, (int)n, query_num_cu(), nullptr) != hipSuccess) { (void)hipDeviceSynchronize(); return -4; }
+    return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -5;
+}
+
 template <typename T>
 int jtj_entry(size_t m, size_t n, T* J, const T* y, const T* y_old, const T* dx, int broyden, T* JJ, T* Jy,
               void* stream_, float* kernel_ms)
@@ -321,6 +412,46 @@ int mir_lsq_lm_solve_class(size_t elem_size, size_t n, int bounded, int generic,
     const LmSolveClass c = lm_solve_class((int)elem_size, (int)n, bounded != 0, generic != 0, diagnostic != 0);
     out[0] = c.kind; out[1] = c.nb; out[2] = c.bounded;
     return 0;
+}
+int mir_lsq_lr_pass_d(size_t m, size_t n, int k, const double* J, double* U, double* D, const double* dx, const double* dx_dot,
+                      const double* y, int count, const double* y_old, double* JJ, double* Jy, const mir_lsq_lm_solve_record_d* spec,
+                      double absTolerance, double relTolerance, double* partials, double* reduced, double* sums, double* jy_inf,
+                      int info[6])
+{
+    return lr_pass_entry<double>(m, n, k, J, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, spec, absTolerance, relTolerance, partials,
+                                 reduced, sums, jy_inf, info);
+}
+int mir_lsq_lr_pass_s(size_t m, size_t n, int k, const float* J, float* U, float* D, const float* dx, const float* dx_dot,
+                      const float* y, int count, const float* y_old, float* JJ, float* Jy, const mir_lsq_lm_solve_record_s* spec,
+                      float absTolerance, float relTolerance, float* partials, float* reduced, float* sums, float* jy_inf,
+                      int info[6])
+{
+    return lr_pass_entry<float>(m, n, k, J, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, spec, absTolerance, relTolerance, partials,
+                                reduced, sums, jy_inf, info);
+}
+int mir_lsq_lr_flush_d(size_t m, size_t n, int k, double* J, const double* U, const double* D, int info[2])
+{
+    return lr_flush_entry<double>(m, n, k, J, U, D, info);
+}
+int mir_lsq_lr_flush_s(size_t m, size_t n, int k, float* J, const float* U, const float* D, int info[2])
+{
+    return lr_flush_entry<float>(m, n, k, J, U, D, info);
+}
+int mir_lsq_lr_class(size_t elem_size, size_t n, int aligned, int out[2])
+{
+    if ((elem_size != 4 && elem_size != 8) || n == 0 || n > (size_t)kLrMaxN || !out) return -1;
+    const LrClass c = lr_class((int)n, aligned != 0);
+    out[0] = c.ncp; out[1] = c.vec;
+    return 0;
+}
+int mir_lsq_lr_blocks(size_t m, int num_cu)
+{
+    if (m == 0) return -1;
+    if (num_cu <= 0) {
+        if (!device_available()) return -2;
+        num_cu = query_num_cu();
+    }
+    return lr_blocks(m, num_cu);
 }
 int mir_lsq_jtj_s(size_t m, size_t n, float* J, const float* y, const float* y_old, const float* dx, int broyden,
                   float* JJ, float* Jy, void* stream, float* kernel_ms)
