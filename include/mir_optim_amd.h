@@ -783,6 +783,62 @@ int mir_lsq_lr_class(size_t elem_size, size_t n, int aligned, int out[2]);
  * -1 (arguments) or -2 (no device). */
 int mir_lsq_lr_blocks(size_t m, int num_cu);
 
+/* Unit-level access to the decision and bookkeeping kernels of the general solver's round (csrc/misc_kernels.h). All pointers are
+ * HOST pointers; each call owns its device memory, keeps no state and synchronises. Every region a kernel is handed lies in one
+ * allocation preset to 0xFF bytes with at least 4 KiB of them in front of it and behind it (as mir_lsq_lm_solve_*'s); "guard" below is
+ * the first band that is not intact, or -1, "bands" their number. Return values as mir_lsq_lm_solve_*'s.
+ * mir_lsq_lm_state_*: the device-resident scalars of the LM loop (csrc/solve_types.h, LmState), field for field.
+ * mir_lsq_decide_*: ONE launch of the decision kernel (LS:1080-1161 over a ladder of ks trials, 1 <= ks <= 8) with the solver's
+ * geometry. In and out (each comes back as it is on the device after the launch): state; rec[ks]; sums[ks] (the trials' sums of
+ * squares); x[n]; trial, dx_chain (ks x n); dx_acc[n]; partials (ks x pstride; nparts > 0: sums[k] is first formed from the nparts
+ * stage-1 partials at partials + k pstride; nparts = 0: partials may be NULL). mode: MIR_LSQ_DECIDE_* bits; with MIRROR the state
+ * and the accepted point are also published to pinned, device-mapped host memory preset to 0xFF (host_state, host_x[n] return
+ * it), without it the kernel is given no mirror and both come back as 0xFF bytes. info = { guard, bands } (the mirror's bands
+ * follow the device's: state, x[n]).
+ * mir_lsq_fd_points_*: ONE launch of the finite-difference points (LS:1027-1031) for x, lower, upper (n values each, n <= 4096)
+ * and the step eps: X ((2 n + with_base) x n: row 2 j = x with x_j + eps clipped to upper_j, row 2 j + 1 = x with x_j - eps clipped
+ * to lower_j, with_base: row 2 n = x), twh[n] the widths the device computed, twh_host[n] the solver's host copy of them.
+ * mir_lsq_fd_fill_*: ONE launch of the column fill (LS:1037-1046) for the panel of columns [j0, j0 + pc): Y 2 pc rows of m values,
+ * ldy >= m apart (the two points of column j0 + c in rows 2 c, 2 c + 1), twh[n], J (m x n row-major, in and out). col != 0 (pc = 1):
+ * the single-column kernel of host-callback mode on rows 0 and 1 of Y with twh[j0].
+ * mir_lsq_entry_state_*: the entry of a solve (LS:953-971): the two-stage sum of squares of v[0 .. m) on mir_lsq_sumsq_blocks(m)
+ * workgroups (partials[nb], *sum), the initial state from it (state; host_state its pinned mirror, sequence number seq); then
+ * the same stage 1 on a grid of nb x 2 over v[0 .. m) and v[m .. 2m) (partials2: 2 x nb) and stage 2 on two workgroups (sums2[2]);
+ * then the forced refresh's mu = 1 (LS:984-989) on the image st2. info = { nb, guard, bands }.
+ * mir_lsq_unpack_grad_*: ONE launch that expands packed = [ lower triangle of J^T J by rows | J^T y ] (n (n + 1) / 2 + n values,
+ * n <= 4096) into JJ (n x n), Jy and the state's jy_inf = ||J^T y||_inf (LS:1053); state is an image in and out. */
+typedef struct {
+    double lambda, mu, residual, trial_residual, dx_dot, new_dx_dot, predicted, trial_xnorm, jy_inf, improvement, rho, pad0;
+    int32_t qp_status, qp_iterations, flags, decision; uint32_t iterations; int32_t accepted_k;
+    uint32_t consumed, fcalls, rejects, guards, qp_active, null_tail, seq, coop_rescued; int32_t spec_ok;
+} mir_lsq_lm_state_d;
+typedef struct {
+    float lambda, mu, residual, trial_residual, dx_dot, new_dx_dot, predicted, trial_xnorm, jy_inf, improvement, rho, pad0;
+    int32_t qp_status, qp_iterations, flags, decision; uint32_t iterations; int32_t accepted_k;
+    uint32_t consumed, fcalls, rejects, guards, qp_active, null_tail, seq, coop_rescued; int32_t spec_ok;
+} mir_lsq_lm_state_s;
+enum { MIR_LSQ_DECIDE_CHECK_GRAD = 1u, MIR_LSQ_DECIDE_LAMBDA_FROM_STATE = 2u, MIR_LSQ_DECIDE_SPEC_STATIC = 4u, MIR_LSQ_DECIDE_MIRROR = 8u };
+int mir_lsq_decide_d(const mir_least_squares_settings_d* settings, size_t n, int ks, unsigned mode, uint32_t maxIterations, uint32_t seq,
+                     mir_lsq_lm_state_d* state, mir_lsq_lm_solve_record_d* rec, double* sums, double* x, double* trial, double* dx_chain,
+                     double* dx_acc, double* partials, int nparts, int pstride, mir_lsq_lm_state_d* host_state, double* host_x, int info[2]);
+int mir_lsq_decide_s(const mir_least_squares_settings_s* settings, size_t n, int ks, unsigned mode, uint32_t maxIterations, uint32_t seq,
+                     mir_lsq_lm_state_s* state, mir_lsq_lm_solve_record_s* rec, float* sums, float* x, float* trial, float* dx_chain,
+                     float* dx_acc, float* partials, int nparts, int pstride, mir_lsq_lm_state_s* host_state, float* host_x, int info[2]);
+int mir_lsq_fd_points_d(size_t n, const double* x, const double* lower, const double* upper, double eps, int with_base, double* X,
+                        double* twh, double* twh_host, int info[2]);
+int mir_lsq_fd_points_s(size_t n, const float* x, const float* lower, const float* upper, float eps, int with_base, float* X,
+                        float* twh, float* twh_host, int info[2]);
+int mir_lsq_fd_fill_d(size_t m, size_t n, size_t ldy, int j0, int pc, const double* Y, const double* twh, double* J, int col, int info[2]);
+int mir_lsq_fd_fill_s(size_t m, size_t n, size_t ldy, int j0, int pc, const float* Y, const float* twh, float* J, int col, int info[2]);
+int mir_lsq_entry_state_d(size_t m, const double* v, uint32_t seq, double* partials, double* sum, mir_lsq_lm_state_d* state,
+                          mir_lsq_lm_state_d* host_state, double* partials2, double* sums2, mir_lsq_lm_state_d* st2, int info[3]);
+int mir_lsq_entry_state_s(size_t m, const float* v, uint32_t seq, float* partials, float* sum, mir_lsq_lm_state_s* state,
+                          mir_lsq_lm_state_s* host_state, float* partials2, float* sums2, mir_lsq_lm_state_s* st2, int info[3]);
+/* workgroups of the entry residual's sum of squares for m rows (host code); -1: m == 0 */
+int mir_lsq_sumsq_blocks(size_t m);
+int mir_lsq_unpack_grad_d(size_t n, const double* packed, mir_lsq_lm_state_d* state, double* JJ, double* Jy, int info[2]);
+int mir_lsq_unpack_grad_s(size_t n, const float* packed, mir_lsq_lm_state_s* state, float* JJ, float* Jy, int info[2]);
+
 /* Covariance of the fitted parameters of the general solver: cov = s^2 inv(J^T J) at x (usually the x a solve returned), from
  * ONE full Jacobian refresh made exactly as a refresh of the solve makes it (g if given, else finite differences through the
  * same callbacks, options->fb / fbRowMajor / fbRowMajorDiff, fd_batch and clipping of x +- jacobianEpsilon to [l, u]), the J^T J

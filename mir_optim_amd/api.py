@@ -41,6 +41,7 @@ __all__ = [
     "fitSplineGpu", "splineEvalGpu", "fit_spline_eval_gpu", "fit_spline_eval_host", "fit_spline_factor",
     "lmSolve", "lm_solve_class",
     "lrPass", "lrFlush", "lr_class", "lr_blocks", "lr_len",
+    "lm_state_dtype", "lmDecide", "fdPoints", "fdFill", "entryState", "sumsq_blocks", "unpackGrad",
 ]
 
 MODEL_EXP_DECAY = 0      # n = 3: p0 exp(-t p1) + p2
@@ -342,6 +343,17 @@ def lib():
         L.mir_lsq_lr_class.argtypes = [sz, sz, C.c_int, C.POINTER(C.c_int * 2)]
         L.mir_lsq_lr_blocks.restype = C.c_int
         L.mir_lsq_lr_blocks.argtypes = [sz, C.c_int]
+        vp, i2 = C.c_void_p, C.POINTER(C.c_int * 2)
+        for suf, S, ct in (("d", _Sd, C.c_double), ("s", _Ss, C.c_float)):
+            for name, args in (("decide", [C.POINTER(S), sz, C.c_int, C.c_uint, C.c_uint32, C.c_uint32] + [vp] * 8 + [C.c_int, C.c_int, vp, vp, i2]),
+                               ("fd_points", [sz, vp, vp, vp, ct, C.c_int, vp, vp, vp, i2]),
+                               ("fd_fill", [sz, sz, sz, C.c_int, C.c_int, vp, vp, vp, C.c_int, i2]),
+                               ("entry_state", [sz, vp, C.c_uint32] + [vp] * 7 + [C.POINTER(C.c_int * 3)]),
+                               ("unpack_grad", [sz, vp, vp, vp, vp, i2])):
+                fn = getattr(L, "mir_lsq_%s_%s" % (name, suf))
+                fn.restype, fn.argtypes = C.c_int, args
+        L.mir_lsq_sumsq_blocks.restype = C.c_int
+        L.mir_lsq_sumsq_blocks.argtypes = [sz]
         L.mir_lsq_batched_posvx_s.restype = C.c_int
         L.mir_lsq_batched_posvx_s.argtypes = [sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mir_optimize_least_squares_batched_d.restype = C.c_int
@@ -1087,6 +1099,148 @@ def lrFlush(m, n, k, J, U, D, dtype=np.float64):
     if rc != 0:
         raise RuntimeError(f"mir_lsq_lr_flush failed: {rc}")
     return int(info[0]), bool(info[1])
+
+
+LM_FLAG_TRIAL_NOT_FINITE = 8                       # kFlagTrialNotFinite (set by the decision, not by a solve)
+LM_DECIDE_REJECT, LM_DECIDE_ACCEPT, LM_DECIDE_ACCEPT_NO_PREDICTION, LM_DECIDE_NUMERIC_ERROR, LM_DECIDE_GRAD_SMALL = 1, 2, 3, 4, 5
+LM_STATE_FLOATS = ("lambda", "mu", "residual", "trial_residual", "dx_dot", "new_dx_dot", "predicted", "trial_xnorm", "jy_inf",
+                   "improvement", "rho", "pad0")
+LM_STATE_INTS = (("qp_status", np.int32), ("qp_iterations", np.int32), ("flags", np.int32), ("decision", np.int32),
+                 ("iterations", np.uint32), ("accepted_k", np.int32), ("consumed", np.uint32), ("fcalls", np.uint32),
+                 ("rejects", np.uint32), ("guards", np.uint32), ("qp_active", np.uint32), ("null_tail", np.uint32), ("seq", np.uint32),
+                 ("coop_rescued", np.uint32), ("spec_ok", np.int32))
+
+
+def lm_state_dtype(dtype):
+    """mir_lsq_lm_state_d / _s (the kernels' LmState) as a structured dtype; in double the struct ends with 4 bytes of padding"""
+    f = np.dtype(dtype)
+    names = list(LM_STATE_FLOATS) + [k for k, _ in LM_STATE_INTS]
+    formats = [f] * len(LM_STATE_FLOATS) + [t for _, t in LM_STATE_INTS]
+    offsets = [i * f.itemsize for i in range(12)] + [12 * f.itemsize + 4 * i for i in range(len(LM_STATE_INTS))]
+    size = 12 * f.itemsize + 4 * len(LM_STATE_INTS)
+    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": -(-size // f.itemsize) * f.itemsize})
+
+
+def lmDecide(state, rec, sums, x, trial, dx_chain, dx_acc, settings=None, dtype=np.float64, check_grad=False, lambda_from_state=False,
+             spec_static=False, mirror=True, maxIterations=1000, seq=1, partials=None, nparts=0):
+    """One launch of the decision kernel (mir_lsq_decide_d / _s; the header has the contract). state: one lm_state_dtype element,
+    rec: ks lm_solve_record_dtype elements; partials: ks x pstride or None. Nothing passed in is written. Returns a dict of what
+    is on the device after the launch -- state, rec, sums, x, trial, dx_chain, dx_acc, partials -- plus host_state, host_x (the
+    pinned mirror; bytes of 0xFF without it), guard, bands."""
+    dtype = np.dtype(dtype)
+    state = np.array(state, dtype=lm_state_dtype(dtype)).reshape(1).copy()
+    rec = np.array(rec, dtype=lm_solve_record_dtype(dtype)).reshape(-1).copy()
+    ks = rec.size
+    x, dx_acc = (np.array(v, dtype=dtype, order="C").reshape(-1) for v in (x, dx_acc))
+    n = x.size
+    sums = np.array(sums, dtype=dtype, order="C").reshape(-1)
+    trial, dx_chain = (np.array(v, dtype=dtype, order="C") for v in (trial, dx_chain))
+    if sums.shape != (ks,) or trial.shape != (ks, n) or dx_chain.shape != (ks, n) or dx_acc.shape != (n,):
+        raise ValueError("lmDecide: sums ks, trial and dx_chain ks x n, x and dx_acc n values")
+    pstride = 0
+    if nparts:
+        partials = np.array(partials, dtype=dtype, order="C")
+        if partials.ndim != 2 or partials.shape[0] != ks:
+            raise ValueError("lmDecide: partials ks x pstride")
+        pstride = partials.shape[1]
+    else:
+        partials = None
+    if settings is None:
+        settings = LeastSquaresSettings(dtype.type)
+    host_state = np.zeros(1, dtype=lm_state_dtype(dtype))
+    host_x = np.zeros(n, dtype=dtype)
+    info = (C.c_int * 2)()
+    mode = (1 if check_grad else 0) | (2 if lambda_from_state else 0) | (4 if spec_static else 0) | (8 if mirror else 0)
+    fn = lib().mir_lsq_decide_d if dtype == np.float64 else lib().mir_lsq_decide_s
+    rc = fn(C.byref(settings), n, ks, mode, maxIterations, seq, state.ctypes.data, rec.ctypes.data, sums.ctypes.data, x.ctypes.data,
+            trial.ctypes.data, dx_chain.ctypes.data, dx_acc.ctypes.data, partials.ctypes.data if partials is not None else None,
+            nparts, pstride, host_state.ctypes.data, host_x.ctypes.data, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_decide failed: {rc}")
+    return {"state": state, "rec": rec, "sums": sums, "x": x, "trial": trial, "dx_chain": dx_chain, "dx_acc": dx_acc,
+            "partials": partials, "host_state": host_state, "host_x": host_x, "guard": int(info[0]), "bands": int(info[1])}
+
+
+def fdPoints(x, lower, upper, eps, dtype=np.float64, with_base=False):
+    """One launch of the finite-difference points (mir_lsq_fd_points_d / _s). Returns a dict: X ((2 n + with_base) x n), twh (the
+    device's widths), twh_host (the solver's host copy of the same arithmetic), guard, bands."""
+    dtype = np.dtype(dtype)
+    x, lower, upper = (np.array(v, dtype=dtype, order="C").reshape(-1) for v in (x, lower, upper))
+    n = x.size
+    X = np.zeros((2 * n + (1 if with_base else 0), n), dtype=dtype)
+    twh, twh_host = np.zeros(n, dtype=dtype), np.zeros(n, dtype=dtype)
+    info = (C.c_int * 2)()
+    fn = lib().mir_lsq_fd_points_d if dtype == np.float64 else lib().mir_lsq_fd_points_s
+    rc = fn(n, x.ctypes.data, lower.ctypes.data, upper.ctypes.data, float(dtype.type(eps)), int(bool(with_base)), X.ctypes.data, twh.ctypes.data,
+            twh_host.ctypes.data, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_fd_points failed: {rc}")
+    return {"X": X, "twh": twh, "twh_host": twh_host, "guard": int(info[0]), "bands": int(info[1])}
+
+
+def fdFill(Y, twh, J, j0, pc, dtype=np.float64, col=False):
+    """One launch of the finite-difference column fill (mir_lsq_fd_fill_d / _s): Y 2 pc x ldy, twh n, J m x n (not written: the
+    filled copy is returned), panel [j0, j0 + pc); col: the single-column kernel. Returns a dict: J, guard, bands."""
+    dtype = np.dtype(dtype)
+    Y, twh, J = np.array(Y, dtype=dtype, order="C"), np.array(twh, dtype=dtype, order="C").reshape(-1), np.array(J, dtype=dtype, order="C")
+    m, n = J.shape
+    if Y.shape[0] != 2 * pc or Y.shape[1] < m or twh.size != n:
+        raise ValueError("fdFill: Y 2 pc x ldy with ldy >= m, twh n values")
+    info = (C.c_int * 2)()
+    fn = lib().mir_lsq_fd_fill_d if dtype == np.float64 else lib().mir_lsq_fd_fill_s
+    rc = fn(m, n, Y.shape[1], j0, pc, Y.ctypes.data, twh.ctypes.data, J.ctypes.data, int(bool(col)), C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_fd_fill failed: {rc}")
+    return {"J": J, "guard": int(info[0]), "bands": int(info[1])}
+
+
+def sumsq_blocks(m):
+    """workgroups of the entry residual's sum of squares (mir_lsq_sumsq_blocks; host code, no GPU)"""
+    rc = lib().mir_lsq_sumsq_blocks(m)
+    if rc < 1:
+        raise ValueError(f"mir_lsq_sumsq_blocks: {rc}")
+    return rc
+
+
+def entryState(v, st2, dtype=np.float64, seq=1):
+    """The entry of a solve (mir_lsq_entry_state_d / _s): v 2 x m (row 0 is the residual vector), st2 one lm_state_dtype element
+    for the mu reset. Returns a dict: partials (nb), sum, state, host_state, partials2 (2 x nb), sums2 (2), st2, nb, guard, bands."""
+    dtype = np.dtype(dtype)
+    v = np.array(v, dtype=dtype, order="C")
+    if v.ndim != 2 or v.shape[0] != 2:
+        raise ValueError("entryState: v 2 x m")
+    m = v.shape[1]
+    nb = sumsq_blocks(m)
+    partials, s, partials2, sums2 = np.zeros(nb, dtype=dtype), np.zeros(1, dtype=dtype), np.zeros((2, nb), dtype=dtype), np.zeros(2, dtype=dtype)
+    state, host_state = np.zeros(1, dtype=lm_state_dtype(dtype)), np.zeros(1, dtype=lm_state_dtype(dtype))
+    st2 = np.array(st2, dtype=lm_state_dtype(dtype)).reshape(1).copy()
+    info = (C.c_int * 3)()
+    fn = lib().mir_lsq_entry_state_d if dtype == np.float64 else lib().mir_lsq_entry_state_s
+    rc = fn(m, v.ctypes.data, seq, partials.ctypes.data, s.ctypes.data, state.ctypes.data, host_state.ctypes.data, partials2.ctypes.data,
+            sums2.ctypes.data, st2.ctypes.data, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_entry_state failed: {rc}")
+    if info[0] != nb:
+        raise RuntimeError(f"mir_lsq_entry_state ran {info[0]} workgroups, mir_lsq_sumsq_blocks said {nb}")
+    return {"partials": partials, "sum": s[0], "state": state, "host_state": host_state, "partials2": partials2, "sums2": sums2,
+            "st2": st2, "nb": nb, "guard": int(info[1]), "bands": int(info[2])}
+
+
+def unpackGrad(packed, n, state, dtype=np.float64):
+    """One launch that expands the packed [J^T J lower | J^T y] buffer (mir_lsq_unpack_grad_d / _s). Returns a dict: JJ, Jy, state
+    (the image after the launch: jy_inf written), guard, bands."""
+    dtype = np.dtype(dtype)
+    packed = np.array(packed, dtype=dtype, order="C").reshape(-1)
+    if packed.size != n * (n + 1) // 2 + n:
+        raise ValueError("unpackGrad: n (n + 1) / 2 + n values")
+    state = np.array(state, dtype=lm_state_dtype(dtype)).reshape(1).copy()
+    JJ, Jy = np.zeros((n, n), dtype=dtype), np.zeros(n, dtype=dtype)
+    info = (C.c_int * 2)()
+    fn = lib().mir_lsq_unpack_grad_d if dtype == np.float64 else lib().mir_lsq_unpack_grad_s
+    rc = fn(n, packed.ctypes.data, state.ctypes.data, JJ.ctypes.data, Jy.ctypes.data, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_unpack_grad failed: {rc}")
+    return {"JJ": JJ, "Jy": Jy, "state": state, "guard": int(info[0]), "bands": int(info[1])}
 
 
 def _box_qp_batched_pack(P, q, l, u, x, dtype, unconstrainedSolution):

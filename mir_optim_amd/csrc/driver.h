@@ -132,6 +132,27 @@ struct Buffers {
 
 constexpr int kPartials = 1024;
 
+// workgroups of the entry residual's two-stage sum of squares (Solver::sumsq, LS:955): 4096 rows each, at most kPartials
+inline int sumsq_blocks(size_t m)
+{
+    int nb = (int)((m + 4095) / 4096);
+    if (nb > kPartials) nb = kPartials;
+    return nb < 1 ? 1 : nb;
+}
+
+// the interval widths of k_fd_points with the same arithmetic on the host (LS:1027-1033): twh[j] = min(x_j + eps, u_j) - max(x_j - eps, l_j)
+template <typename T>
+inline void fd_widths(const T* x, const T* lower, const T* upper, T eps, size_t n, T* twh)
+{
+    for (size_t j = 0; j < n; ++j) {
+        const T save = x[j];
+        T xmh = save - eps, xph = save + eps;
+        xmh = std::fmax(xmh, lower[j]);
+        xph = std::fmin(xph, upper[j]);
+        twh[j] = xph - xmh;
+    }
+}
+
 template <typename T> Buffers<T> carve(void* base, size_t m, size_t n, int num_cu);
 template <typename T> mir_lsq_workspace* workspace_create(size_t m, size_t n);
 void workspace_destroy(mir_lsq_workspace* ws);
@@ -284,7 +305,6 @@ struct Solver {
     bool setup();
     void teardown();
     bool eval_f(const T* x_dev, const T* x_host, T* y_dev);
-    int sumsq_blocks() const;
     bool sumsq(const T* v, int slot);
     bool trial_sums(const T* v, int count, size_t vstride);
     bool allreduce(T* buf, size_t count, int kind);

@@ -105,13 +105,7 @@ bool Solver<T>::jacobian_products(bool broyden, const T* y_dev, const T* yold_de
 template <typename T>
 void Solver<T>::fd_widths_host()
 {
-    for (uint32_t j = 0; j < n; ++j) {
-        const T save = xh[j];
-        T xmh = save - S->jacobianEpsilon, xph = save + S->jacobianEpsilon;
-        xmh = std::fmax(xmh, lh[j]);
-        xph = std::fmin(xph, uh[j]);
-        twh_h[j] = xph - xmh;
-    }
+    fd_widths<T>(xh, lh, uh, S->jacobianEpsilon, n, twh_h.data());
 }
 
 // The panel of a device-callback refresh, decided in ONE place for fd_device() and fd_entry(): pb, the columns per callback

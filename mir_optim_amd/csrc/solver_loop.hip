@@ -156,16 +156,9 @@ bool Solver<T>::eval_f(const T* x_dev, const T* x_host, T* y_dev)
 
 // ---- ||v||^2 -> B.sum[slot] on device (all-reduced over row shards): the residual at entry, LS:955
 template <typename T>
-int Solver<T>::sumsq_blocks() const
-{
-    int nb = (int)((m + 4095) / 4096);
-    if (nb > kPartials) nb = kPartials;
-    return nb < 1 ? 1 : nb;
-}
-template <typename T>
 bool Solver<T>::sumsq(const T* v, int slot)
 {
-    const int nb = sumsq_blocks();
+    const int nb = sumsq_blocks(m);
     MIRLSQ_LAUNCH(k_sumsq_partial<T>, dim3(nb), dim3(256), 0, stream, v, m, B.partials, (size_t)0, kPartials);
     MIRLSQ_LAUNCH(k_sumsq_final<T>, dim3(1), dim3(256), 0, stream, B.partials, nb, B.sum + slot, kPartials);
     if (comm && !allreduce(B.sum + slot, 1, 2)) return false;

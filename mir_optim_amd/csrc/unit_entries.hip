@@ -1,7 +1,9 @@
 // unit_entries.hip -- unit-level access to the kernels of the path (parity tests, micro-benchmarks) and the standalone
 // BOXCQP entry: mir_solve_box_qp_gpu_* (boxcqp.d:85-102 is D-only), mir_lsq_jtj_*, mir_lsq_fd_jtj_d, mir_lsq_fd_diff_jtj_d,
 // mir_lsq_lm_solve_* (one launch of the LM solve kernels; mir_lsq_lm_solve_class is host code), mir_lsq_lr_pass_* / mir_lsq_lr_flush_*
-// (the read-only Broyden sweep's launches; mir_lsq_lr_class and mir_lsq_lr_blocks are host code), mir_lsq_selftest_reductions, mir_fit_spline_gpu_eval_* / _eval_host_* / _factor_* (fit_spline_gpu.hip). Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
+// (the read-only Broyden sweep's launches; mir_lsq_lr_class and mir_lsq_lr_blocks are host code), mir_lsq_decide_* / mir_lsq_fd_points_* /
+// mir_lsq_fd_fill_* / mir_lsq_entry_state_* / mir_lsq_unpack_grad_* (the decision and bookkeeping kernels of misc_kernels.h, one launch
+// each between guard bands; mir_lsq_sumsq_blocks is host code), mir_lsq_selftest_reductions, mir_fit_spline_gpu_eval_* / _eval_host_* / _factor_* (fit_spline_gpu.hip). Each call owns its scratch and synchronises before it returns. mir_lsq_jtj_plan is host code.
 #include <cstddef>
 #include <cstring>
 #include <memory>
@@ -285,6 +287,219 @@ int lr_flush_entry(size_t m, size_t n, int k, T* J, const T* U, const T* D, int 
     return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -5;
 }
 
+// The allocation of the entries below: regions between guard bands as lm_solve_entry lays them out (at least kLmGuardBytes of
+// 0xFF bytes in front of each region and behind the last, regions 256-byte aligned, band b in front of region b), everything
+// preset to 0xFF. Device memory, or -- pinned -- device-mapped coherent host memory as the solver's mirror (workspace.hip).
+struct Banded {
+    struct Region { size_t off, bytes; };
+    std::vector<Region> reg;
+    size_t off = 0, total = 0;
+    bool pinned = false;
+    char* base = nullptr;        // the address the kernels are given
+    char* host = nullptr;        // pinned: the host's address of the same memory
+    std::unique_ptr<unsigned char[]> img;
+    ~Banded() { if (pinned) { if (host) (void)hipHostFree(host); } else if (base) (void)hipFree(base); }
+    size_t take(size_t count, size_t elem)
+    {
+        off = align_up(off + kLmGuardBytes, 256);
+        reg.push_back({off, count * elem});
+        off += count * elem;
+        return reg.size() - 1;
+    }
+    bool alloc(bool pinned_ = false)
+    {
+        pinned = pinned_;
+        total = align_up(off + kLmGuardBytes, 256);
+        if (pinned) {
+            if (hipHostMalloc((void**)&host, total, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { host = nullptr; return false; }
+            std::memset(host, 0xFF, total);
+            return hipHostGetDevicePointer((void**)&base, host, 0) == hipSuccess;
+        }
+        if (hipMalloc((void**)&base, total) != hipSuccess) { base = nullptr; return false; }
+        return hipMemset(base, 0xFF, total) == hipSuccess;
+    }
+    char* at(size_t r) const { return base + reg[r].off; }
+    bool up(size_t r, const void* src, size_t bytes) const
+    {
+        if (bytes > reg[r].bytes) return false;
+        if (!bytes) return true;
+        if (pinned) { std::memcpy(host + reg[r].off, src, bytes); return true; }
+        return hipMemcpy(at(r), src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    bool up(size_t r, const void* src) const { return up(r, src, reg[r].bytes); }
+    bool fetch()                 // behind a device synchronisation
+    {
+        img.reset(new unsigned char[total]);
+        if (pinned) { std::memcpy(img.get(), host, total); return true; }
+        return hipMemcpy(img.get(), base, total, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    int damaged() const          // the first band that is not intact, or -1
+    {
+        for (size_t b = 0; b <= reg.size(); ++b) {
+            const size_t lo = b ? reg[b - 1].off + reg[b - 1].bytes : 0, hi = b < reg.size() ? reg[b].off : total;
+            for (size_t i = lo; i < hi; ++i)
+                if (img[i] != 0xFF) return (int)b;
+        }
+        return -1;
+    }
+    int bands() const { return (int)reg.size() + 1; }
+    void down(size_t r, void* dst) const { if (reg[r].bytes) std::memcpy(dst, img.get() + reg[r].off, reg[r].bytes); }
+};
+inline bool launches_done() { return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess; }
+
+template <typename T> struct StateAbi;
+template <> struct StateAbi<double> { using type = mir_lsq_lm_state_d; using rec = mir_lsq_lm_solve_record_d; };
+template <> struct StateAbi<float> { using type = mir_lsq_lm_state_s; using rec = mir_lsq_lm_solve_record_s; };
+template <typename T> constexpr bool state_abi_ok()
+{
+    using A = typename StateAbi<T>::type;
+    return sizeof(A) == sizeof(LmState<T>) && offsetof(A, jy_inf) == offsetof(LmState<T>, jy_inf)
+        && offsetof(A, qp_status) == offsetof(LmState<T>, qp_status) && offsetof(A, iterations) == offsetof(LmState<T>, iterations)
+        && offsetof(A, null_tail) == offsetof(LmState<T>, null_tail) && offsetof(A, seq) == offsetof(LmState<T>, seq)
+        && offsetof(A, coop_rescued) == offsetof(LmState<T>, coop_rescued) && offsetof(A, spec_ok) == offsetof(LmState<T>, spec_ok)
+        && sizeof(typename StateAbi<T>::rec) == sizeof(ChainRec<T>) && offsetof(typename StateAbi<T>::rec, flags) == offsetof(ChainRec<T>, flags);
+}
+static_assert(state_abi_ok<double>() && state_abi_ok<float>(), "mir_lsq_lm_state_* / mir_lsq_lm_solve_record_* are LmState / ChainRec");
+
+// mir_lsq_decide_*: ONE k_decide_chain launch with the solver's geometry (Solver::enqueue_decide) on host operands.
+template <typename T, typename S>
+int decide_entry(const S* settings, size_t n_, int ks, unsigned mode, uint32_t maxIterations, uint32_t seq, void* state, void* rec,
+                 T* sums, T* x, T* trial, T* dx_chain, T* dx_acc, T* partials, int nparts, int pstride, void* host_state, T* host_x,
+                 int info[2])
+{
+    if (!settings || !state || !rec || !sums || !x || !trial || !dx_chain || !dx_acc || !host_state || !host_x || !info) return -1;
+    if (n_ == 0 || n_ > (size_t)1 << 20 || ks < 1 || ks > kChainMax || (mode & ~15u)) return -1;
+    if (nparts < 0 || (nparts > 0 && (!partials || pstride < nparts))) return -1;
+    if (!device_available()) return -2;
+    const int n = (int)n_;
+    const bool mirror = (mode & MIR_LSQ_DECIDE_MIRROR) != 0;
+    Banded d, p;
+    const size_t rsum = d.take(ks, sizeof(T)), rrec = d.take(ks, sizeof(ChainRec<T>)), rst = d.take(1, sizeof(LmState<T>)),
+                 rx = d.take(n, sizeof(T)), rtr = d.take((size_t)ks * n, sizeof(T)), rdc = d.take((size_t)ks * n, sizeof(T)),
+                 rda = d.take(n, sizeof(T)), rpa = d.take(nparts > 0 ? (size_t)ks * pstride : 0, sizeof(T));
+    const size_t pst = p.take(1, sizeof(LmState<T>)), px = p.take(n, sizeof(T));
+    if (!d.alloc() || (mirror && !p.alloc(true))) return -3;
+    bool good = d.up(rsum, sums) && d.up(rrec, rec) && d.up(rst, state) && d.up(rx, x) && d.up(rtr, trial) && d.up(rdc, dx_chain)
+        && d.up(rda, dx_acc) && d.up(rpa, partials);
+    if (!good) return -3;
+    DecideArgs<T> a{};
+    a.sums = (T*)d.at(rsum); a.rec = (const ChainRec<T>*)d.at(rrec); a.st = (LmState<T>*)d.at(rst); a.set = lm_settings_dev(settings);
+    a.x = (T*)d.at(rx); a.trial = (const T*)d.at(rtr); a.dx_chain = (const T*)d.at(rdc); a.dx_acc = (T*)d.at(rda);
+    a.n = n; a.ks = ks; a.check_grad = (mode & MIR_LSQ_DECIDE_CHECK_GRAD) ? 1 : 0;
+    a.lambda_from_state = (mode & MIR_LSQ_DECIDE_LAMBDA_FROM_STATE) ? 1 : 0;
+    a.host_st = mirror ? (LmState<T>*)p.at(pst) : nullptr; a.host_x = mirror ? (T*)p.at(px) : nullptr; a.seq = seq;
+    a.spec_static = (mode & MIR_LSQ_DECIDE_SPEC_STATIC) ? 1 : 0; a.maxIterations = maxIterations;
+    a.partials = (const T*)d.at(rpa); a.nparts = nparts; a.pstride = pstride;
+    hipLaunchKernelGGL(k_decide_chain<T>, dim3(1), dim3(kSolveThreads), 0, nullptr, a);
+    if (!launches_done() || !d.fetch() || (mirror && !p.fetch())) return -5;
+    info[0] = d.damaged(); info[1] = d.bands() + (mirror ? p.bands() : 0);
+    if (info[0] < 0 && mirror && p.damaged() >= 0) info[0] = d.bands() + p.damaged();
+    d.down(rsum, sums); d.down(rrec, rec); d.down(rst, state); d.down(rx, x); d.down(rtr, trial); d.down(rdc, dx_chain);
+    d.down(rda, dx_acc); d.down(rpa, partials);
+    std::memset(host_state, 0xFF, sizeof(LmState<T>));
+    std::memset(host_x, 0xFF, sizeof(T) * n);
+    if (mirror) { p.down(pst, host_state); p.down(px, host_x); }
+    return 0;
+}
+
+// mir_lsq_fd_points_*: ONE k_fd_points launch (64 threads; n workgroups, n + 1 with the base row) and the host's widths
+template <typename T>
+int fd_points_entry(size_t n_, const T* x, const T* lower, const T* upper, T eps, int with_base, T* X, T* twh, T* twh_host, int info[2])
+{
+    if (!x || !lower || !upper || !X || !twh || !twh_host || !info || n_ == 0 || n_ > 4096) return -1;
+    if (!device_available()) return -2;
+    const int n = (int)n_;
+    const size_t rows = 2 * n_ + (with_base ? 1 : 0);
+    Banded d;
+    const size_t rx = d.take(n, sizeof(T)), rlo = d.take(n, sizeof(T)), rup = d.take(n, sizeof(T)), rX = d.take(rows * n, sizeof(T)),
+                 rt = d.take(n, sizeof(T));
+    if (!d.alloc() || !d.up(rx, x) || !d.up(rlo, lower) || !d.up(rup, upper)) return -3;
+    hipLaunchKernelGGL(k_fd_points<T>, dim3(n + (with_base ? 1 : 0)), dim3(64), 0, nullptr, (const T*)d.at(rx), (const T*)d.at(rlo),
+                       (const T*)d.at(rup), eps, n, (T*)d.at(rX), (T*)d.at(rt));
+    if (!launches_done() || !d.fetch()) return -5;
+    info[0] = d.damaged(); info[1] = d.bands();
+    d.down(rX, X); d.down(rt, twh);
+    fd_widths<T>(x, lower, upper, eps, n_, twh_host);
+    return 0;
+}
+
+// mir_lsq_fd_fill_*: ONE k_fd_fill launch on the grid of Solver::fd_device, or (col) ONE k_fd_fill_col launch as Solver::fd_task's
+template <typename T>
+int fd_fill_entry(size_t m, size_t n_, size_t ldy, int j0, int pc, const T* Y, const T* twh, T* J, int col, int info[2])
+{
+    if (!Y || !twh || !J || !info || m == 0 || n_ == 0 || n_ > 4096 || m > (size_t)1 << 24 || ldy < m) return -1;
+    if (j0 < 0 || pc < 1 || (size_t)j0 + pc > n_ || (col && pc != 1)) return -1;
+    if (!device_available()) return -2;
+    const int n = (int)n_;
+    Banded d;
+    // the panel ends with its last row's m-th element: a read behind it is a NaN
+    const size_t ry = d.take((size_t)(2 * pc - 1) * ldy + m, sizeof(T)), rt = d.take(n, sizeof(T)), rJ = d.take(m * n_, sizeof(T));
+    if (!d.alloc() || !d.up(ry, Y) || !d.up(rt, twh) || !d.up(rJ, J)) return -3;
+    const T* Yd = (const T*)d.at(ry);
+    if (col) {
+        hipLaunchKernelGGL(k_fd_fill_col<T>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, Yd, Yd + ldy, twh[j0], (T*)d.at(rJ),
+                           m, n, j0);
+    } else {
+        dim3 grid((unsigned)((m + 63) / 64), (unsigned)((pc + 31) / 32));
+        hipLaunchKernelGGL(k_fd_fill<T>, grid, dim3(256), 0, nullptr, Yd, ldy, (const T*)d.at(rt), (T*)d.at(rJ), m, n, j0, pc);
+    }
+    if (!launches_done() || !d.fetch()) return -5;
+    info[0] = d.damaged(); info[1] = d.bands();
+    d.down(rJ, J);
+    return 0;
+}
+
+// mir_lsq_entry_state_*: the launches of Solver::sumsq on sumsq_blocks(m) workgroups and k_init_state with a mirror (the entry of
+// a solve, LS:953-971); then k_sumsq_partial on a grid of (nb, 2) over the two vectors at v (m apart, nb partials each) with
+// k_sumsq_final on two workgroups; then k_reset_mu on the state image st2.
+template <typename T>
+int entry_state_entry(size_t m, const T* v, uint32_t seq, T* partials, T* sum, void* state, void* host_state, T* partials2, T* sums2,
+                      void* st2, int info[3])
+{
+    if (!v || !partials || !sum || !state || !host_state || !partials2 || !sums2 || !st2 || !info || m == 0 || m > (size_t)1 << 28) return -1;
+    if (!device_available()) return -2;
+    const int nb = sumsq_blocks(m);
+    Banded d, p;
+    const size_t rv = d.take(2 * m, sizeof(T)), rp = d.take(nb, sizeof(T)), rs = d.take(1, sizeof(T)), rst = d.take(1, sizeof(LmState<T>)),
+                 rp2 = d.take((size_t)2 * nb, sizeof(T)), rs2 = d.take(2, sizeof(T)), rst2 = d.take(1, sizeof(LmState<T>));
+    const size_t pst = p.take(1, sizeof(LmState<T>));
+    if (!d.alloc() || !p.alloc(true) || !d.up(rv, v) || !d.up(rst2, st2)) return -3;
+    const T* vd = (const T*)d.at(rv);
+    hipLaunchKernelGGL(k_sumsq_partial<T>, dim3(nb), dim3(256), 0, nullptr, vd, m, (T*)d.at(rp), (size_t)0, kPartials);
+    hipLaunchKernelGGL(k_sumsq_final<T>, dim3(1), dim3(256), 0, nullptr, (const T*)d.at(rp), nb, (T*)d.at(rs), kPartials);
+    hipLaunchKernelGGL(k_init_state<T>, dim3(1), dim3(1), 0, nullptr, (const T*)d.at(rs), (LmState<T>*)d.at(rst), (LmState<T>*)p.at(pst), seq);
+    hipLaunchKernelGGL(k_sumsq_partial<T>, dim3(nb, 2), dim3(256), 0, nullptr, vd, m, (T*)d.at(rp2), m, nb);
+    hipLaunchKernelGGL(k_sumsq_final<T>, dim3(2), dim3(256), 0, nullptr, (const T*)d.at(rp2), nb, (T*)d.at(rs2), nb);
+    hipLaunchKernelGGL(k_reset_mu<T>, dim3(1), dim3(1), 0, nullptr, (LmState<T>*)d.at(rst2));
+    if (!launches_done() || !d.fetch() || !p.fetch()) return -5;
+    info[0] = nb; info[1] = d.damaged(); info[2] = d.bands() + p.bands();
+    if (info[1] < 0 && p.damaged() >= 0) info[1] = d.bands() + p.damaged();
+    d.down(rp, partials); d.down(rs, sum); d.down(rst, state); d.down(rp2, partials2); d.down(rs2, sums2); d.down(rst2, st2);
+    p.down(pst, host_state);
+    return 0;
+}
+
+// mir_lsq_unpack_grad_*: ONE jtj_unpack (k_unpack_grad on n + 1 workgroups of 128 threads) on a packed buffer and a state image
+template <typename T>
+int unpack_grad_entry(size_t n_, const T* packed, void* state, T* JJ, T* Jy, int info[2])
+{
+    if (!packed || !state || !JJ || !Jy || !info || n_ == 0 || n_ > 4096) return -1;
+    if (!device_available()) return -2;
+    const int n = (int)n_;
+    Banded d;
+    const size_t rp = d.take(n_ * (n_ + 1) / 2 + n_, sizeof(T)), rJJ = d.take(n_ * n_, sizeof(T)), rJy = d.take(n_, sizeof(T)),
+                 rst = d.take(1, sizeof(LmState<T>));
+    if (!d.alloc() || !d.up(rp, packed) || !d.up(rst, state)) return -3;
+    if (jtj_unpack<T>((const T*)d.at(rp), n, (T*)d.at(rJJ), (T*)d.at(rJy), (LmState<T>*)d.at(rst), nullptr) != hipSuccess) {
+        (void)hipDeviceSynchronize();
+        return -4;
+    }
+    if (!launches_done() || !d.fetch()) return -5;
+    info[0] = d.damaged(); info[1] = d.bands();
+    d.down(rJJ, JJ); d.down(rJy, Jy); d.down(rst, state);
+    return 0;
+}
+
 template <typename T>
 int jtj_entry(size_t m, size_t n, T* J, const T* y, const T* y_old, const T* dx, int broyden, T* JJ, T* Jy,
               void* stream_, float* kernel_ms)
@@ -452,6 +667,57 @@ int mir_lsq_lr_blocks(size_t m, int num_cu)
         num_cu = query_num_cu();
     }
     return lr_blocks(m, num_cu);
+}
+int mir_lsq_decide_d(const mir_least_squares_settings_d* settings, size_t n, int ks, unsigned mode, uint32_t maxIterations, uint32_t seq,
+                     mir_lsq_lm_state_d* state, mir_lsq_lm_solve_record_d* rec, double* sums, double* x, double* trial, double* dx_chain,
+                     double* dx_acc, double* partials, int nparts, int pstride, mir_lsq_lm_state_d* host_state, double* host_x, int info[2])
+{
+    return decide_entry<double>(settings, n, ks, mode, maxIterations, seq, state, rec, sums, x, trial, dx_chain, dx_acc, partials, nparts,
+                                pstride, host_state, host_x, info);
+}
+int mir_lsq_decide_s(const mir_least_squares_settings_s* settings, size_t n, int ks, unsigned mode, uint32_t maxIterations, uint32_t seq,
+                     mir_lsq_lm_state_s* state, mir_lsq_lm_solve_record_s* rec, float* sums, float* x, float* trial, float* dx_chain,
+                     float* dx_acc, float* partials, int nparts, int pstride, mir_lsq_lm_state_s* host_state, float* host_x, int info[2])
+{
+    return decide_entry<float>(settings, n, ks, mode, maxIterations, seq, state, rec, sums, x, trial, dx_chain, dx_acc, partials, nparts,
+                               pstride, host_state, host_x, info);
+}
+int mir_lsq_fd_points_d(size_t n, const double* x, const double* lower, const double* upper, double eps, int with_base, double* X,
+                        double* twh, double* twh_host, int info[2])
+{
+    return fd_points_entry<double>(n, x, lower, upper, eps, with_base, X, twh, twh_host, info);
+}
+int mir_lsq_fd_points_s(size_t n, const float* x, const float* lower, const float* upper, float eps, int with_base, float* X,
+                        float* twh, float* twh_host, int info[2])
+{
+    return fd_points_entry<float>(n, x, lower, upper, eps, with_base, X, twh, twh_host, info);
+}
+int mir_lsq_fd_fill_d(size_t m, size_t n, size_t ldy, int j0, int pc, const double* Y, const double* twh, double* J, int col, int info[2])
+{
+    return fd_fill_entry<double>(m, n, ldy, j0, pc, Y, twh, J, col, info);
+}
+int mir_lsq_fd_fill_s(size_t m, size_t n, size_t ldy, int j0, int pc, const float* Y, const float* twh, float* J, int col, int info[2])
+{
+    return fd_fill_entry<float>(m, n, ldy, j0, pc, Y, twh, J, col, info);
+}
+int mir_lsq_entry_state_d(size_t m, const double* v, uint32_t seq, double* partials, double* sum, mir_lsq_lm_state_d* state,
+                          mir_lsq_lm_state_d* host_state, double* partials2, double* sums2, mir_lsq_lm_state_d* st2, int info[3])
+{
+    return entry_state_entry<double>(m, v, seq, partials, sum, state, host_state, partials2, sums2, st2, info);
+}
+int mir_lsq_entry_state_s(size_t m, const float* v, uint32_t seq, float* partials, float* sum, mir_lsq_lm_state_s* state,
+                          mir_lsq_lm_state_s* host_state, float* partials2, float* sums2, mir_lsq_lm_state_s* st2, int info[3])
+{
+    return entry_state_entry<float>(m, v, seq, partials, sum, state, host_state, partials2, sums2, st2, info);
+}
+int mir_lsq_sumsq_blocks(size_t m) { return m ? sumsq_blocks(m) : -1; }
+int mir_lsq_unpack_grad_d(size_t n, const double* packed, mir_lsq_lm_state_d* state, double* JJ, double* Jy, int info[2])
+{
+    return unpack_grad_entry<double>(n, packed, state, JJ, Jy, info);
+}
+int mir_lsq_unpack_grad_s(size_t n, const float* packed, mir_lsq_lm_state_s* state, float* JJ, float* Jy, int info[2])
+{
+    return unpack_grad_entry<float>(n, packed, state, JJ, Jy, info);
 }
 int mir_lsq_jtj_s(size_t m, size_t n, float* J, const float* y, const float* y_old, const float* dx, int broyden,
                   float* JJ, float* Jy, void* stream, float* kernel_ms)
