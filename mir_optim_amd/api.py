@@ -461,6 +461,14 @@ def workloads_lib():
         W.wl_uniform.argtypes = [C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]
         W.wl_tanh_linear_generate.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+        sz = C.c_size_t
+        W.wl_tanh_linear_class.restype = C.c_int
+        W.wl_tanh_linear_class.argtypes = [C.c_int, sz, sz, sz, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int * 4)]
+        W.wl_gauss_sum_class.restype = C.c_int
+        W.wl_gauss_sum_class.argtypes = [C.c_int, sz, sz, sz, C.POINTER(C.c_int * 2)]
+        for name in ("wl_unary_d", "wl_unary_s"):
+            getattr(W, name).restype = C.c_int
+            getattr(W, name).argtypes = [C.c_void_p, C.c_int, sz, C.c_void_p, C.c_void_p]
         _wl = W
     return _wl
 

@@ -128,10 +128,12 @@ __global__ __launch_bounds__(256) void k_tanh_linear_rows(const T* __restrict__ 
     }
 }
 
+inline unsigned addr16(const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); }
+
+// the one-point kernels of class c (tl_class_point: TL_SWEEP with its NCP and VEC, or TL_ROWS)
 template <typename T, int NCP, int MODE>
-void launch_tanh_linear_ncp(const T* A, const T* b, const T* x, T* out, size_t m, int n, dim3 grid, hipStream_t s)
+void launch_tanh_linear_ncp(const T* A, const T* b, const T* x, T* out, size_t m, int n, dim3 grid, bool vec, hipStream_t s)
 {
-    const bool vec = (n % 2 == 0) && (reinterpret_cast<uintptr_t>(A) % (2 * sizeof(T)) == 0);
     if (vec) hipLaunchKernelGGL((k_tanh_linear<T, NCP, MODE, true>), grid, dim3(256), 0, s, A, b, x, out, m, n);
     else hipLaunchKernelGGL((k_tanh_linear<T, NCP, MODE, false>), grid, dim3(256), 0, s, A, b, x, out, m, n);
 }
@@ -139,20 +141,18 @@ void launch_tanh_linear_ncp(const T* A, const T* b, const T* x, T* out, size_t m
 template <typename T, int MODE>
 void launch_tanh_linear(const T* A, const T* b, const T* x, T* out, size_t m, int n, hipStream_t s)
 {
+    const TlClass c = tl_class_point((size_t)n, addr16(A), (int)sizeof(T), MODE);
     const size_t G = (m + 3) / 4;
     size_t blocks = (G + 3) / 4;
     if (blocks > 256 * 4) blocks = 256 * 4;
     if (blocks < 1) blocks = 1;
-    const int ncp = (n + 31) / 32;                         // column pairs per lane
     dim3 grid((unsigned)blocks);
-    if (ncp > 8) {
-        hipLaunchKernelGGL((k_tanh_linear_rows<T, MODE>), grid, dim3(256), 0, s, A, b, x, out, m, n);
-        return;
-    }
-    if (ncp <= 1) launch_tanh_linear_ncp<T, 1, MODE>(A, b, x, out, m, n, grid, s);
-    else if (ncp <= 2) launch_tanh_linear_ncp<T, 2, MODE>(A, b, x, out, m, n, grid, s);
-    else if (ncp <= 4) launch_tanh_linear_ncp<T, 4, MODE>(A, b, x, out, m, n, grid, s);
-    else launch_tanh_linear_ncp<T, 8, MODE>(A, b, x, out, m, n, grid, s);
+    const bool vec = c.flags & TL_VEC;
+    if (c.family == TL_ROWS) hipLaunchKernelGGL((k_tanh_linear_rows<T, MODE>), grid, dim3(256), 0, s, A, b, x, out, m, n);
+    else if (c.width == 1) launch_tanh_linear_ncp<T, 1, MODE>(A, b, x, out, m, n, grid, vec, s);
+    else if (c.width == 2) launch_tanh_linear_ncp<T, 2, MODE>(A, b, x, out, m, n, grid, vec, s);
+    else if (c.width == 4) launch_tanh_linear_ncp<T, 4, MODE>(A, b, x, out, m, n, grid, vec, s);
+    else launch_tanh_linear_ncp<T, 8, MODE>(A, b, x, out, m, n, grid, vec, s);
 }
 
 // ---- Gaussian-sum: n = 3K+1, x = [a | c | w | b]; y_i = sum_k a_k exp(-(t_i-c_k)^2/(2 w_k^2)) + b - data_i
@@ -237,7 +237,14 @@ __global__ __launch_bounds__(256) void k_exp_decay(const T* __restrict__ t, cons
     }
 }
 
-
+// ---- the device's own tanh / exp on a vector (fn 0: dtanh, 1: dexp of workloads_device.h), for the tests: the function alone
+//      against a high-precision reference, and its values as the T of the exact cells (tests/model_cases.py)
+template <typename T>
+__global__ __launch_bounds__(256) void k_unary(int fn, size_t count, const T* __restrict__ in, T* __restrict__ out)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = fn == 0 ? dtanh(in[i]) : dexp(in[i]);
+}
 
 // ---- a handful of points (p <= 8) in one sweep over A: the lambda-ladder trials of the solver. HBM-bound like the
 //      single-point kernel (A is read once), one 16-lane DPP reduction and one tanh per (row, point).
@@ -290,20 +297,16 @@ __global__ __launch_bounds__(256) void k_tanh_linear_multi(const double* __restr
     }
 }
 
-bool launch_tanh_linear_multi(const double* A, const double* b, const double* X, double* Y, size_t m, int n, int P, hipStream_t s)
+void launch_tanh_linear_multi(int ncp, const double* A, const double* b, const double* X, double* Y, size_t m, int n, int P, hipStream_t s)
 {
-    if (P > 8 || n > 128 || n % 2 != 0) return false;
-    if (reinterpret_cast<uintptr_t>(A) % 16 != 0 || reinterpret_cast<uintptr_t>(X) % 16 != 0) return false;
     const size_t G = (m + 3) / 4;
     size_t blocks = (G + 3) / 4;
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;
-    const int ncp = (n + 31) / 32;
     dim3 grid((unsigned)blocks), blk(256);
-    if (ncp <= 1) hipLaunchKernelGGL((k_tanh_linear_multi<1, 8>), grid, blk, 0, s, A, b, X, Y, m, n, P);
-    else if (ncp <= 2) hipLaunchKernelGGL((k_tanh_linear_multi<2, 8>), grid, blk, 0, s, A, b, X, Y, m, n, P);
+    if (ncp == 1) hipLaunchKernelGGL((k_tanh_linear_multi<1, 8>), grid, blk, 0, s, A, b, X, Y, m, n, P);
+    else if (ncp == 2) hipLaunchKernelGGL((k_tanh_linear_multi<2, 8>), grid, blk, 0, s, A, b, X, Y, m, n, P);
     else hipLaunchKernelGGL((k_tanh_linear_multi<4, 8>), grid, blk, 0, s, A, b, X, Y, m, n, P);
-    return true;
 }
 
 inline unsigned blocks_for(size_t m)
@@ -347,42 +350,66 @@ void wl_tanh_linear_g_d(void* vctx, size_t m, size_t n, const double* x, double*
     auto* c = static_cast<wl_tanh_linear_ctx*>(vctx);
     launch_tanh_linear<double, 1>((const double*)c->A, (const double*)c->b, x, J, m, (int)n, (hipStream_t)c->stream);
 }
-// batched residual (mir_lsq_batched_function_d): p points in one sweep over A (MFMA GEMM); shapes the
-// GEMM kernel does not cover fall back to one sweep per point.
+// The batched entries: ONE dispatcher on tl_class (workloads_gemm.h). A DMA class whose LDS size cannot be set
+// (hipFuncSetAttribute) falls to the next: a BASE panel to the plain difference panel plus the sweep, every other to dma = false.
+static void tanh_linear_batched(int op, wl_tanh_linear_ctx* ctx, size_t m, size_t n, size_t p, const double* X, double* Y, bool dense)
+{
+    const double *A = (const double*)ctx->A, *b = (const double*)ctx->b;
+    hipStream_t s = (hipStream_t)ctx->stream;
+    const int rao = op == TL_OP_FBD ? ctx->read_a_once : 0;
+    const bool base = op == TL_OP_FBD && p == 2 * n + 1;
+    const int P = (int)(base ? 2 * n : p);
+    TlClass c = tl_class(op, m, n, p, addr16(A), addr16(X), addr16(Y), 8, rao, dense);
+    if (c.family == TL_DMA && !launch_tlb_dma_class(c, A, b, X, Y, m, P, s, rao, dense)) {
+        if (c.flags & TL_BASE) {
+            c.flags &= ~TL_BASE;
+            c.launches = 2;
+            if (!launch_tlb_dma_class(c, A, b, X, Y, m, P, s, rao, dense)) c = tl_class(op, m, n, p, addr16(A), addr16(X), addr16(Y), 8, rao, dense, false);
+        } else {
+            c = tl_class(op, m, n, p, addr16(A), addr16(X), addr16(Y), 8, rao, dense, false);
+        }
+    }
+    if (c.family == TL_MULTI) launch_tanh_linear_multi(c.width, A, b, X, Y, m, (int)n, P, s);
+    else if (c.family == TL_LOOP)
+        for (size_t k = 0; k < p; ++k) launch_tanh_linear<double, 0>(A, b, X + k * n, Y + k * m, m, (int)n, s);
+    else if (c.family != TL_DMA) launch_tanh_linear_gemm_class(c, A, b, X, Y, m, (int)n, P, s);
+    // the extra point of a p = 2n + 1 difference panel that the launch has not written: the one-point sweep, the same bits
+    if (base && !(c.flags & TL_BASE)) launch_tanh_linear<double, 0>(A, b, X + 2 * n * n, Y + m * n, m, (int)n, s);
+}
+// batched residual (mir_lsq_batched_function_d): p points in one sweep over A (a handful of points: k_tanh_linear_multi; else the
+// MFMA GEMM); shapes the GEMM kernels do not cover take one sweep per point.
 void wl_tanh_linear_fb_d(void* vctx, size_t m, size_t n, size_t p, const double* X, double* Y)
 {
-    auto* c = static_cast<wl_tanh_linear_ctx*>(vctx);
-    if (p <= 8 && launch_tanh_linear_multi((const double*)c->A, (const double*)c->b, X, Y, m, (int)n, (int)p, (hipStream_t)c->stream)) return;
-    if (launch_tanh_linear_batched((const double*)c->A, (const double*)c->b, X, Y, m, (int)n, (int)p, (hipStream_t)c->stream)) return;
-    for (size_t k = 0; k < p; ++k)
-        launch_tanh_linear<double, 0>((const double*)c->A, (const double*)c->b, X + k * n, Y + k * m, m, (int)n, (hipStream_t)c->stream);
+    tanh_linear_batched(TL_OP_FB, static_cast<wl_tanh_linear_ctx*>(vctx), m, n, p, X, Y, false);
 }
 // the same p points with Y written m x p row-major (mir_lsq_gpu_options.fbRowMajor)
 void wl_tanh_linear_fbr_d(void* vctx, size_t m, size_t n, size_t p, const double* X, double* Y)
 {
-    auto* c = static_cast<wl_tanh_linear_ctx*>(vctx);
-    launch_tanh_linear_batched_rm((const double*)c->A, (const double*)c->b, X, Y, m, (int)n, (int)p, (hipStream_t)c->stream);
+    tanh_linear_batched(TL_OP_FBR, static_cast<wl_tanh_linear_ctx*>(vctx), m, n, p, X, Y, false);
 }
 // the same p = 2n points [x + h e_0, x - h e_0, ...] with the m x n row-major DIFFERENCE panel written
 // (mir_lsq_gpu_options.fbRowMajorDiff): D[i n + j] = f(X_2j)_i - f(X_2j+1)_i
 // p = 2n + 1 (MIR_LSQ_FD_BASE_POINT): one more point behind the 2n, its residual VECTOR behind the panel at D[m n .. m n + m) --
 // at n = 128 from the stage of A the GEMM already holds in LDS, elsewhere by the one-point sweep; the same bits either way
-static void tanh_linear_fbd(wl_tanh_linear_ctx* c, size_t m, size_t n, size_t p, const double* X, double* D, bool dense)
-{
-    const double *A = (const double*)c->A, *b = (const double*)c->b;
-    const bool base = p == 2 * n + 1;
-    const bool folded = launch_tanh_linear_batched_diff(A, b, X, D, m, (int)n, (int)(base ? 2 * n : p), (hipStream_t)c->stream,
-                                                        c->read_a_once, dense, base);
-    if (base && !folded) launch_tanh_linear<double, 0>(A, b, X + 2 * n * n, D + m * n, m, (int)n, (hipStream_t)c->stream);
-}
 void wl_tanh_linear_fbd_d(void* vctx, size_t m, size_t n, size_t p, const double* X, double* D)
 {
-    tanh_linear_fbd(static_cast<wl_tanh_linear_ctx*>(vctx), m, n, p, X, D, false);
+    tanh_linear_batched(TL_OP_FBD, static_cast<wl_tanh_linear_ctx*>(vctx), m, n, p, X, D, false);
 }
 // the same panel with every product of the GEMM computed (n = 128: no forking off the base point's chain): for A/B runs and tests
 void wl_tanh_linear_fbd_dense_d(void* vctx, size_t m, size_t n, size_t p, const double* X, double* D)
 {
-    tanh_linear_fbd(static_cast<wl_tanh_linear_ctx*>(vctx), m, n, p, X, D, true);
+    tanh_linear_batched(TL_OP_FBD, static_cast<wl_tanh_linear_ctx*>(vctx), m, n, p, X, D, true);
+}
+// Which kernel a call of the entries above runs, for the tests (tl_class, workloads_gemm.h): op 0 f, 1 g, 2 fb, 3 fbr, 4 fbd;
+// a_A, a_x, a_y the addresses of A, X / x and Y / y / J / D modulo 16; elem 8 (the _d entries) or 4 (_s: f and g).
+// out: family, width, flags, launches. Returns 0, or -1 for an op or elem it does not know.
+int wl_tanh_linear_class(int op, size_t m, size_t n, size_t p, unsigned a_A, unsigned a_x, unsigned a_y, int elem, int read_a_once,
+                         int dense, int* out)
+{
+    if (op < TL_OP_F || op > TL_OP_FBD || (elem != 8 && !(elem == 4 && op <= TL_OP_G))) return -1;
+    const TlClass c = tl_class(op, m, n, p, a_A & 15, a_x & 15, a_y & 15, elem, op == TL_OP_FBD ? read_a_once : 0, dense);
+    out[0] = c.family; out[1] = c.width; out[2] = c.flags; out[3] = c.launches;
+    return 0;
 }
 void wl_tanh_linear_f_s(void* vctx, size_t m, size_t n, const float* x, float* y)
 {
@@ -439,6 +466,20 @@ void wl_omp_thread_manager(void* ctx, uint32_t count, wl_task task, wl_task_fn f
     }
 }
 
+// Which Gaussian-sum kernel an entry runs (op 0 f, 2 fb, 3 fbr: the numbers of wl_tanh_linear_class): out[0] = 0 k_gauss_sum,
+// 1 k_gauss_sum_batched point-major, 2 the same row-major; out[1] = 1 when the constants of the Gaussians live in registers
+// (k_gauss_sum: K <= kGaussMax, else gauss_row_any; row-major: the FIXED instance -- a point per thread, which takes K <= kGaussMax
+// and a grid whose thread count is a multiple of p; cfg 2: p = 32 points, 256-thread workgroups). Returns -1 for another op.
+int wl_gauss_sum_class(int op, size_t m, size_t n, size_t p, int* out)
+{
+    const bool regs = (n - 1) / 3 <= (size_t)kGaussMax;
+    if (op == TL_OP_F) { out[0] = 0; out[1] = regs; return 0; }
+    if (op == TL_OP_FB) { out[0] = 1; out[1] = 0; return 0; }
+    if (op != TL_OP_FBR) return -1;
+    out[0] = 2;
+    out[1] = regs && p > 0 && ((size_t)blocks_for(m * p) * 256) % p == 0;
+    return 0;
+}
 void wl_gauss_sum_f_d(void* vctx, size_t m, size_t n, const double* x, double* y)
 {
     auto* c = static_cast<wl_curve_ctx*>(vctx);
@@ -460,9 +501,10 @@ void wl_gauss_sum_fb_d(void* vctx, size_t m, size_t n, size_t p, const double* X
 void wl_gauss_sum_fbr_d(void* vctx, size_t m, size_t n, size_t p, const double* X, double* Y)
 {
     auto* c = static_cast<wl_curve_ctx*>(vctx);
-    // a point per thread when the thread count of the grid is a multiple of p (cfg 2: p = 32 points, 256-thread workgroups)
     const unsigned nb = blocks_for(m * p);
-    if ((n - 1) / 3 <= (size_t)kGaussMax && p > 0 && ((size_t)nb * 256) % p == 0)
+    int cls[2];
+    wl_gauss_sum_class(TL_OP_FBR, m, n, p, cls);
+    if (cls[1])
         hipLaunchKernelGGL((k_gauss_sum_batched<double, true, true>), dim3(nb), dim3(256), 0, (hipStream_t)c->stream,
                            (const double*)c->t, (const double*)c->data, X, Y, m, (int)n, (int)p);
     else
@@ -482,6 +524,21 @@ void wl_exp_decay_f_s(void* vctx, size_t m, size_t n, const float* x, float* y)
     auto* c = static_cast<wl_curve_ctx*>(vctx);
     hipLaunchKernelGGL(k_exp_decay<float>, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)c->stream,
                        (const float*)c->t, (const float*)c->data, x, y, m, c->kind);
+}
+
+// Test helper: out[i] = fn(in[i]) for `count` device values with the device functions the residual kernels call
+// (fn 0: dtanh, 1: dexp). Returns 0, or -1 for an unknown fn (nothing is launched).
+int wl_unary_d(void* stream, int fn, size_t count, const double* in, double* out)
+{
+    if (fn != 0 && fn != 1) return -1;
+    if (count) hipLaunchKernelGGL(k_unary<double>, dim3(blocks_for(count)), dim3(256), 0, (hipStream_t)stream, fn, count, in, out);
+    return 0;
+}
+int wl_unary_s(void* stream, int fn, size_t count, const float* in, float* out)
+{
+    if (fn != 0 && fn != 1) return -1;
+    if (count) hipLaunchKernelGGL(k_unary<float>, dim3(blocks_for(count)), dim3(256), 0, (hipStream_t)stream, fn, count, in, out);
+    return 0;
 }
 
 // Test helper: `blocks` workgroups of 256 threads, each holding `lds_bytes` of LDS, that do nothing but stay on their CU for

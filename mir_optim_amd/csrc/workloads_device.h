@@ -51,6 +51,13 @@ __device__ inline double lane_pair_swap(double v)
 // tanh for the synthetic residuals: 1 - 2 / (exp(2|x|) + 1) with a degree-13 exp polynomial and a Newton-refined
 // reciprocal, ~35 fp64 instructions instead of libm's ~135 (absolute error ~2e-16; the residual tanh(.) - b only
 // needs absolute accuracy). The same function is used by the single-point and the batched kernels.
+// Held to a long-double tanh within 2^-51 over the whole line by tests/test_gpu_tanh_cells.py (wl_unary_d runs it alone); odd,
+// |y| <= 1, +-1 exactly from |x| = 20 on, +-0 kept.
+// A NaN DOES NOT COME OUT A NaN: fmin returns the operand that is a number, so dtanh(NaN) = copysign(1, NaN) = +-1, and a NaN in
+// x or in A gives a finite residual (libm's tanh, the host callback and the oracle return NaN). A clamp that a NaN passes,
+// `t > 40 ? 40 : t` or `2 (ax > 20 ? 20 : ax)`, costs the forked n = 128 difference-panel kernel, which sits at its 168-register
+// limit, 12 bytes of scratch memory it does not have today (profiles/r23/dtanh_nan_resources.txt), so the clamp stays as it is:
+// a caller who needs a NaN to surface checks x before the call. DESIGN section 11.
 __device__ inline double dtanh(double x)
 {
     const double ax = fabs(x);

@@ -1113,68 +1113,60 @@ __global__ __launch_bounds__(256) void k_tanh_linear_batched_wide(const double* 
 
 }  // namespace
 
-bool launch_tanh_linear_batched_diff(const double* A, const double* b, const double* X, double* D, size_t m, int n, int P,
-                                     hipStream_t s, int read_a_once, bool dense, bool base)
+// The launchers take the class tl_class (workloads_gemm.h) chose: nothing here decides a shape.
+bool launch_tlb_dma_class(const TlClass& c, const double* A, const double* b, const double* X, double* Y, size_t m, int P, hipStream_t s,
+                          int read_a_once, bool dense)
 {
-    if (m >= 32 && P % 16 == 0) {                          // whole 16-point MFMA tiles: no clamped lanes, whose pairs would store zeros
+    if (c.flags & TL_DIFF) {                               // whole 16-point MFMA tiles: no clamped lanes, whose pairs would store zeros
         const int mode = read_a_once ? 1 : dense ? 0 : 2;
         // the extra point of a p = 2n + 1 call rides on the n = 128 kernel (forked or dense; not on the read-A-once experiment)
-        if (base && n == 128 && P == 2 * n && mode != 1 && launch_tlb_dma<32, true, true, true>(A, b, X, D, m, P, s, mode)) return true;
-        if (n == 256 && launch_tlb_dma<64, true, true>(A, b, X, D, m, P, s, mode)) return false;
-        if (n == 128 && launch_tlb_dma<32, true, true>(A, b, X, D, m, P, s, mode)) return false;
-        if (n == 64 && launch_tlb_dma<16, true, true>(A, b, X, D, m, P, s, mode)) return false;
-        if (n == 32 && launch_tlb_dma<8, true, true>(A, b, X, D, m, P, s, mode)) return false;
+        if (c.flags & TL_BASE) return launch_tlb_dma<32, true, true, true>(A, b, X, Y, m, P, s, mode);
+        switch (c.width) {
+        case 64: return launch_tlb_dma<64, true, true>(A, b, X, Y, m, P, s, mode);
+        case 32: return launch_tlb_dma<32, true, true>(A, b, X, Y, m, P, s, mode);
+        case 16: return launch_tlb_dma<16, true, true>(A, b, X, Y, m, P, s, mode);
+        default: return launch_tlb_dma<8, true, true>(A, b, X, Y, m, P, s, mode);
+        }
     }
-    if (n > 256 && n % 8 == 0 && P % 2 == 0 && m > 0) {
-        const size_t nt = (m + 63) / 64;
-        hipLaunchKernelGGL(k_tanh_linear_batched_wide<1>, dim3((unsigned)(nt < 256 * 8 ? nt : 256 * 8)), dim3(256), 0, s, A, b, X, D, m, n, P);
-        return false;
+    if (c.flags & TL_RM) {
+        switch (c.width) {
+        case 64: return launch_tlb_dma<64, true>(A, b, X, Y, m, P, s);
+        case 32: return launch_tlb_dma<32, true>(A, b, X, Y, m, P, s);
+        case 16: return launch_tlb_dma<16, true>(A, b, X, Y, m, P, s);
+        default: return launch_tlb_dma<8, true>(A, b, X, Y, m, P, s);
+        }
     }
-    size_t blocks = (m * (size_t)(P / 2) + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(k_tanh_linear_batched_diff_generic, dim3((unsigned)(blocks ? blocks : 1)), dim3(256), 0, s, A, b, X, D, m, n, P);
-    return false;
+    switch (c.width) {
+    case 64: return launch_tlb_dma<64>(A, b, X, Y, m, P, s);
+    case 32: return launch_tlb_dma<32>(A, b, X, Y, m, P, s);
+    case 16: return launch_tlb_dma<16>(A, b, X, Y, m, P, s);
+    default: return launch_tlb_dma<8>(A, b, X, Y, m, P, s);
+    }
 }
 
-void launch_tanh_linear_batched_rm(const double* A, const double* b, const double* X, double* Y, size_t m, int n, int P,
+void launch_tanh_linear_gemm_class(const TlClass& c, const double* A, const double* b, const double* X, double* Y, size_t m, int n, int P,
                                    hipStream_t s)
 {
-    if (m >= 32) {
-        if (n == 256 && launch_tlb_dma<64, true>(A, b, X, Y, m, P, s)) return;
-        if (n == 128 && launch_tlb_dma<32, true>(A, b, X, Y, m, P, s)) return;
-        if (n == 64 && launch_tlb_dma<16, true>(A, b, X, Y, m, P, s)) return;
-        if (n == 32 && launch_tlb_dma<8, true>(A, b, X, Y, m, P, s)) return;
-    }
-    if (n > 256 && n % 8 == 0 && m > 0) {
+    if (c.family == TL_WIDE) {
         const size_t nt = (m + 63) / 64;
-        hipLaunchKernelGGL(k_tanh_linear_batched_wide<0>, dim3((unsigned)(nt < 256 * 8 ? nt : 256 * 8)), dim3(256), 0, s, A, b, X, Y, m, n, P);
-        return;
+        const dim3 grid((unsigned)(nt < 256 * 8 ? nt : 256 * 8));
+        if (c.width == 0) hipLaunchKernelGGL(k_tanh_linear_batched_wide<0>, grid, dim3(256), 0, s, A, b, X, Y, m, n, P);
+        else if (c.width == 1) hipLaunchKernelGGL(k_tanh_linear_batched_wide<1>, grid, dim3(256), 0, s, A, b, X, Y, m, n, P);
+        else hipLaunchKernelGGL(k_tanh_linear_batched_wide<2>, grid, dim3(256), 0, s, A, b, X, Y, m, n, P);
+    } else if (c.family == TL_GENERIC_DIFF) {
+        size_t blocks = (m * (size_t)(P / 2) + 255) / 256;
+        if (blocks > 256 * 16) blocks = 256 * 16;
+        hipLaunchKernelGGL(k_tanh_linear_batched_diff_generic, dim3((unsigned)(blocks ? blocks : 1)), dim3(256), 0, s, A, b, X, Y, m, n, P);
+    } else if (c.family == TL_GENERIC_RM) {
+        size_t blocks = (m * (size_t)P + 255) / 256;
+        if (blocks > 256 * 16) blocks = 256 * 16;
+        hipLaunchKernelGGL(k_tanh_linear_batched_rm_generic, dim3((unsigned)(blocks ? blocks : 1)), dim3(256), 0, s, A, b, X, Y, m, n, P);
+    } else {                                               // TL_MFMA
+        const size_t ntiles = (m + 15) / 16;
+        const unsigned grid = (unsigned)(ntiles < 256 ? ntiles : 256);
+        if (c.width == 4) hipLaunchKernelGGL(k_tanh_linear_batched<4>, dim3(grid), dim3(1024), 0, s, A, b, X, Y, m, n, P);
+        else if (c.width == 8) hipLaunchKernelGGL(k_tanh_linear_batched<8>, dim3(grid), dim3(1024), 0, s, A, b, X, Y, m, n, P);
+        else if (c.width == 16) hipLaunchKernelGGL(k_tanh_linear_batched<16>, dim3(grid), dim3(1024), 0, s, A, b, X, Y, m, n, P);
+        else hipLaunchKernelGGL(k_tanh_linear_batched<32>, dim3(grid), dim3(1024), 0, s, A, b, X, Y, m, n, P);
     }
-    size_t blocks = (m * (size_t)P + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(k_tanh_linear_batched_rm_generic, dim3((unsigned)(blocks ? blocks : 1)), dim3(256), 0, s, A, b, X, Y, m, n, P);
-}
-
-bool launch_tanh_linear_batched(const double* A, const double* b, const double* X, double* Y, size_t m, int n, int P,
-                                hipStream_t s)
-{
-    if (n == 256 && m >= 32 && launch_tlb_dma<64>(A, b, X, Y, m, P, s)) return true;
-    if (n > 256 && n % 8 == 0 && m > 0) {
-        const size_t nt = (m + 63) / 64;
-        hipLaunchKernelGGL(k_tanh_linear_batched_wide<2>, dim3((unsigned)(nt < 256 * 8 ? nt : 256 * 8)), dim3(256), 0, s, A, b, X, Y, m, n, P);
-        return true;
-    }
-    if (n % 2 != 0 || n > 128 || n < 4) return false;
-    if (m >= 32) {
-        if (n == 128 && launch_tlb_dma<32>(A, b, X, Y, m, P, s)) return true;
-        if (n == 64 && launch_tlb_dma<16>(A, b, X, Y, m, P, s)) return true;
-        if (n == 32 && launch_tlb_dma<8>(A, b, X, Y, m, P, s)) return true;
-    }
-    const size_t ntiles = (m + 15) / 16;
-    unsigned grid = (unsigned)(ntiles < 256 ? ntiles : 256);
-    if (n <= 16) hipLaunchKernelGGL(k_tanh_linear_batched<4>, dim3(grid), dim3(1024), 0, s, A, b, X, Y, m, n, P);
-    else if (n <= 32) hipLaunchKernelGGL(k_tanh_linear_batched<8>, dim3(grid), dim3(1024), 0, s, A, b, X, Y, m, n, P);
-    else if (n <= 64) hipLaunchKernelGGL(k_tanh_linear_batched<16>, dim3(grid), dim3(1024), 0, s, A, b, X, Y, m, n, P);
-    else hipLaunchKernelGGL(k_tanh_linear_batched<32>, dim3(grid), dim3(1024), 0, s, A, b, X, Y, m, n, P);
-    return true;
 }

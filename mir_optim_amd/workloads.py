@@ -1,6 +1,7 @@
 """Synthetic workloads of SURVEY.md section 8d as DEVICE-callback problems (plumbing around
 csrc/workloads.hip): build the inputs on the host with the counter RNG, upload them, and expose the
 native callback addresses + context that mir_optimize_least_squares_gpu_* needs."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -24,6 +25,55 @@ def uniform(seed, count, offset=0):
 
 def _addr(name):
     return C.cast(getattr(api.workloads_lib(), name), C.c_void_p).value
+
+
+OPS = {"f": 0, "g": 1, "fb": 2, "fbr": 3, "fbd": 4}
+TL_FAMILIES = ("SWEEP", "ROWS", "MULTI", "MFMA", "DMA", "WIDE", "GENERIC_RM", "GENERIC_DIFF", "LOOP")
+TL_FLAGS = (("VEC", 1), ("RM", 2), ("DIFF", 4), ("BASE", 8))
+TlClass = collections.namedtuple("TlClass", "family width flags mode launches")
+
+
+def tanh_linear_class(op, m, n, p=1, a_A=0, a_x=0, a_y=0, elem=8, read_a_once=False, dense=False):
+    """The kernel a call of the tanh-linear entry `op` ('f', 'g', 'fb', 'fbr', 'fbd') runs, from the library's own choice
+    (wl_tanh_linear_class; csrc/workloads_gemm.h says what the fields mean): TlClass(family name, width, frozenset of flag
+    names, mode, launches). a_A, a_x, a_y: the addresses of A, X and Y modulo 16; elem: 8 for the double entries, 4 for float."""
+    out = (C.c_int * 4)()
+    if api.workloads_lib().wl_tanh_linear_class(OPS[op], m, n, p, a_A, a_x, a_y, elem, int(read_a_once), int(dense), C.byref(out)) != 0:
+        raise ValueError(f"wl_tanh_linear_class: no entry {op!r} with elements of {elem} bytes")
+    return TlClass(TL_FAMILIES[out[0]], out[1], frozenset(k for k, bit in TL_FLAGS if out[2] & bit), out[2] >> 4, out[3])
+
+
+def gauss_sum_class(op, m, n, p=1):
+    """(kernel, registers) of the Gaussian-sum entry `op` ('f', 'fb', 'fbr'): 'k_gauss_sum' | 'batched_pm' | 'batched_rm', and
+    whether the Gaussians' constants live in registers (row-major: the FIXED instance) -- wl_gauss_sum_class."""
+    out = (C.c_int * 2)()
+    if api.workloads_lib().wl_gauss_sum_class(OPS[op], m, n, p, C.byref(out)) != 0:
+        raise ValueError(f"wl_gauss_sum_class: no entry {op!r}")
+    return ("k_gauss_sum", "batched_pm", "batched_rm")[out[0]], bool(out[1])
+
+
+UNARY = {"tanh": 0, "exp": 1}
+
+
+def unary(fn, values, dtype=np.float64):
+    """The device's own dtanh ('tanh') or dexp ('exp') of csrc/workloads_device.h on every element of `values` (wl_unary_d /
+    wl_unary_s: the function the residual kernels call, run alone). Returns an array of `values`' shape."""
+    v = np.ascontiguousarray(values, dtype=dtype)
+    if v.size == 0:
+        return v.copy()
+    stream = api.Stream()
+    din = api.DeviceBuffer(v.ravel())
+    dout = api.DeviceBuffer(nbytes=v.nbytes, dtype=dtype, shape=(v.size,))
+    try:
+        call = api.workloads_lib().wl_unary_d if np.dtype(dtype) == np.float64 else api.workloads_lib().wl_unary_s
+        if call(C.c_void_p(stream.handle), C.c_int(UNARY[fn]), C.c_size_t(v.size), C.c_void_p(din.ptr), C.c_void_p(dout.ptr)) != 0:
+            raise ValueError(f"wl_unary: unknown function {fn!r}")
+        stream.synchronize()
+        return dout.download().reshape(v.shape)
+    finally:
+        din.free()
+        dout.free()
+        stream.close()
 
 
 def tanh_linear_data(m, n, row_offset=0, noise=1e-3):
