@@ -212,6 +212,11 @@ enum {
                                                     helper workgroups that share its factorisation (solve_coop.h) */
     MIR_LSQ_VARIANT_NO_FD_BASE_POINT = 1u << 14, /* ignore MIR_LSQ_FD_BASE_POINT: f(x0) by a call of its own, p = 2n always
                                                     (A/B runs and tests; bit-identical results either way) */
+    MIR_LSQ_VARIANT_FD_WRITE_J = 1u << 15,       /* the fused kernel of the difference panel writes J = D * (1 / twh) on every refresh
+                                                    and the Broyden sweeps read J. By default (f64, fbRowMajorDiff, n <= 256, the
+                                                    read-only sweep) that write is left out: the unscaled panel stays J0 until the
+                                                    next refresh or flush and the sweeps scale what they load; bit-identical
+                                                    results either way */
     MIR_LSQ_VARIANT_FD_HOST_COLUMNS = 1u << 13,  /* host-callback finite differences column by column (per-slot staging vectors,
                                                     a strided column write and a stream synchronisation per task, under a
                                                     lock) instead of through the pinned point-major panel */
@@ -702,7 +707,8 @@ int mir_lsq_jtj_s(size_t m, size_t n, float* J, const float* y, const float* y_o
 int mir_lsq_fd_jtj_d(size_t m, size_t n, const double* Yrm, const double* twh, const double* y, double* J,
                      double* JJ, double* Jy, void* stream, float* kernel_ms);
 /* The same from the m x n row-major DIFFERENCE panel D[i][j] = f(x + h e_j)_i - f(x - h e_j)_i (what a fbRowMajorDiff callback
- * writes; f64; n <= 128, n = 192, n = 256, else -6): J = D * (1 / twh) column-wise (zero for twh = 0), JJ, Jy. */
+ * writes; f64; n <= 128, n = 192, n = 256, else -6): J = D * (1 / twh) column-wise (zero for twh = 0), JJ, Jy. J may be NULL:
+ * the Jacobian rows are formed for J^T J and J^T y only and not written (the solver's default refresh). */
 int mir_lsq_fd_diff_jtj_d(size_t m, size_t n, const double* Drm, const double* twh, const double* y, double* J,
                           double* JJ, double* Jy, void* stream, float* kernel_ms);
 /* Which kernel those entries and the solver launch (csrc/jtj_plan.h; host code, no device needed): element size 4 / 8, a device
@@ -776,6 +782,17 @@ int mir_lsq_lr_pass_s(size_t m, size_t n, int k, const float* J, float* U, float
                       int info[6]);
 int mir_lsq_lr_flush_d(size_t m, size_t n, int k, double* J, const double* U, const double* D, int info[2]);
 int mir_lsq_lr_flush_s(size_t m, size_t n, int k, float* J, const float* U, const float* D, int info[2]);
+/* The same pass and flush when the refresh did not write J (the default with a fbRowMajorDiff callback; f64, n <= 256): P is the
+ * unscaled m x n difference panel (what mir_lsq_fd_diff_jtj_d reads) and twh its n interval widths, both DEVICE pointers. The
+ * sweep scales what it loads, d * (1 / twh) or 0 for twh = 0: every output has the bits of mir_lsq_lr_pass_d on the J that
+ * mir_lsq_fd_diff_jtj_d writes from P and twh. The flush writes J = scale(P) + the k terms and leaves P as it is. The instance is
+ * mir_lsq_lr_class(8, n, P -- for the flush P and J -- on the grid of two elements). */
+int mir_lsq_lr_pass_scaled_d(size_t m, size_t n, int k, const double* P, const double* twh, double* U, double* D, const double* dx,
+                             const double* dx_dot, const double* y, int count, const double* y_old, double* JJ, double* Jy,
+                             const mir_lsq_lm_solve_record_d* spec, double absTolerance, double relTolerance, double* partials,
+                             double* reduced, double* sums, double* jy_inf, int info[6]);
+int mir_lsq_lr_flush_scaled_d(size_t m, size_t n, int k, double* J, const double* P, const double* twh, const double* U, const double* D,
+                              int info[2]);
 /* The kernel instance the sweep and the flush run (host code, no device needed): element size 4 / 8, n <= 512, aligned: J lies on
  * the grid of two elements. out = { chunks a lane, 1 = vector loads (even n and aligned) }. Returns 0, or -1 (arguments). */
 int mir_lsq_lr_class(size_t elem_size, size_t n, int aligned, int out[2]);

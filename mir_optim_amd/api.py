@@ -36,7 +36,7 @@ __all__ = [
     "fit_spline_residuals", "variant_lr_cap",
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
     "VARIANT_SOLVE_BOUNDED", "VARIANT_DEBUG_SOLVE", "VARIANT_HOST_PROFILE", "VARIANT_SOLVE_GENERIC", "VARIANT_SOLVE_ONE_WORKGROUP", "VARIANT_DEBUG_HELPERS_ABSENT", "VARIANT_FD_HOST_COLUMNS",
-    "VARIANT_NO_PIPELINE", "FD_BASE_POINT", "VARIANT_NO_FD_BASE_POINT", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA", "BATCHED_BOUNDS_PER_PROBLEM",
+    "VARIANT_NO_PIPELINE", "FD_BASE_POINT", "VARIANT_NO_FD_BASE_POINT", "VARIANT_FD_WRITE_J", "BatchedOptions", "BatchedExtras", "BATCHED_ABSOLUTE_SIGMA", "BATCHED_BOUNDS_PER_PROBLEM",
     "covariance", "spdInverse", "COVARIANCE_ABSOLUTE_SIGMA",
     "fitSplineGpu", "splineEvalGpu", "fit_spline_eval_gpu", "fit_spline_eval_host", "fit_spline_factor",
     "lmSolve", "lm_solve_class",
@@ -70,6 +70,7 @@ VARIANT_SOLVE_ONE_WORKGROUP = 1 << 11
 VARIANT_DEBUG_HELPERS_ABSENT = 1 << 12
 VARIANT_FD_HOST_COLUMNS = 1 << 13
 VARIANT_NO_FD_BASE_POINT = 1 << 14
+VARIANT_FD_WRITE_J = 1 << 15
 VARIANT_NO_PIPELINE = 1 << 22
 
 
@@ -339,6 +340,11 @@ def lib():
             fn = getattr(L, "mir_lsq_lr_flush_" + suf)
             fn.restype = C.c_int
             fn.argtypes = [sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int * 2)]
+        L.mir_lsq_lr_pass_scaled_d.restype = C.c_int
+        L.mir_lsq_lr_pass_scaled_d.argtypes = [sz, sz, C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 4 \
+            + [C.c_double, C.c_double] + [C.c_void_p] * 4 + [C.POINTER(C.c_int * 6)]
+        L.mir_lsq_lr_flush_scaled_d.restype = C.c_int
+        L.mir_lsq_lr_flush_scaled_d.argtypes = [sz, sz, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(C.c_int * 2)]
         L.mir_lsq_lr_class.restype = C.c_int
         L.mir_lsq_lr_class.argtypes = [sz, sz, C.c_int, C.POINTER(C.c_int * 2)]
         L.mir_lsq_lr_blocks.restype = C.c_int
@@ -1073,11 +1079,15 @@ def lr_blocks(m, num_cu=0):
     return rc
 
 
-def lrPass(m, n, k, J, U, D, dx, dx_dot, y, y_old, JJ, Jy, dtype=np.float64, count=1, spec=None, absTolerance=0.0, relTolerance=0.0):
+def lrPass(m, n, k, J, U, D, dx, dx_dot, y, y_old, JJ, Jy, dtype=np.float64, count=1, spec=None, absTolerance=0.0, relTolerance=0.0,
+           twh=None):
     """One Broyden pass of the read-only sweep on DEVICE pointers (mir_lsq_lr_pass_d / _s; the header has the contract). spec: None,
-    or a dict with fields of lm_solve_record_dtype (the others zero). Returns a dict: partials (nblk x lr_len(n)), reduced, sums
+    or a dict with fields of lm_solve_record_dtype (the others zero). twh: a device pointer to n interval widths -- J is then the
+    unscaled difference panel (mir_lsq_lr_pass_scaled_d; f64, n <= 256). Returns a dict: partials (nblk x lr_len(n)), reduced, sums
     (count), jy_inf, cls (as lr_class), nblk, guard (first damaged band of the call's own regions or -1), bands, touched."""
     dtype = np.dtype(dtype)
+    if twh is not None and dtype != np.float64:
+        raise ValueError("the scaled sweep exists in f64 only")
     nblk, ln = lr_blocks(m), lr_len(n)
     partials, reduced = np.zeros((nblk, ln), dtype=dtype), np.zeros(ln, dtype=dtype)
     sums, jy_inf = np.zeros(count, dtype=dtype), np.zeros(1, dtype=dtype)
@@ -1087,10 +1097,14 @@ def lrPass(m, n, k, J, U, D, dx, dx_dot, y, y_old, JJ, Jy, dtype=np.float64, cou
         for key, v in spec.items():
             rec[key] = v
     info = (C.c_int * 6)()
-    fn = lib().mir_lsq_lr_pass_d if dtype == np.float64 else lib().mir_lsq_lr_pass_s
-    rc = fn(m, n, k, J, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, rec.ctypes.data if rec is not None else None,
+    tail = (dx, dx_dot, y, count, y_old, JJ, Jy, rec.ctypes.data if rec is not None else None,
             float(absTolerance), float(relTolerance), partials.ctypes.data, reduced.ctypes.data, sums.ctypes.data, jy_inf.ctypes.data,
             C.byref(info))
+    if twh is not None:
+        rc = lib().mir_lsq_lr_pass_scaled_d(m, n, k, J, twh, U, D, *tail)
+    else:
+        fn = lib().mir_lsq_lr_pass_d if dtype == np.float64 else lib().mir_lsq_lr_pass_s
+        rc = fn(m, n, k, J, U, D, *tail)
     if rc != 0:
         raise RuntimeError(f"mir_lsq_lr_pass failed: {rc}")
     if info[2] != nblk:
@@ -1109,7 +1123,17 @@ def lrFlush(m, n, k, J, U, D, dtype=np.float64):
     return int(info[0]), bool(info[1])
 
 
-LM_FLAG_TRIAL_NOT_FINITE = 8                       # kFlagTrialNotFinite (set by the decision, not by a solve)
+def lrFlushScaled(m, n, k, J, P, twh, U, D):
+    """J = scale(P) + the k pending terms on DEVICE pointers (mir_lsq_lr_flush_scaled_d): P the unscaled difference panel, twh its
+    widths; P is only read. Returns the class as lr_class (vector loads: even n, J and P both on the grid of two elements)."""
+    info = (C.c_int * 2)()
+    rc = lib().mir_lsq_lr_flush_scaled_d(m, n, k, J, P, twh, U, D, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"mir_lsq_lr_flush_scaled failed: {rc}")
+    return int(info[0]), bool(info[1])
+
+
+LM_FLAG_TRIAL_NOT_FINITE = 8                     # kFlagTrialNotFinite (set by the decision, not by a solve)
 LM_DECIDE_REJECT, LM_DECIDE_ACCEPT, LM_DECIDE_ACCEPT_NO_PREDICTION, LM_DECIDE_NUMERIC_ERROR, LM_DECIDE_GRAD_SMALL = 1, 2, 3, 4, 5
 LM_STATE_FLOATS = ("lambda", "mu", "residual", "trial_residual", "dx_dot", "new_dx_dot", "predicted", "trial_xnorm", "jy_inf",
                    "improvement", "rho", "pad0")
@@ -1375,10 +1399,13 @@ def jtj_plan(elem_size, m, n, num_cu, op, aligned=True):
     return d
 
 
-def fd_jtj(Yrm, twh, y, diff=False):
+def fd_jtj(Yrm, twh, y, diff=False, write_J=True):
     """Unit-level access to the J^T J kernel with the finite-difference fill fused in (mir_lsq_fd_jtj_d).
     Yrm: m x 2n row-major (+h / -h residual pairs) -- or, diff=True, the m x n difference panel (mir_lsq_fd_diff_jtj_d).
+    write_J=False (diff only): a NULL J, as the solver's default refresh passes it; the J returned is None.
     Returns (J, JJ full symmetric, Jy, kernel_ms)."""
+    if not write_J and not diff:
+        raise ValueError("only the difference-panel kernel takes a NULL J")
     L = lib()
     Yrm = np.ascontiguousarray(Yrm, dtype=np.float64)
     m, n2 = Yrm.shape
@@ -1390,10 +1417,10 @@ def fd_jtj(Yrm, twh, y, diff=False):
     dJJ = DeviceBuffer(nbytes=n * n * 8, dtype=np.float64, shape=(n, n))
     dJy = DeviceBuffer(nbytes=n * 8, dtype=np.float64, shape=(n,))
     ms = C.c_float(0)
-    rc = (L.mir_lsq_fd_diff_jtj_d if diff else L.mir_lsq_fd_jtj_d)(m, n, dY.ptr, dt.ptr, dy.ptr, dJ.ptr, dJJ.ptr, dJy.ptr, None, C.byref(ms))
+    rc = (L.mir_lsq_fd_diff_jtj_d if diff else L.mir_lsq_fd_jtj_d)(m, n, dY.ptr, dt.ptr, dy.ptr, dJ.ptr if write_J else None, dJJ.ptr, dJy.ptr, None, C.byref(ms))
     if rc != 0:
         raise RuntimeError(f"mir_lsq_fd_jtj_d failed: {rc}")
-    out = dJ.download(), dJJ.download(), dJy.download(), ms.value
+    out = dJ.download() if write_J else None, dJJ.download(), dJy.download(), ms.value
     for b in (dY, dt, dy, dJ, dJJ, dJy):
         b.free()
     return out

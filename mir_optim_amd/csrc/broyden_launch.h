@@ -29,6 +29,7 @@ struct LrArgs {
     const ChainRec<T>* spec_rec;
     T absTolerance, relTolerance;
 };
+constexpr int kLrScaledMaxN = 256;   // the widest difference panel a fused FD kernel takes (jtj_fdp8.h)
 
 // workgroups of the sweep: 4 per CU, at least ~8 row steps per wave (never more than kLrMaxBlocks: the trial sums' partials
 // of k_lr_sumsq share the layout)
@@ -60,7 +61,11 @@ template <typename T> inline LrClass lr_class_of(int n, const T* J)
 }
 
 // the sweep: per-workgroup partial vectors -> a.partials (nblk x lr_len(n)); column a.k of U is written
-template <typename T> hipError_t lr_sweep(const LrArgs<T>& a, int nblk, hipStream_t s);
+// SCALED sweep (f64, n <= kLrScaledMaxN): twh != nullptr says that J0 was never written -- a.J is the unscaled m x n
+// finite-difference DIFFERENCE panel of the last refresh and twh its n interval widths; the sweep scales what it loads
+// (fd_scale, common.h) and holds the bits the fused FD kernel would have written to J. nullptr: a.J is J0 itself. (twh rides
+// beside the argument block, not in it: the block's size is part of the plain instances' device code.)
+template <typename T> hipError_t lr_sweep(const LrArgs<T>& a, int nblk, hipStream_t s, const T* twh = nullptr);
 // fixed-order sum of the partial vectors -> out (lr_len(n)): the all-reduce payload of a Broyden pass
 template <typename T> hipError_t lr_reduce(const T* partials, int nblk, int n, T* out, hipStream_t s);
 // the n x n side: JJ += v dx^T + dx v^T + uu dx dx^T, Jy, |Jy|_inf, D_k = dx from the (all-reduced) vector lr
@@ -72,5 +77,10 @@ template <typename T> hipError_t lr_sumsq(const T* v, size_t m, int count, size_
 template <typename T> hipError_t lr_sumsq_final(const T* partials, int pstride, int nblk, int count, T* out, hipStream_t s);
 // J += the k pending terms, in place, in update order (the reference's successive `ger`s, LS:1006)
 template <typename T> hipError_t lr_flush(T* J, const T* U, const T* D, int k, size_t m, int n, int num_cu, hipStream_t s);
+// J = scale(P) + the k pending terms, in update order: the flush when J0 is still the unscaled difference panel P with the
+// widths twh (as lr_sweep's); P is only read, J is materialised (k = 0 included). f64, n <= kLrScaledMaxN. The instance is
+// lr_class(n, J and P both on the grid of 2 elements).
+hipError_t lr_flush_scaled(double* J, const double* P, const double* twh, const double* U, const double* D, int k, size_t m, int n,
+                           int num_cu, hipStream_t s);
 
 }  // namespace mirlsq

@@ -68,10 +68,19 @@ __device__ __forceinline__ T lr_wave_sumsq(const T* __restrict__ y, size_t m, si
     return yy;
 }
 
+// SCALED: a.J is the unscaled finite-difference difference panel and twh its interval widths (the refresh did not write J,
+// broyden_launch.h): a lane forms 1 / twh of its 2 NCP columns once, ahead of the row loop, and scales every pair it loads
+// (fd_scale, common.h) before any use -- from there on the operations and their order are those of the plain sweep, on the
+// values the plain sweep would have loaded from J: the same bits in s, u, va, ga and in the no-go branch.
+// A scaled instance is the one with a trailing argument, `const T* twh`: Src is that one type, or empty -- the plain instances
+// keep their signature and their argument block (its size is part of their device code).
+template <typename A> __device__ __forceinline__ A lr_only(A a) { return a; }
 // (four workgroups per CU up to n = 128)
-template <typename T, int NCP, bool VEC>
-__global__ __launch_bounds__(256, (NCP <= 4 ? 4 : 1)) void k_broyden_lr(const LrArgs<T> a)
+template <typename T, int NCP, bool VEC, typename... Src>
+__global__ __launch_bounds__(256, (NCP <= 4 ? 4 : 1)) void k_broyden_lr(const LrArgs<T> a, const Src... src)
 {
+    constexpr bool SCALED = sizeof...(Src) == 1;
+    static_assert(sizeof...(Src) <= 1, "at most the widths");
     using P2 = typename LrPair<T>::type;
     __shared__ T red[4][lr_len(kLrMaxN)];
     __shared__ T coef[kLrMax];
@@ -115,6 +124,27 @@ __global__ __launch_bounds__(256, (NCP <= 4 ? 4 : 1)) void k_broyden_lr(const Lr
         const T t0 = a.dx[ok0[c] ? col : 0], t1 = a.dx[ok1[c] ? col + 1 : 0];
         d0[c] = ok0[c] ? t0 : T(0);
         d1[c] = ok1[c] ? t1 : T(0);
+    }
+    // 1 / twh of the two columns a load of chunk c brings (lanes past n re-read column 0, or the pair [0, 1] with VEC, as below)
+    // The vector flavour keeps them in registers (n = 128: 128 VGPRs, four workgroups a CU, no scratch). The element-wise
+    // flavour (odd n, offset views) has none to spare under that bound: its reciprocals live in an LDS table, and so does its
+    // copy of dx (d0, d1: zeros past n) -- both in red, which nobody needs until the row loop is over (a barrier then separates
+    // the two uses).
+    constexpr bool INV_LDS = SCALED && !VEC;
+    T* const invt = &red[0][0];
+    T* const dxt = invt + kLrScaledMaxN;
+    T i0[SCALED && !INV_LDS ? NCP : 1], i1[SCALED && !INV_LDS ? NCP : 1];
+    if constexpr (INV_LDS) {
+        const T* __restrict__ twh = lr_only(src...);
+        for (int j = threadIdx.x; j < n; j += blockDim.x) invt[j] = fd_inv_width(twh[j]);
+        for (int j = threadIdx.x; j < 32 * NCP; j += blockDim.x) dxt[j] = j < n ? a.dx[j] : T(0);
+    } else if constexpr (SCALED) {
+        const T* __restrict__ twh = lr_only(src...);
+#pragma unroll
+        for (int c = 0; c < NCP; ++c) {
+            i0[c] = fd_inv_width(twh[coff[c]]);
+            i1[c] = fd_inv_width(twh[coff[c] + 1]);        // (VEC: n is even, the pair [coff, coff + 1] is inside the row)
+        }
     }
     __syncthreads();
     const bool own = p < k;
@@ -160,13 +190,41 @@ __global__ __launch_bounds__(256, (NCP <= 4 ? 4 : 1)) void k_broyden_lr(const Lr
 #pragma unroll
         for (int e = 0; e < UNR; ++e) {
             if (g0 + e < ge) {
+                [[maybe_unused]] int lo = 0;                       // INV_LDS: the lane's column inside a chunk, opaque per trip --
+                if constexpr (INV_LDS) { lo = 2 * p; asm volatile("" : "+v"(lo)); }   // the table reads stay in the loop, not in 32 registers
+                if constexpr (SCALED) {
+#pragma unroll
+                    for (int c = 0; c < NCP; ++c) {
+                        if constexpr (INV_LDS) {
+                            v0[e][c] = fd_scale(v0[e][c], invt[ok0[c] ? 32 * c + lo : 0]);
+                            v1[e][c] = fd_scale(v1[e][c], invt[ok1[c] ? 32 * c + lo + 1 : 0]);
+                            d0[c] = dxt[32 * c + lo];
+                            d1[c] = dxt[32 * c + lo + 1];
+                        } else {
+                            v0[e][c] = fd_scale(v0[e][c], i0[c]);
+                            v1[e][c] = fd_scale(v1[e][c], i1[c]);
+                        }
+                    }
+                }
                 const size_t row = 4 * (g0 + e) + q;
                 const bool rok = row < m;
                 T yn = ynv[e];
                 const T yo = yov[e], ul = ulv[e];
                 T s = ul * cp;
+                if constexpr (SCALED) {
+                    // The row sum as the PLAIN instances hold it after contraction, written out: the compiler is free to choose
+                    // which product of `a b + c d` it fuses, and with the scaling in front of the sum it chose the other one
+                    // (NCP = 1: different bits in s). Every plain instance forms fma(ul, cp, fma(v0, d0, v1 d1)) for the first
+                    // chunk and adds fma(v0, d0, v1 d1) for each further one; tests/test_gpu_lr_scaled.py holds every scaled
+                    // instance to its plain one bit for bit.
+#pragma clang fp contract(off)
+                    s = dfma(ul, cp, dfma(v0[e][0], d0[0], v1[e][0] * d1[0]));
 #pragma unroll
-                for (int c = 0; c < NCP; ++c) s += v0[e][c] * d0[c] + v1[e][c] * d1[c];
+                    for (int c = 1; c < NCP; ++c) s = s + dfma(v0[e][c], d0[c], v1[e][c] * d1[c]);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < NCP; ++c) s += v0[e][c] * d0[c] + v1[e][c] * d1[c];
+                }
                 s = sum16(s);
                 T u = nd * ((yo - yn) + s);                        // LS:1003-1005: axpy(-1, y, mBuffer); gemv; scal(-d)
                 if (!rok) { u = 0; yn = 0; }
@@ -187,6 +245,7 @@ __global__ __launch_bounds__(256, (NCP <= 4 ? 4 : 1)) void k_broyden_lr(const Lr
         }
     }
 
+    if constexpr (INV_LDS) __syncthreads();                  // every wave is done with the table in red
     // the four row groups of the wave, then the four waves of the block, in a fixed order
     auto qsum = [](T v) { v += wave_shfl_xor(v, 16); v += wave_shfl_xor(v, 32); return v; };
 #pragma unroll
@@ -327,10 +386,15 @@ __global__ __launch_bounds__(256) void k_lr_finish(const T* __restrict__ lr, T* 
 }
 
 // fold the k pending terms into J: J[i,:] += u_0[i] dx_0 + ... + u_{k-1}[i] dx_{k-1}, in update order
-template <typename T, int NCP, bool VEC>
+// SCALED: J0 is not in J but in the unscaled difference panel P (widths twh): J[i,:] = fd_scale(P[i,:]) + the same terms in the
+// same order -- the bits of the plain flush of a J that holds the scaled panel. P is only read.
+template <typename T> struct LrFlushSrc { const T* P; const T* twh; };       // SCALED: the panel and its widths
+template <typename T, int NCP, bool VEC, typename... Src>                    // Src: LrFlushSrc<T> (SCALED), or empty
 __global__ __launch_bounds__(256) void k_lr_flush(T* J, const T* __restrict__ U, const T* __restrict__ D,
-                                                  int k, size_t m, int n)
+                                                  int k, size_t m, int n, const Src... src)
 {
+    constexpr bool SCALED = sizeof...(Src) == 1;
+    static_assert(sizeof...(Src) <= 1, "at most the panel and its widths");
     using P2 = typename LrPair<T>::type;
     extern __shared__ unsigned char lr_smem[];
     T* Ds = reinterpret_cast<T*>(lr_smem);                 // k x n
@@ -347,6 +411,14 @@ __global__ __launch_bounds__(256) void k_lr_flush(T* J, const T* __restrict__ U,
         ok1[c] = col + 1 < n;
         coff[c] = ok0[c] ? col : 0;
     }
+    T i0[SCALED ? NCP : 1], i1[SCALED ? NCP : 1];
+    if constexpr (SCALED) {
+#pragma unroll
+        for (int c = 0; c < NCP; ++c) {
+            i0[c] = fd_inv_width(lr_only(src...).twh[coff[c]]);
+            i1[c] = fd_inv_width(lr_only(src...).twh[(VEC || ok1[c]) ? coff[c] + 1 : 0]);
+        }
+    }
     const size_t G = (m + 3) / 4;
     const size_t wave_id = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const size_t nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
@@ -356,6 +428,7 @@ __global__ __launch_bounds__(256) void k_lr_flush(T* J, const T* __restrict__ U,
         const size_t rr = rok ? row : m - 1;
         T* rp = J + rr * (size_t)n;
         const T* sp = rp;
+        if constexpr (SCALED) sp = lr_only(src...).P + rr * (size_t)n;
         T v0[NCP], v1[NCP];
 #pragma unroll
         for (int c = 0; c < NCP; ++c) {
@@ -368,6 +441,7 @@ __global__ __launch_bounds__(256) void k_lr_flush(T* J, const T* __restrict__ U,
                 v0[c] = sp[coff[c]];
                 v1[c] = sp[ok1[c] ? coff[c] + 1 : 0];
             }
+            if constexpr (SCALED) { v0[c] = fd_scale(v0[c], i0[c]); v1[c] = fd_scale(v1[c], i1[c]); }
         }
         for (int l = 0; l < k; ++l) {
             const T ul = U[(size_t)l * m + rr];

@@ -31,6 +31,15 @@ inline thread_local uint64_t tl_launches = 0;
 // one rounding, whatever the compiler's contraction setting: sums that two kernels must form bit for bit alike
 __device__ inline double dfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ inline float dfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// ---- Jacobian element from an element d of the finite-difference DIFFERENCE panel (D[i][j] = f(x + h e_j)_i - f(x - h e_j)_i)
+// and the interval width t = twh[j] of its column: scal(1 / twh, Jj), LS:1047, a zero column for a collapsed interval (LS:1046).
+// The operations of fdp_producer_plain<NCB, true> (jtj_fdp.h): one reciprocal per column, one multiply per element, and the zero
+// is selected on the reciprocal -- a NaN or Inf of d in a collapsed column reads as 0, elsewhere it propagates through the
+// multiply. A kernel that reads the panel through these holds bit for bit what the fused FD kernel would have written to J.
+__device__ __forceinline__ double fd_inv_width(double t) { return t == 0 ? 0.0 : 1.0 / t; }
+__device__ __forceinline__ double fd_scale(double d, double inv) { return inv == 0 ? 0.0 : d * inv; }
+__device__ __forceinline__ double fd_jacobian_element(double d, double t) { return fd_scale(d, fd_inv_width(t)); }
+
 // ---- pending rank-one Broyden terms (broyden_lr.h): sizes shared by the sweep, its reduction and the n x n finish
 constexpr int kLrMax = 16;
 // [ v0 (n) | g0 (n) | w (kLrMax) | h (kLrMax) | uu | uy | yy ]   yy = ||y_new||^2: the trial's sum of squares (LS:1115) rides on

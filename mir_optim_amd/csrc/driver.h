@@ -182,6 +182,13 @@ struct Solver {
     FB fbr = nullptr;          // batched residual callback writing Y row-major (m x p): the pair panel of the fused FD kernels
     FB fbd = nullptr;          // batched residual callback writing the m x n row-major DIFFERENCE panel (fbRowMajorDiff)
     int fd_fused = 0;          // 1: the (+h, -h) pair panel, 2: the difference panel of this refresh is in ws->ypanel and J has not been filled yet
+    // J0 lives UNSCALED in ws->ypanel, scaled by B.twh: the last refresh was the fused kernel of the difference panel and did not
+    // write B.J (a.Jout = nullptr) -- the Broyden sweeps and the flush read the panel and scale what they load (lr_sweep, lr_flush_scaled).
+    // Set by jacobian_products() for the fd_fused == 2 refresh of a solve with read-only Broyden passes (lowrank, n <=
+    // kLrScaledMaxN, no MIR_LSQ_VARIANT_FD_WRITE_J); cleared by the flush, which materialises B.J, and by every other refresh.
+    bool j0_in_panel = false;
+    const T* lr_j0() const { return j0_in_panel ? static_cast<const T*>(ws->ypanel) : B.J; }
+    const T* lr_twh() const { return j0_in_panel ? B.twh : nullptr; }
     // MIR_LSQ_FD_BASE_POINT (fd_entry, solver_jacobian.hip): the caller's fbd also takes p = 2n + 1, so the entry residual f(x0)
     // and the first refresh's difference panel -- same x0 -- come from ONE call. fd_entry_ready: that panel is in ws->ypanel and
     // the first pass's fd_device() has only its bookkeeping left; a solve that ends before that pass discards it.

@@ -30,9 +30,26 @@ hipError_t lr_dispatch(LrClass c, F&& f)
 }
 }  // namespace
 template <typename T>
-hipError_t lr_sweep(const LrArgs<T>& a, int nblk, hipStream_t s)
+hipError_t lr_sweep(const LrArgs<T>& a, int nblk, hipStream_t s, const T* twh)
 {
     if (a.n > kLrMaxN || a.k < 0 || a.k >= kLrMax) return hipErrorInvalidValue;
+    if (twh) {
+        // J is the unscaled difference panel: the scaled instance of the same class
+        if constexpr (std::is_same<T, double>::value) {
+            if (a.n > kLrScaledMaxN) return hipErrorInvalidValue;
+            return lr_dispatch(lr_class_of<T>(a.n, a.J), [&](auto ncp, auto vec) {
+                constexpr int NCP = decltype(ncp)::value;
+                if constexpr (NCP <= kLrScaledMaxN / 32) {
+                    MIRLSQ_LAUNCH((k_broyden_lr<T, NCP, decltype(vec)::value, const T*>), dim3(nblk), dim3(256), 0, s, a, twh);
+                    return hipGetLastError();
+                } else {
+                    return hipErrorInvalidValue;
+                }
+            });
+        } else {
+            return hipErrorInvalidValue;                 // the difference panel exists in f64 only
+        }
+    }
     return lr_dispatch(lr_class_of<T>(a.n, a.J), [&](auto ncp, auto vec) {
         MIRLSQ_LAUNCH((k_broyden_lr<T, decltype(ncp)::value, decltype(vec)::value>), dim3(nblk), dim3(256), 0, s, a);
         return hipGetLastError();
@@ -52,6 +69,28 @@ hipError_t lr_flush(T* J, const T* U, const T* D, int k, size_t m, int n, int nu
     return lr_dispatch(lr_class_of<T>(n, J), [&](auto ncp, auto vec) {
         MIRLSQ_LAUNCH((k_lr_flush<T, decltype(ncp)::value, decltype(vec)::value>), dim3((unsigned)blocks), dim3(256), lds, s, J, U, D, k, m, n);
         return hipGetLastError();
+    });
+}
+
+hipError_t lr_flush_scaled(double* J, const double* P, const double* twh, const double* U, const double* D, int k, size_t m, int n,
+                           int num_cu, hipStream_t s)
+{
+    if (n > kLrScaledMaxN || k < 0 || k > kLrMax || !P || !twh) return hipErrorInvalidValue;
+    const size_t G = (m + 3) / 4;
+    size_t blocks = (G + 3) / 4;
+    if (blocks > (size_t)num_cu * 8) blocks = (size_t)num_cu * 8;
+    if (blocks < 1) blocks = 1;
+    const size_t lds = (size_t)k * n * sizeof(double);
+    const bool aligned = reinterpret_cast<uintptr_t>(J) % 16 == 0 && reinterpret_cast<uintptr_t>(P) % 16 == 0;
+    return lr_dispatch(lr_class(n, aligned), [&](auto ncp, auto vec) {
+        constexpr int NCP = decltype(ncp)::value;
+        if constexpr (NCP <= kLrScaledMaxN / 32) {
+            MIRLSQ_LAUNCH((k_lr_flush<double, NCP, decltype(vec)::value, LrFlushSrc<double>>), dim3((unsigned)blocks), dim3(256), lds, s, J, U, D, k, m, n,
+                          LrFlushSrc<double>{P, twh});
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
     });
 }
 
@@ -85,7 +124,7 @@ hipError_t lr_sumsq_final(const T* partials, int pstride, int nblk, int count, T
 }
 
 #define MIRLSQ_INSTANTIATE(T)                                                                                             \
-    template hipError_t lr_sweep<T>(const LrArgs<T>&, int, hipStream_t);                                                  \
+    template hipError_t lr_sweep<T>(const LrArgs<T>&, int, hipStream_t, const T*);                                        \
     template hipError_t lr_reduce<T>(const T*, int, int, T*, hipStream_t);                                                \
     template hipError_t lr_finish<T>(const T*, T*, const T*, int, int, T*, T*, LmState<T>*, hipStream_t);                 \
     template hipError_t lr_sumsq<T>(const T*, size_t, int, size_t, T*, int, int, hipStream_t);                            \

@@ -3,6 +3,8 @@
 //   full refreshes: finite differences through device callbacks (LS:1016-1050 restructured into panels), through host
 //   callbacks with the reference's thread-manager contract (LS:1018-1049 literally), or the analytic g (LS:1011-1015);
 //   J^T y and J^T J (LS:1052, 1065) with the row-shard all-reduce behind them.
+#include <type_traits>
+
 #include "driver.h"
 #include "launch_util.h"
 #include "misc_kernels.h"
@@ -18,7 +20,15 @@ bool Solver<T>::broyden_lowrank(const T* y_dev, const T* yold_dev)
         const uint64_t launches_before = launches_now();
         struct Excl { Solver* s; uint64_t l0; ~Excl() { s->launches_excluded += s->launches_now() - l0; } } excl{this, launches_before};
         // fold the pending rank-one terms into J (the reference's successive `ger`s, LS:1006) ...
-        if (!ok(lr_flush<T>(B.J, U, B.lrD, lr_k, m, (int)n, ws->num_cu, stream), "broyden flush")) return false;
+        if (j0_in_panel) {
+            // ... J0 is still the unscaled difference panel: B.J = scale(panel) + the terms, and J is in memory from here on
+            if constexpr (std::is_same<T, double>::value) {
+                if (!ok(lr_flush_scaled(B.J, lr_j0(), B.twh, U, B.lrD, lr_k, m, (int)n, ws->num_cu, stream), "broyden flush")) return false;
+            } else {
+                return false;                            // (never set: the difference panel exists in f64 only)
+            }
+            j0_in_panel = false;
+        } else if (!ok(lr_flush<T>(B.J, U, B.lrD, lr_k, m, (int)n, ws->num_cu, stream), "broyden flush")) return false;
         lr_k = 0;
         if (stats) stats->broyden_flushes++;
         // ... and resynchronise: J^T J and J^T y_old recomputed from the flushed J, as the reference's syrk / gemv do
@@ -32,11 +42,11 @@ bool Solver<T>::broyden_lowrank(const T* y_dev, const T* yold_dev)
     // (the pass of a fused round is enqueued by enqueue_fused_tail, solver_loop.hip: the same kernels, the sweep ahead of the
     // decision and the n x n side inside the solve's launch)
     LrArgs<T> a{};
-    a.J = B.J; a.U = U; a.D = B.lrD; a.dx = B.dx_acc; a.dx_dot = &B.st->dx_dot; a.y = y_dev; a.y_old = yold_dev;
+    a.J = lr_j0(); a.U = U; a.D = B.lrD; a.dx = B.dx_acc; a.dx_dot = &B.st->dx_dot; a.y = y_dev; a.y_old = yold_dev;
     a.partials = B.lrpart; a.m = m; a.n = (int)n; a.k = lr_k;
     const int nblk = lr_blocks(m, ws->num_cu), len = lr_len((int)n);
     ev_begin(1);
-    if (!ok(lr_sweep<T>(a, nblk, stream), "broyden sweep")) return false;
+    if (!ok(lr_sweep<T>(a, nblk, stream, lr_twh()), "broyden sweep")) return false;
     ev_end();
     if (!ok(lr_reduce<T>(B.lrpart, nblk, (int)n, B.lrvec, stream), "broyden reduce")) return false;
     if (comm && !allreduce(B.lrvec, (size_t)len, 1)) return false;
@@ -74,7 +84,7 @@ template <typename T>
 bool Solver<T>::jacobian_products(bool broyden, const T* y_dev, const T* yold_dev)
 {
     if (broyden && lowrank) return broyden_lowrank(y_dev, yold_dev);
-    if (!broyden) lr_k = 0;                             // J was refreshed in full: nothing is pending any more
+    if (!broyden) { lr_k = 0; j0_in_panel = false; }    // J was refreshed in full: nothing is pending any more, and J0 is in B.J ...
     JtjArgs<T> a{};
     a.J = B.J; a.Jout = B.J; a.y = y_dev; a.y_old = yold_dev; a.dx = B.dx_acc; a.dx_dot = &B.st->dx_dot;
     a.slabs = B.slabs; a.m = m; a.n = (int)n;
@@ -84,6 +94,12 @@ bool Solver<T>::jacobian_products(bool broyden, const T* y_dev, const T* yold_de
         const JtjOp op = fd_fused == 2 ? JtjOp::fd_diff : JtjOp::fd;
         fd_fused = 0;
         a.J = static_cast<const T*>(ws->ypanel); a.twh = B.twh;
+        // ... unless this is the difference panel and only read-only sweeps will want J0: the 1 GB write of J = D (1 / twh) is
+        // left out, the panel stays where it is until the next refresh replaces it and the sweeps scale what they load
+        if (op == JtjOp::fd_diff && lowrank && n <= (uint32_t)kLrScaledMaxN && !(variant & MIR_LSQ_VARIANT_FD_WRITE_J)) {
+            j0_in_panel = true;
+            a.Jout = nullptr;
+        }
         const bool direct = unpack_in_reduce(op);
         ev_begin(3);
         if (!ok(jtj_run<T>(plan, op, a, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "fd + jtj kernel")) return false;

@@ -365,13 +365,13 @@ bool Solver<T>::enqueue_fused_tail(const T* ytr, bool check_grad, bool lambda_fr
     spec_events_from = events.size();
     if (stats) stats->fused_rounds++;
     LrArgs<T> a{};
-    a.J = B.J; a.U = static_cast<T*>(ws->ulr); a.D = B.lrD; a.dx = B.dx; a.dx_dot = &B.rec[0].new_dx_dot; a.y = ytr; a.y_old = y;
+    a.J = lr_j0(); a.U = static_cast<T*>(ws->ulr); a.D = B.lrD; a.dx = B.dx; a.dx_dot = &B.rec[0].new_dx_dot; a.y = ytr; a.y_old = y;
     a.partials = B.lrpart; a.m = m; a.n = (int)n; a.k = lr_k;
     a.spec_rec = B.rec; a.absTolerance = sd.absTolerance; a.relTolerance = sd.relTolerance;
     const int nblk = lr_blocks(m, ws->num_cu), len = lr_len((int)n);
     spec_enqueue = true;                                 // (the events of the pass run ahead count once it is committed)
     ev_begin(1);
-    const bool swept = ok(lr_sweep<T>(a, nblk, stream), "broyden sweep");
+    const bool swept = ok(lr_sweep<T>(a, nblk, stream, lr_twh()), "broyden sweep");
     ev_end();
     spec_enqueue = false;
     if (!swept || !ok(lr_reduce<T>(B.lrpart, nblk, (int)n, B.lrvec, stream), "broyden reduce")) return false;

@@ -206,7 +206,7 @@ int lm_solve_entry(const S* settings, size_t n_, T* JJ, T* Jy, T* x, T* lower, T
 // the stage-1 partials of the sums (pstride = the workgroup count, so that the region ends with the last partial), the sums, the
 // state and the record -- lies in one allocation of the call's, banded as lm_solve_entry's and preset to the same 0xFF bytes.
 template <typename T, typename R>
-int lr_pass_entry(size_t m, size_t n_, int k, const T* J, T* U, T* D, const T* dx, const T* dx_dot, const T* y, int count,
+int lr_pass_entry(size_t m, size_t n_, int k, const T* J, const T* twh, T* U, T* D, const T* dx, const T* dx_dot, const T* y, int count,
                   const T* y_old, T* JJ, T* Jy, const R* spec, T absTolerance, T relTolerance, T* partials, T* reduced, T* sums,
                   T* jy_inf, int info[6])
 {
@@ -245,7 +245,7 @@ int lr_pass_entry(size_t m, size_t n_, int k, const T* J, T* U, T* D, const T* d
     a.partials = (T*)at(rpart); a.m = m; a.n = n; a.k = k;
     a.spec_rec = spec ? (const ChainRec<T>*)at(rrec) : nullptr;
     a.absTolerance = absTolerance; a.relTolerance = relTolerance;
-    good = lr_sweep<T>(a, nblk, nullptr) == hipSuccess
+    good = lr_sweep<T>(a, nblk, nullptr, twh) == hipSuccess     // twh != nullptr: J is the unscaled difference panel
         && lr_reduce<T>((const T*)at(rpart), nblk, n, (T*)at(rvec), nullptr) == hipSuccess
         && (spec || lr_finish<T>((const T*)at(rvec), D, dx, k, n, JJ, Jy, (LmState<T>*)at(rst), nullptr) == hipSuccess)
         && lr_sumsq<T>(y, m, count, m, (T*)at(rsp), nblk, nblk, nullptr) == hipSuccess
@@ -633,7 +633,7 @@ int mir_lsq_lr_pass_d(size_t m, size_t n, int k, const double* J, double* U, dou
                       double absTolerance, double relTolerance, double* partials, double* reduced, double* sums, double* jy_inf,
                       int info[6])
 {
-    return lr_pass_entry<double>(m, n, k, J, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, spec, absTolerance, relTolerance, partials,
+    return lr_pass_entry<double>(m, n, k, J, nullptr, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, spec, absTolerance, relTolerance, partials,
                                  reduced, sums, jy_inf, info);
 }
 int mir_lsq_lr_pass_s(size_t m, size_t n, int k, const float* J, float* U, float* D, const float* dx, const float* dx_dot,
@@ -641,8 +641,27 @@ int mir_lsq_lr_pass_s(size_t m, size_t n, int k, const float* J, float* U, float
                       float absTolerance, float relTolerance, float* partials, float* reduced, float* sums, float* jy_inf,
                       int info[6])
 {
-    return lr_pass_entry<float>(m, n, k, J, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, spec, absTolerance, relTolerance, partials,
+    return lr_pass_entry<float>(m, n, k, J, nullptr, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, spec, absTolerance, relTolerance, partials,
                                 reduced, sums, jy_inf, info);
+}
+int mir_lsq_lr_pass_scaled_d(size_t m, size_t n, int k, const double* P, const double* twh, double* U, double* D, const double* dx,
+                             const double* dx_dot, const double* y, int count, const double* y_old, double* JJ, double* Jy,
+                             const mir_lsq_lm_solve_record_d* spec, double absTolerance, double relTolerance, double* partials,
+                             double* reduced, double* sums, double* jy_inf, int info[6])
+{
+    if (!twh || n > (size_t)kLrScaledMaxN) return -1;
+    return lr_pass_entry<double>(m, n, k, P, twh, U, D, dx, dx_dot, y, count, y_old, JJ, Jy, spec, absTolerance, relTolerance, partials,
+                                 reduced, sums, jy_inf, info);
+}
+int mir_lsq_lr_flush_scaled_d(size_t m, size_t n, int k, double* J, const double* P, const double* twh, const double* U, const double* D,
+                              int info[2])
+{
+    if (!J || !P || !twh || !U || !D || !info || m == 0 || n == 0 || n > (size_t)kLrScaledMaxN || k < 1 || k > kLrMax) return -1;
+    if (!device_available()) return -2;
+    const LrClass cls = lr_class((int)n, reinterpret_cast<uintptr_t>(J) % 16 == 0 && reinterpret_cast<uintptr_t>(P) % 16 == 0);
+    info[0] = cls.ncp; info[1] = cls.vec;
+    if (lr_flush_scaled(J, P, twh, U, D, k, m, (int)n, query_num_cu(), nullptr) != hipSuccess) { (void)hipDeviceSynchronize(); return -4; }
+    return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -5;
 }
 int mir_lsq_lr_flush_d(size_t m, size_t n, int k, double* J, const double* U, const double* D, int info[2])
 {
