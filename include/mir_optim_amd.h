@@ -635,6 +635,42 @@ int mir_lsq_batched16_covariance_d(const mir_least_squares_settings_d* settings,
  * enqueued on `stream`. -1 bad arguments, -3 m = 0 or (17 m + 272) doubles above the LDS limit, -2 no device, -5 launch. */
 int mir_lsq_batched16_jtj_d(size_t count, size_t m, size_t n, const double* J, const double* y, double* JJ, double* Jy, void* stream);
 
+/* The FITTED CURVE of every problem of a batch on a grid of abscissae of the caller's choice, and its 1-sigma CONFIDENCE BAND --
+ * the eval_uncertainty of a curve-fitting interface -- from the x and the covariance a batched fit left on the device:
+ *     value[k][i] = eval(tq_i; x_k)                                          always written: a pure function of x
+ *     sigma[k][i] = sqrt(max(0, g^T C_k g)),  g = d eval / d x at (tq_i, x_k),  C_k = covariance + k n^2
+ * One kernel launch (csrc/batched_predict.h: a wavefront per problem, a query per lane), enqueued on options->stream; every
+ * pointer is a DEVICE pointer; no allocation, no synchronisation.
+ *   x            count x n                           tq      q values for all problems (tq_stride 0) or count x q (tq_stride q)
+ *   covariance   count x n x n, as the covariance entries above write it; required when sigma is given, else not read
+ *   value        count x q, required                 sigma   count x q, or NULL: not wanted
+ *   lower/upper  both NULL (unbounded, nothing fixed) or both given: n values, or count x n with
+ *                MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM in extras->flags
+ * g is formed as the covariance kernels form a Jacobian row, without weights and data: the model's derivative with
+ * MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN in options->variant (-1 for a model without one), else central differences with
+ * settings->jacobianEpsilon, both points clipped to the box. A parameter with l_j == u_j is FIXED: g_j = 0, and row j and column j
+ * of the covariance are not read. The sum runs over the free indices in a fixed order of fused multiply-adds: the same input
+ * gives the same bits. The conventions of the covariance pass through: when a free diagonal entry C_jj is not finite, every
+ * sigma of that problem is that entry (+inf: a degenerate covariance; NaN: a failed fit); all parameters fixed: sigma = 0.
+ * extras: NULL, or flags only -- one that carries weights or a covariance pointer is answered -1; other flags are ignored.
+ * Returns 0 (also for count == 0 or q == 0, which launch nothing); -1 bad arguments: the model id, implausible options or extras,
+ * a missing settings / x / tq / value pointer, one of lower / upper without the other, sigma without covariance, a tq_stride that
+ * is neither 0 nor q, count or q >= 2^31 -- all answered before a device is looked for (-2); -5 the launch failed.
+ * _s / _d take the MIR_LSQ_MODEL_* ids, mir_lsq_batched16_predict_d the MIR_LSQ_MODEL16_* ids; each answers -1 to the other
+ * family's. A caller's own model: launch_batched_predict<Model> of include/mir_optim_amd_batched.hpp. */
+int mir_lsq_batched_predict_s(const mir_least_squares_settings_s* settings, size_t count, size_t q, int model, const float* x,
+                              const float* lower, const float* upper, const float* tq, size_t tq_stride, const float* covariance,
+                              float* value, float* sigma, const mir_lsq_batched_options* options,
+                              const mir_lsq_batched_extras* extras);
+int mir_lsq_batched_predict_d(const mir_least_squares_settings_d* settings, size_t count, size_t q, int model, const double* x,
+                              const double* lower, const double* upper, const double* tq, size_t tq_stride, const double* covariance,
+                              double* value, double* sigma, const mir_lsq_batched_options* options,
+                              const mir_lsq_batched_extras* extras);
+int mir_lsq_batched16_predict_d(const mir_least_squares_settings_d* settings, size_t count, size_t q, int model, const double* x,
+                                const double* lower, const double* upper, const double* tq, size_t tq_stride,
+                                const double* covariance, double* value, double* sigma, const mir_lsq_batched_options* options,
+                                const mir_lsq_batched_extras* extras);
+
 /* Resident-J solver (include/mir_optim_amd_resident.hpp, launch_resident<Model>): the whole loop of least_squares.d:972-1175
  * in ONE cooperative launch for problems whose Jacobian, residuals and per-row data fit the LDS of the chip (BASELINE
  * cfg 2). The residual model is a compile-time type of the caller's, as on the batched path. Options and statistics of

@@ -70,6 +70,16 @@
 // handled in the kernel) and takes (16 + 2) m + 272 doubles of LDS: m <= 1119. tests/user_model/user_model_n16.hip is the example.
 // Weights and covariance work as above through the trailing extras of launch_batched16 and launch_batched16_covariance<Model>
 // (k_lm_batched16<Model, true>, k_batched16_covariance<Model>); tests/user_model/user_model_n16_weighted.hip is the example.
+//
+// The fitted curve and its confidence band: launch_batched_predict<Model>, at the end of this file, for a model of either width.
+// With x (count x n) and the covariance (count x n x n) a fit left on the device, and q abscissae of the caller's choice (one
+// grid for the batch or one per problem), it writes  value = eval(tq_i; x_k)  and, where wanted,  sigma = sqrt(g^T C_k g),
+// g = d eval / d x at tq_i -- the 1-sigma band of the curve, what a curve-fit front end's eval_uncertainty computes -- with the
+// model's own grad (MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) or the central differences, clipped to the box, that built the
+// covariance; a fixed parameter (l_j == u_j) contributes nothing and its row and column of the covariance are not read. The
+// covariance's conventions pass through: +inf for a problem whose covariance is +inf, NaN for one whose fit failed; value is
+// written for every problem. One kernel (mir_optim_amd/csrc/batched_predict.h: a wave per problem, a query per lane), one launch,
+// no allocation, no synchronisation. tests/user_model/user_model_predict.hip is the example.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -83,6 +93,7 @@
 #include "../mir_optim_amd/csrc/batched_kernel.h"
 #include "../mir_optim_amd/csrc/batched_bounded.h"
 #include "../mir_optim_amd/csrc/batched16_kernel.h"
+#include "../mir_optim_amd/csrc/batched_predict.h"
 
 namespace mir_optim_amd {
 
@@ -449,6 +460,57 @@ int launch_batched16_covariance(const mir_least_squares_settings_d* S, size_t co
 {
     return detail::launch_covariance_with<Model, Kernels, detail::BatchedLayout<Model, true>>(S, count, m, x, lower, upper, t, t_stride, data,
                                                                                               results, opt, extras);
+}
+
+// ---- the fitted curve and its 1-sigma band on a grid of abscissae: k_batched_predict (mir_optim_amd/csrc/batched_predict.h) ----
+namespace detail {
+// THE argument checks of a prediction, all answered -1: the model has the derivative it is asked for; the extras are plausible and
+// carry neither weights nor a covariance pointer (the covariance is an argument here; their flags pass); x, tq and value are
+// there; lower and upper are both NULL or both given; sigma comes with a covariance; tq_stride is 0 or q; count, q < 2^31.
+template <class Model, class T = batched_value_t<Model>>
+bool predict_arguments(const void* S, size_t count, size_t q, const T* x, const T* lower, const T* upper, const T* tq, size_t tq_stride,
+                       const T* covariance, const T* value, const T* sigma, const mir_lsq_batched_options* opt,
+                       const mir_lsq_batched_extras* extras, mir_lsq_batched_extras& e)
+{
+    if (opt && (opt->variant & MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN) && !mirlsq::batched_has_grad<Model>::value) return false;
+    if (!batched_extras(extras, 0, e) || e.weights || e.covariance) return false;
+    if (!S || !x || !tq || !value || (lower == nullptr) != (upper == nullptr) || (sigma && !covariance)) return false;
+    return (tq_stride == 0 || tq_stride == q) && count < ((size_t)1 << 31) && q < ((size_t)1 << 31);
+}
+}  // namespace detail
+
+// value (count x q) = eval(tq_i; x_k) and, when `sigma` (count x q) is given, sigma = sqrt(max(0, g^T C_k g)) with C_k =
+// covariance + k n^2 (count x n x n values, as the covariance entries write them; required with sigma) -- see the top of this
+// file. Every pointer is a DEVICE pointer; the one launch is enqueued on options->stream; no allocation, no synchronisation.
+// tq: q values for all problems (tq_stride 0) or count x q (tq_stride q). lower / upper: both NULL (unbounded, nothing fixed) or
+// both given, n values, or count x n with MIR_LSQ_BATCHED_BOUNDS_PER_PROBLEM in extras->flags; they clip the difference points
+// as in the fit, and l_j == u_j fixes parameter j. settings->jacobianEpsilon is the step of the differences;
+// options->variant: MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN. A model of any width: n <= 8 in float or double, 9 <= n <= 16 in double.
+// Returns 0 (also for count == 0 or q == 0: nothing is launched), -1 bad arguments (detail::predict_arguments), -5 the launch failed.
+template <class Model>
+int launch_batched_predict(const batched_settings_t<Model>* S, size_t count, size_t q, const batched_value_t<Model>* x,
+                           const batched_value_t<Model>* lower, const batched_value_t<Model>* upper,
+                           const batched_value_t<Model>* tq, size_t tq_stride, const batched_value_t<Model>* covariance,
+                           batched_value_t<Model>* value, batched_value_t<Model>* sigma, const mir_lsq_batched_options* opt = nullptr,
+                           const mir_lsq_batched_extras* extras = nullptr)
+{
+    using T = batched_value_t<Model>;
+    detail::BatchedLayout<Model>::checks();
+    mir_lsq_batched_extras e;
+    if (!detail::predict_arguments<Model>(S, count, q, x, lower, upper, tq, tq_stride, covariance, value, sigma, opt, extras, e)) return -1;
+    if (count == 0 || q == 0) return 0;
+    mirlsq::BatchedPredictArgs<T> a{};
+    a.jacobianEpsilon = S->jacobianEpsilon;
+    a.count = (int)count; a.q = (int)q;
+    a.x = x; a.lower = lower; a.upper = upper; a.b_stride = lower ? detail::bound_stride<Model>(e) : 0;
+    a.tq = tq; a.tq_stride = (int)tq_stride;
+    a.variant = opt ? opt->variant : 0;
+    a.cov = covariance; a.value = value; a.sigma = sigma;
+    // a wave per problem and slice of the chunks of 64 queries: enough slices for ~8192 waves in flight, each keeping its C
+    const size_t chunks = (q + 63) / 64, slices = std::min<size_t>(chunks, std::min<size_t>((8192 + count - 1) / count, 65535));
+    hipLaunchKernelGGL(mirlsq::k_batched_predict<Model>, dim3((unsigned)count, (unsigned)slices), dim3(64), 0,
+                       opt ? static_cast<hipStream_t>(opt->stream) : nullptr, a);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
 }  // namespace mir_optim_amd

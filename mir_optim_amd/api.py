@@ -30,7 +30,7 @@ __all__ = [
     "LeastSquaresException", "optimize", "optimizeLeastSquares", "solveBoxQP", "leastSquaresStatusString",
     "mir_least_squares_work_length", "mir_least_squares_iwork_length", "mir_box_qp_work_length",
     "mir_box_qp_iwork_length", "GpuOptions", "Stats", "lib", "workloads_lib", "device_count",
-    "DeviceBuffer", "Stream", "jtj", "fd_jtj", "DEVICE_CALLBACKS", "TIME_KERNELS", "optimizeLeastSquaresBatched", "batchedPosvx", "BATCHED_NO_LADDER", "BATCHED_DEVICE_BOUNDS",
+    "DeviceBuffer", "Stream", "jtj", "fd_jtj", "DEVICE_CALLBACKS", "TIME_KERNELS", "optimizeLeastSquaresBatched", "batchedPosvx", "predictBatched", "BATCHED_ANALYTIC_JACOBIAN", "BATCHED_NO_LADDER", "BATCHED_DEVICE_BOUNDS",
     "solveBoxQPBatched", "BOX_QP_UNCONSTRAINED_SOLUTION",
     "MODEL_EXP_DECAY", "MODEL_EXP3_AFFINE", "MODEL_EXP_DECAY_PAD8", "MODEL16_EXP_HARM16", "MODEL16_GAUSS3_AFFINE", "batched16JtJ", "optimizeLeastSquaresBatched16", "ResultS", "Trace", "TraceRecord", "Spline", "FitSplineResult", "fitSpline",
     "fit_spline_residuals", "variant_lr_cap",
@@ -382,6 +382,11 @@ def lib():
             fn.restype = C.c_int
             fn.argtypes = [C.POINTER(_Sd), sz, sz, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
                            C.c_void_p, C.POINTER(BatchedOptions), C.POINTER(BatchedExtras)]
+        for name, S in (("mir_lsq_batched_predict_s", _Ss), ("mir_lsq_batched_predict_d", _Sd), ("mir_lsq_batched16_predict_d", _Sd)):
+            fn = getattr(L, name)
+            fn.restype = C.c_int
+            fn.argtypes = [C.POINTER(S), sz, sz, C.c_int] + [C.c_void_p] * 4 + [sz] + [C.c_void_p] * 3 \
+                + [C.POINTER(BatchedOptions), C.POINTER(BatchedExtras)]
         L.mir_lsq_batched16_jtj_d.restype = C.c_int
         L.mir_lsq_batched16_jtj_d.argtypes = [sz, sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("box_qp_s", "box_qp_d", "box_qp16_s", "box_qp16_d"):
@@ -874,6 +879,7 @@ def batched16JtJ(J, y):
 
 
 BATCHED_NO_LADDER = 1
+BATCHED_ANALYTIC_JACOBIAN = 2   # MIR_LSQ_BATCHED_ANALYTIC_JACOBIAN: the model's own derivative instead of finite differences
 BATCHED_DEVICE_BOUNDS = 4       # MIR_LSQ_BATCHED_DEVICE_BOUNDS: bounded steps are solved inside the wave kernel (no -100, no fallback)
 BATCHED_ABSOLUTE_SIGMA = 1      # mir_lsq_batched_extras.flags
 BATCHED_BOUNDS_PER_PROBLEM = 2  # mir_lsq_batched_extras.flags: lower / upper hold count x n values, row k the box of problem k
@@ -904,6 +910,63 @@ def batchedPosvx(P, rhs, dtype=np.float32):
     for b in (dP, db, dx, di):
         b.free()
     return x, info
+
+
+_MODEL_N = {MODEL_EXP_DECAY: 3, MODEL_EXP3_AFFINE: 8, MODEL_EXP_DECAY_PAD8: 8, MODEL16_EXP_HARM16: 16, MODEL16_GAUSS3_AFFINE: 11}
+
+
+def predictBatched(model, x, tq, covariance=None, l=None, u=None, settings=None, variant=0, dtype=np.float32):
+    """The fitted curve of every problem of a batch on a grid of abscissae, and its 1-sigma confidence band
+    (mir_lsq_batched_predict_s, with dtype=np.float64 mir_lsq_batched_predict_d; a MODEL16_* id goes to
+    mir_lsq_batched16_predict_d and requires float64). x: count x n fitted parameters; tq: q abscissae for all problems or
+    count x q. Returns value (count x q) = model(tq; x_k) -- or, with covariance (count x n x n, as a batched fit with
+    covariance=True returns it), (value, sigma): sigma = sqrt(g^T C_k g), g the derivative of the model with respect to its
+    parameters at tq, by central differences with settings.jacobianEpsilon clipped to l / u (variant=BATCHED_ANALYTIC_JACOBIAN:
+    the model's own derivative, for a model that has one). l / u: None, n values or count x n, as in
+    optimizeLeastSquaresBatched; a parameter with l_j == u_j is fixed and contributes nothing to the band. sigma is +inf where
+    the covariance is (a degenerate problem) and NaN where the fit had failed; value is computed for every problem.
+    Wrong shapes raise ValueError."""
+    model = int(model)
+    wide = model in _MODELS16
+    if wide and np.dtype(dtype) != np.float64:
+        raise ValueError(f"the MODEL16_* models are evaluated in float64 only, not {np.dtype(dtype)}: pass dtype=np.float64")
+    suf = _batched_suffix(dtype)
+    dtype = np.float32 if suf == "s" else np.float64
+    x = np.ascontiguousarray(x, dtype=dtype)
+    tq = np.ascontiguousarray(tq, dtype=dtype)
+    if x.ndim != 2 or (model in _MODEL_N and x.shape[1] != _MODEL_N[model]):
+        raise ValueError(f"x: count x n{' with n = %d' % _MODEL_N[model] if model in _MODEL_N else ''}, not {x.shape}")
+    count, n = x.shape
+    if tq.ndim not in (1, 2) or (tq.ndim == 2 and tq.shape[0] != count):
+        raise ValueError(f"tq: q values or {count} x q, not {tq.shape}")
+    q = tq.shape[-1]
+    if covariance is not None:
+        covariance = np.ascontiguousarray(covariance, dtype=dtype)
+        if covariance.shape != (count, n, n):
+            raise ValueError(f"covariance: {count} x {n} x {n}, not {covariance.shape}")
+    bounded = l is not None or u is not None
+    lo, up, per_problem = _batched_bounds(l, u, count, n, dtype) if bounded else (None, None, False)
+    S = LeastSquaresSettings(dtype) if settings is None else settings
+    value = np.empty((count, q), dtype=dtype)
+    if count == 0 or q == 0:
+        return value if covariance is None else (value, np.empty((count, q), dtype=dtype))
+    ins = [DeviceBuffer(a) if a is not None else None for a in (x, lo, up, tq, covariance)]
+    outs = [DeviceBuffer(nbytes=value.nbytes, dtype=dtype, shape=value.shape) for _ in range(1 if covariance is None else 2)]
+    ptr = [b.ptr if b is not None else None for b in ins]
+    st = Stream()
+    name = "mir_lsq_batched16_predict_d" if wide else "mir_lsq_batched_predict_" + suf
+    ex = BatchedExtras(flags=BATCHED_BOUNDS_PER_PROBLEM if per_problem else 0)
+    rc = getattr(lib(), name)(C.byref(S), count, q, model, ptr[0], ptr[1], ptr[2], ptr[3], 0 if tq.ndim == 1 else q, ptr[4], outs[0].ptr,
+                              outs[1].ptr if len(outs) == 2 else None, C.byref(BatchedOptions(variant=variant, stream=st.handle)),
+                              C.byref(ex))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed: {rc}")
+    st.synchronize()
+    res = [b.download().copy() for b in outs]
+    for b in ins + outs:
+        if b is not None:
+            b.free()
+    return res[0] if covariance is None else (res[0], res[1])
 
 
 COVARIANCE_ABSOLUTE_SIGMA = 1      # MIR_LSQ_COVARIANCE_ABSOLUTE_SIGMA

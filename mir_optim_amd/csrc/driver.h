@@ -14,6 +14,8 @@
 //   launch_*.hip         the translation units that instantiate the kernels (jtj_plan.h, broyden_launch.h, solve_launch.h)
 //   covariance.hip       Solver<T>::covariance(): one refresh at x, J^T J, its inverse (launch_spd_inverse.hip) -> covariance
 //   batched.hip, batched_d.hip   one-wavefront-per-problem batched fits in float / double: the two instances of batched_host.h
+//   batched_predict.hip, batched_predict_d.hip   fitted curves and confidence bands of the batched fits (batched_predict.h;
+//                        float / double with the 16-wide models): the two instances of batched_predict_host.h
 //   comm.hip             row-shard communicators;  unit_entries.hip
 //   fit_spline.cpp, fit_spline_gpu.hip   fitSpline, a caller of the path: host callbacks / its residuals as kernels (device points)
 //

@@ -21,11 +21,13 @@ from mir_optim_amd import build as hipbuild  # noqa: E402
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only", "-S"]
 # every unit of the two libraries that can carry kernels, and every example of tests/user_model/
-UNITS = [u[:-4] for u in hipbuild.SOLVER_UNITS + hipbuild.WORKLOAD_UNITS if u.endswith(".hip")]
-USER = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(os.path.dirname(hipbuild.HERE), "tests", "user_model", "*.hip")))
 RENAMES = {}        # demangled-name substitutions that pair a kernel whose parameter type was renamed: none
-NEW_UNITS = []      # units and examples of the branch only, whose kernels are listed and not compared: none
-NEW_USER = []
+# units and examples of the branch only, whose kernels are listed and not compared (r25: the fitted-curve kernel)
+NEW_UNITS = ["batched_predict", "batched_predict_d"]
+NEW_USER = ["user_model_predict"]
+UNITS = [u[:-4] for u in hipbuild.SOLVER_UNITS + hipbuild.WORKLOAD_UNITS if u.endswith(".hip") and u[:-4] not in NEW_UNITS]
+USER = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(os.path.dirname(hipbuild.HERE), "tests", "user_model", "*.hip"))
+              if os.path.basename(f)[:-4] not in NEW_USER)
 
 
 def compile_tree(tree, out):
