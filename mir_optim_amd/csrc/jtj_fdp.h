@@ -24,6 +24,9 @@
 // nothing written back), and the m x n DIFFERENCE panel the caller's kernel has already subtracted (FD = false, DIFF = true:
 // mir_lsq_gpu_options.fbRowMajorDiff -- the plain producer applies scal(1 / twh), the consumers write J): half the panel bytes.
 //
+// The difference panel whose caller keeps it as J0 (Jout == nullptr, aligned rows) has a kernel of its own, k_jtj_fdp_nw: the same
+// stages, slabs and MFMA order with store-free consumers (WRITES_J = false) and the lean producer (fdp_producer_lean).
+//
 // Slabs are laid out exactly like k_jtj's (jtj_kernel.h), so k_jtj_slab_reduce finishes the job. Rows past m are clamped on the
 // load side and written as zeros to LDS.
 #pragma once
@@ -218,6 +221,111 @@ __device__ __forceinline__ void fdp_producer_plain(const JtjArgs<double>& a, dou
     }
 }
 
+// LEAN variant of the difference-panel producer, for the store-free kernel (k_jtj_fdp_nw): the same pairs go to the same LDS
+// places with the same arithmetic as in fdp_producer_plain<NCB, true>, but the steady state has no row handling.
+//   * Loads: 16-byte BUFFER loads over this workgroup's rows (the panel) and 8-byte ones over its y -- a scalar stage base
+//     plus a per-lane constant, no address registers, no clamp and no compare against m: what lies past row m - 1 is past the
+//     end of the buffer and reads as zero. Every stage issues the same loads, so the waits are counted across the back edge.
+//     (The offsets are 32-bit: the launcher takes this kernel only when a workgroup's rows span less than 4 GB.)
+//   * Convert: a stage whose 32 rows all exist (every stage but the last of the matrix), in a wave that has neither a padding
+//     column nor a collapsed interval among its columns (decided once per launch), is the multiplies and the LDS writes
+//     alone -- v * inv is what `inv == 0 ? 0 : v * inv` selects when inv != 0, the same bits. Every other stage runs the
+//     selects of the plain producer (zero columns LS:1046, padding, rows past m).
+template <int NCB>
+__device__ __forceinline__ void fdp_producer_lean(const JtjArgs<double>& a, double* smem, int lane, int w, size_t s0, size_t S)
+{
+    using C = JtjFdpCfg<NCB, false>;
+    constexpr int n = C::N;                                // padded
+    constexpr int NI = C::NI;
+    constexpr int HP = n / 2;                              // pairs per padded row
+    const size_t m = a.m;
+    const int nr = a.n;
+    const unsigned hr = (unsigned)(nr / 2);                // pairs per source row
+
+    unsigned voff[NI];                                     // byte offset of the pair inside the wave's RP source rows (padding: column 0)
+    double inv0[NI], inv1[NI];                             // 1 / twh of the pair's two columns (0: collapsed interval)
+    bool sel = nr != n;                                    // this lane needs a select: padding columns are stored as zeros, ...
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int f = 64 * i + lane, jp = f % HP;         // row f / HP of the wave's RP rows, pair column jp
+        const int pc = 2 * jp >= nr ? 0 : jp;
+        voff[i] = 16u * ((unsigned)(f / HP) * hr + (unsigned)pc);
+        const double t0 = a.twh[2 * pc], t1 = a.twh[2 * pc + 1];
+        inv0[i] = t0 == 0 ? 0.0 : 1.0 / t0;
+        inv1[i] = t1 == 0 ? 0.0 : 1.0 / t1;
+        sel = sel || inv0[i] == 0 || inv1[i] == 0;         // ... and so are the columns of collapsed intervals
+    }
+    const bool lean = __builtin_amdgcn_ballot_w64(sel) == 0;   // wave-uniform
+
+    // this workgroup's rows of the panel and of y as buffers: everything past the end of the arrays reads as zero
+    const size_t rowb = s0 * C::RS < m ? s0 * C::RS : m;
+    const size_t left = (m - rowb) * (size_t)nr * sizeof(double), yleft = (m - rowb) * sizeof(double);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double*>(a.J + rowb * (size_t)nr), 0, (int)(left < 0xffffffffull ? left : 0xffffffffull), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ysrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double*>(a.y + rowb), 0, (int)(yleft < 0xffffffffull ? yleft : 0xffffffffull), 0x00020000);
+    const unsigned yoff = 8u * (unsigned)(lane & (C::RP - 1));
+
+    typedef unsigned int fdp_u4 __attribute__((ext_vector_type(4)));
+    typedef unsigned int fdp_u2 __attribute__((ext_vector_type(2)));
+    fdp_u4 b[2][NI];                                       // two stages of loads in flight, as in the plain producer
+    fdp_u2 yb[2] = {{0, 0}, {0, 0}};
+    const unsigned Su = (unsigned)S;
+    auto issue = [&](unsigned s, auto B) {
+        constexpr int bb = decltype(B)::value;
+        const unsigned sc = s < Su ? s : Su - 1;           // past the end the last stage is read again
+        const unsigned r0 = sc * C::RS + (unsigned)(C::RP * w);   // the wave's first row among the workgroup's rows
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+            b[bb][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff[i], (int)(r0 * (unsigned)nr * 8u), 2);   // nt: the panel is read once
+        yb[bb] = __builtin_amdgcn_raw_buffer_load_b64(ysrc, (int)yoff, (int)(r0 * 8u), 0);
+    };
+    auto convert = [&](size_t s, auto B, auto F) {
+        constexpr int bb = decltype(B)::value;
+        double* slot = smem + (s & 1) * C::SLOT_DOUBLES;
+        const size_t row0 = (s0 + s) * C::RS + C::RP * (size_t)w;
+        const double y = __builtin_bit_cast(double, yb[bb]);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            fdp_v2d v = __builtin_bit_cast(fdp_v2d, b[bb][i]);
+            if constexpr (decltype(F)::value) {            // a full stage of a wave without padding or zero columns
+                v.x = v.x * inv0[i];                       // scal(1 / twh, Jj), LS:1047
+                v.y = v.y * inv1[i];
+            } else {
+                v.x = inv0[i] == 0 ? 0.0 : v.x * inv0[i];  // scal(1 / twh, Jj), LS:1047 (LS:1046: zero column)
+                v.y = inv1[i] == 0 ? 0.0 : v.y * inv1[i];
+                const int f = 64 * i + lane;               // (recomputed here: the steady state keeps no row or padding tables)
+                if (2 * (f % HP) >= nr || row0 + f / HP >= m) v = fdp_v2d{0.0, 0.0};
+            }
+            *reinterpret_cast<fdp_v2d*>(slot + w * C::RP * n + 2 * (64 * i + lane)) = v;
+        }
+        if constexpr (decltype(F)::value) { if (lane < C::RP) slot[C::RS * n + C::RP * w + lane] = y; }
+        else { if (lane < C::RP) slot[C::RS * n + C::RP * w + lane] = (row0 + lane < m) ? y : 0.0; }
+    };
+
+    // The stage pairs run without a test between them and an odd last stage is peeled off, so the back edge has ONE state (stage
+    // t's loads, then stage t + 1's) and every wait in a convert is counted for its own stage only.
+    const size_t fs = m / C::RS > s0 ? m / C::RS - s0 : 0;             // this workgroup's stages before the first partial one
+    const unsigned nlean = lean ? (unsigned)(fs < S ? fs : S) : 0u;
+    auto step = [&](unsigned s, auto U) {
+        if (s < nlean) convert(s, U, IntC<1>{});
+        else convert(s, U, IntC<0>{});
+        issue(s + 2, U);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // my LDS writes of the stage are done
+        __builtin_amdgcn_s_barrier();                        // the stage is complete for the consumers
+    };
+    if (Su > 0) {
+        issue(0, IntC<0>{});
+        issue(1, IntC<1>{});
+        unsigned t = 0;
+        for (; t + 1 < Su; t += 2) {
+            step(t, IntC<0>{});
+            step(t + 1, IntC<1>{});
+        }
+        if (t < Su) step(t, IntC<0>{});
+    }
+}
+
 // FLAT variant of the plain / difference-panel producer, for sources whose rows do not start on 16-byte boundaries -- ODD n
 // (LS:911-926: the reference is generic in n) or an offset view of J. A wave's RP rows are RP n CONTIGUOUS doubles of the source
 // (RP is even, so is the index of their first double): they are read as a flat array of pairs with 16-byte BUFFER loads --
@@ -319,7 +427,17 @@ __device__ __forceinline__ void fdp_producer_plain_flat(const JtjArgs<double>& a
     }
 }
 
-template <int NCB, int ROLE, bool FD = true, bool DIFF = false, bool PRODUCER_WRITES_J = false>
+// accumulator blocks of a role, i.e. its MFMAs per four-row group
+template <int NCB, int ROLE> constexpr int jtj_role_blocks()
+{
+    int c = 0;
+    for (int i = 0; i < jtj_nacc<NCB>(); ++i) c += jtj_owns<NCB, 4, ROLE>(i) ? 1 : 0;
+    return c;
+}
+
+// WRITES_J = false: the store-free instance (the caller keeps the difference panel itself as J, Jout == nullptr): no role has a
+// store path, a row compare or a Jout test -- roles 2 and 3 run the loop of role 1 over their own blocks.
+template <int NCB, int ROLE, bool FD = true, bool DIFF = false, bool PRODUCER_WRITES_J = false, bool WRITES_J = true>
 __device__ __forceinline__ void fdp_consumer(const JtjArgs<double>& a, const double* smem, int lane, size_t s0, size_t S)
 {
     using T = double;
@@ -349,7 +467,7 @@ __device__ __forceinline__ void fdp_consumer(const JtjArgs<double>& a, const dou
             if constexpr (ROLE == 0) g.y = slot[C::RS * n + 4 * gi + q];
         };
         auto side = [&](int gi, const Grp& g) {
-            if constexpr ((FD || DIFF) && ROLE >= 2 && !PRODUCER_WRITES_J) {
+            if constexpr ((FD || DIFF) && ROLE >= 2 && !PRODUCER_WRITES_J && WRITES_J) {
                 // the Jacobian rows leave through roles 2 and 3 (column blocks c = ROLE (mod 2))
                 const size_t row = row0 + 4 * gi + q;
                 if (row < m && a.Jout) {                   // Jout == nullptr: the caller keeps the panel itself as J (unscaled)
@@ -372,17 +490,41 @@ __device__ __forceinline__ void fdp_consumer(const JtjArgs<double>& a, const dou
                     if (jtj_owns<NCB, 4, ROLE>(I * (I + 1) / 2 + Jb2))
                         acc[I * (I + 1) / 2 + Jb2] = Mma<T>::mma(g.v[I], g.v[Jb2], acc[I * (I + 1) / 2 + Jb2]);   // LS:1065
         };
+        // The store-free instance: the LDS reads of group g + 1 are dealt one by one between the first MFMAs of group g, in every role
+        // (left alone, the compiler bunches the reads of a stage's last groups in front of their MFMAs and waits for them).
+        // Only the order of issue is pinned; the MFMAs of one accumulator depend on each other and stay in row order.
+        // (Role 0 at NCB <= 6 is left to the compiler: pinned, it spills LDS addresses that it otherwise keeps in registers.)
+        constexpr int NM = jtj_role_blocks<NCB, ROLE>();                      // MFMAs per group
+        constexpr int NR = (NCB + 1) / 2 + (ROLE == 0 ? 1 : 0);               // ds_read2_b64 per group (role 0: and y)
+        auto pace = [&](auto READS, auto MFMAS) {
+            if constexpr (!WRITES_J && (ROLE != 0 || NCB >= 7)) {
+                if constexpr (!decltype(MFMAS)::value) __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);   // the stage's first reads
+                else if constexpr (!decltype(READS)::value) __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);   // its last MFMAs
+                else {
+                    if constexpr (NM > 0) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    static_for<NR>([&](auto K) {
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                        if constexpr (decltype(K)::value + 1 < NM) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    });
+                    constexpr int rest = NM - (NM < NR + 1 ? NM : NR + 1);
+                    if constexpr (rest > 0) __builtin_amdgcn_sched_group_barrier(0x008, rest, 0);
+                }
+            }
+        };
         Grp ga, gb;
         read(0, ga);
+        pace(IntC<1>{}, IntC<0>{});
         side(0, ga);
 #pragma unroll
         for (int gi = 0; gi < C::GPS; gi += 2) {
             if (gi + 1 < C::GPS) read(gi + 1, gb);
             mfmas(ga);
+            if (gi + 1 < C::GPS) pace(IntC<1>{}, IntC<1>{}); else pace(IntC<0>{}, IntC<1>{});
             if (gi + 1 < C::GPS) {
                 side(gi + 1, gb);
                 if (gi + 2 < C::GPS) read(gi + 2, ga);
                 mfmas(gb);
+                if (gi + 2 < C::GPS) pace(IntC<1>{}, IntC<1>{}); else pace(IntC<0>{}, IntC<1>{});
                 if (gi + 2 < C::GPS) side(gi + 2, ga);
             }
         }
@@ -430,6 +572,31 @@ __global__ __launch_bounds__(kJtjFdpThreads) __attribute__((amdgpu_waves_per_eu(
     else if constexpr (FD) fdp_producer<NCB>(a, smem, lane, wave - 4, s0, S);
     else if constexpr (ELEM) fdp_producer_plain_flat<NCB, DIFF>(a, smem, lane, wave - 4, s0, S);
     else fdp_producer_plain<NCB, DIFF>(a, smem, lane, wave - 4, s0, S);
+}
+
+// The aligned difference panel with Jout == nullptr (the caller keeps the panel itself as J0 and scales it in its sweeps): J^T J
+// and J^T y alone, with the store-free consumers and the lean producer. A kernel of its own name, so that every k_jtj_fdp
+// instance keeps its name and its code. Same stage partition, grid, LDS and slabs.
+template <int NCB>
+__global__ __launch_bounds__(kJtjFdpThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_jtj_fdp_nw(JtjArgs<double> a)
+{
+    using C = JtjFdpCfg<NCB, false>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char fdp_smem[];
+    double* smem = reinterpret_cast<double*>(fdp_smem);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const size_t Stot = (a.m + C::RS - 1) / C::RS;
+    const size_t per = (Stot + gridDim.x - 1) / gridDim.x;
+    const size_t s0 = (size_t)blockIdx.x * per < Stot ? (size_t)blockIdx.x * per : Stot;
+    const size_t s1 = s0 + per < Stot ? s0 + per : Stot;
+    const size_t S = s1 - s0;
+
+    if (wave == 0) fdp_consumer<NCB, 0, false, true, false, false>(a, smem, lane, s0, S);
+    else if (wave == 1) fdp_consumer<NCB, 1, false, true, false, false>(a, smem, lane, s0, S);
+    else if (wave == 2) fdp_consumer<NCB, 2, false, true, false, false>(a, smem, lane, s0, S);
+    else if (wave == 3) fdp_consumer<NCB, 3, false, true, false, false>(a, smem, lane, s0, S);
+    else fdp_producer_lean<NCB>(a, smem, lane, wave - 4, s0, S);
 }
 
 }  // namespace mirlsq

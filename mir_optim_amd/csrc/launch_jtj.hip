@@ -43,6 +43,12 @@ hipError_t fdp_one(const JtjLaunch& l, const JtjArgs<double>& a, hipStream_t s)
     using FC = JtjFdpCfg<NCB, FD>;
     static_assert(jtj_fdp_lds_bytes(NCB, FD) == FC::LDS_BYTES && jtj_fdp_flat_bytes(NCB) == FC::N * sizeof(double), "jtj_plan.h: k_jtj_fdp LDS size");
     if constexpr (!FD) if (l.flat) return launch_one<k_jtj_fdp<NCB, FD, DIFF, true>>(l, FC::THREADS, s, a);
+    // the store-free instance: the aligned difference panel whose caller keeps it as J0 (the flat producer writes J itself);
+    // its producer addresses a workgroup's rows with 32-bit byte offsets
+    if constexpr (DIFF) if (a.Jout == nullptr) {
+        const size_t stages = (a.m + FC::RS - 1) / FC::RS, per = (stages + l.nblk - 1) / l.nblk;
+        if (per * FC::RS * (size_t)a.n * sizeof(double) < (size_t{1} << 32)) return launch_one<k_jtj_fdp_nw<NCB>>(l, FC::THREADS, s, a);
+    }
     return launch_one<k_jtj_fdp<NCB, FD, DIFF>>(l, FC::THREADS, s, a);
 }
 // k_jtj_fdp8 (jtj_fdp8.h); PLAIN: J^T J of a given J
