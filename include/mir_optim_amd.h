@@ -749,8 +749,9 @@ int mir_lsq_fd_diff_jtj_d(size_t m, size_t n, const double* Drm, const double* t
                           double* JJ, double* Jy, void* stream, float* kernel_ms);
 /* Which kernel those entries and the solver launch (csrc/jtj_plan.h; host code, no device needed): element size 4 / 8, a device
  * of num_cu compute units, op 0 = plain J^T J, 1 = behind the Broyden rewrite (MIR_LSQ_VARIANT_BROYDEN_REWRITE), 2 = the pair
- * panel, 3 = the difference panel; aligned16: J is 16-byte aligned. out = { family (0 none: not covered, 1 k_jtj, 2 k_jtj_fdp,
- * 3 k_jtj_pc32, 4 k_jtj8, 5 k_jtj_fdp8, 6 k_jtj_wide), 16-column blocks the kernel is compiled for (k_jtj_wide: of n), 1 = the
+ * panel, 3 = the difference panel, 4 = the difference panel whose caller keeps it as J (mir_lsq_fd_diff_jtj_d with J = NULL);
+ * aligned16: J is 16-byte aligned. out = { family (0 none: not covered, 1 k_jtj, 2 k_jtj_fdp, 3 k_jtj_pc32, 4 k_jtj8,
+ * 5 k_jtj_fdp8, 6 k_jtj_wide, 7 k_jtj_fdp_nw), 16-column blocks the kernel is compiled for (k_jtj_wide: of n), 1 = the
  * flat producer of k_jtj_fdp, grid x, grid y (tile-pair jobs), dynamic LDS bytes, slabs written, elements per slab, block count
  * the slab reduction is given (0: the tile pairs' own reduction), slab elements a workspace holds }. Returns 0, or -1 (arguments). */
 int mir_lsq_jtj_plan(size_t elem_size, size_t m, size_t n, int num_cu, int op, int aligned16, size_t out[10]);

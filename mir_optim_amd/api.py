@@ -1446,8 +1446,8 @@ def jtj(J, y, y_old=None, dx=None, dtype=np.float64):
     return out
 
 
-JTJ_OPS = ("plain", "rewrite", "fd", "fd_diff")
-JTJ_FAMILIES = ("none", "stream", "fdp", "pc32", "ring8", "fdp8", "wide")
+JTJ_OPS = ("plain", "rewrite", "fd", "fd_diff", "fd_diff_keep")
+JTJ_FAMILIES = ("none", "stream", "fdp", "pc32", "ring8", "fdp8", "wide", "fdp_nw")
 
 
 def jtj_plan(elem_size, m, n, num_cu, op, aligned=True):

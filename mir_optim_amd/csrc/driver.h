@@ -337,7 +337,7 @@ struct Solver {
     bool plain_products(const T* y_vec);
     bool unpack_in_reduce(JtjOp op) const { return !comm && jtj_unpacks(plan, op); }
     JtjUnpack<T> unpack_target() { JtjUnpack<T> u; u.JJ = B.JJ; u.Jy = B.Jy; return u; }
-    bool finish_products(bool direct);
+    bool run_products(JtjOp op, const JtjArgs<T>& a, int kind, const char* what);
     bool jacobian_products(bool broyden, const T* y_dev, const T* yold_dev);
     bool fd_panel(size_t& pb, bool& use_diff);
     void fd_widths_host();

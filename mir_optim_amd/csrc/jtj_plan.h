@@ -4,26 +4,30 @@
 //
 // Operations (JtjOp): plain = J^T J + J^T y of a given J (LS:1052, 1065); rewrite = the same behind the Broyden update as the
 // literal restatement of LS:1003-1006, J rewritten (MIR_LSQ_VARIANT_BROYDEN_REWRITE); fd = finite-difference pair panel -> J,
-// J^T J, J^T y (LS:1041-1047 fused); fd_diff = the same from the difference panel. Kernel by shape and operation:
-//   shape                                      plain               rewrite               fd            fd_diff
-//   f64, n <= 128                              fdp <., false> (1)  stream <., ., true>   fdp <., true> fdp <., false, true> (1)
-//   f64, 128 < n <= 256, n % 16 == 0, m even   ring8               ring8, Broyden flag   fdp8          fdp8 <., true> (2)
-//   f64, 128 < n <= 256, the other n and m     fdp8 <., false, true>   wide (3)          fdp8          fdp8 <., true> (2)
-//   f32, n <= 128, n % 4 == 0                  pc32 (4)            stream <., ., true>   none          none
-//   f32, n <= 128, n % 4 != 0                  stream              stream <., ., true>   none          none
-//   n > 256; f32, n > 128                      wide                wide (3)              none          none
-// stream = k_jtj (register streaming), fdp = k_jtj_fdp, pc32 = k_jtj_pc32, ring8 = k_jtj8 (eight-wave LDS-DMA ring),
-// fdp8 = k_jtj_fdp8 (compiled for n rounded up to a multiple of 32), wide = k_jtj_wide (64-column tile-pair jobs, any n).
+// J^T J, J^T y (LS:1041-1047 fused); fd_diff = the same from the difference panel; fd_diff_keep = the difference panel -> J^T J,
+// J^T y alone: J is not written, the caller keeps the panel itself as J0 (Jout == nullptr). Kernel by shape and operation:
+//   shape                                      plain               rewrite               fd            fd_diff                   fd_diff_keep
+//   f64, n <= 128                              fdp <., false> (1)  stream <., ., true>   fdp <., true> fdp <., false, true> (1)  fdp_nw (5)
+//   f64, 128 < n <= 256, n % 16 == 0, m even   ring8               ring8, Broyden flag   fdp8          fdp8 <., true> (2)        as fd_diff
+//   f64, 128 < n <= 256, the other n and m     fdp8 <., false, true>   wide (3)          fdp8          fdp8 <., true> (2)        as fd_diff
+//   f32, n <= 128, n % 4 == 0                  pc32 (4)            stream <., ., true>   none          none                      none
+//   f32, n <= 128, n % 4 != 0                  stream              stream <., ., true>   none          none                      none
+//   n > 256; f32, n > 128                      wide                wide (3)              none          none                      none
+// stream = k_jtj (register streaming), fdp = k_jtj_fdp, fdp_nw = k_jtj_fdp_nw (fdp's store-free instance: same grid, LDS, slabs),
+// pc32 = k_jtj_pc32, ring8 = k_jtj8 (eight-wave LDS-DMA ring), fdp8 = k_jtj_fdp8 (compiled for n rounded up to a multiple of 32),
+// wide = k_jtj_wide (64-column tile-pair jobs, any n).
 // (1) the flat producer (8-byte aligned loads) for odd n, for the difference panel with n % 16 != 0 and -- decided at the launch,
 //     jtj_resolve -- for a J that is not 16-byte aligned.  (2) n % 64 == 0 only (n = 192, 256), else none.
 // (3) k_broyden_wide (n <= 256) / k_broyden_rows in front.  (4) a J that is not 16-byte aligned: stream_fallback (jtj_resolve).
+// (5) where fd_diff is fdp's strided producer (n % 16 == 0) and a workgroup's rows span less than 4 GB (k_jtj_fdp_nw addresses them
+//     with 32-bit byte offsets); else fd_diff's entry: fdp with a null Jout. A panel that is not 16-byte aligned: fdp's flat producer.
 //
-// Offset views. Only J (plain, rewrite) and the difference panel / Jout (fd_diff) may be element-aligned views handed to a unit
+// Offset views. Only J (plain, rewrite) and the difference panel / Jout (fd_diff, fd_diff_keep) may be element-aligned views handed to a unit
 // entry; y, y_old, dx, twh and the pair panel of `fd` are the library's own buffers and always 16-byte aligned. What is verified,
 // at kernel level (tests/jtj_cases.py, tests/test_gpu_jtj_cells.py; tests/test_jtj_cell_coverage.py proves that every instance
 // launch_jtj.hip compiles is in that list): with every buffer between NaN guard bands that must come back bit-identical, each
 // instance is bit-exact on exact-integer data, inside the forward bound gamma_m |J|^T |J| on random data, deterministic, keeps a
-// NaN of the last row to its row and column, and -- stream, fdp's flat producer, fdp8's plain flavour, wide and the two reroutings
+// NaN of the last row to its row and column, and -- stream, fdp's flat producer, fdp8's plain flavour, wide and the reroutings
 // of jtj_resolve -- gives the bits of the aligned run for a J one element off the 16-byte grid.
 // OPEN: ring8 at an offset pointer. k_jtj8 issues 16-byte global_load_lds from J, y and y_old, jtj_resolve keeps ring8 for an
 // unaligned J, and nothing in the code establishes that a 16-byte LDS-DMA from an 8-byte-aligned address is defined. It is not
@@ -71,6 +75,7 @@ constexpr int kWideSlabLen = (kWideTile * kWideTile * 4 + kWideTile) * kWave;   
 // dynamic LDS of the kernels that size it at compile time (launch_jtj.hip asserts the match with the kernels' Cfg structs)
 constexpr size_t jtj8_lds_bytes(int ncb) { return (size_t)4 * 16 * 16 * ncb * 8 + 2 * 4 * 1024; }   // four 16-row stages + the y / y_old rings
 constexpr size_t jtj_fdp_lds_bytes(int ncb, bool fd) { return (size_t)2 * (fd && ncb % 4 ? 16 : 32) * (16 * ncb + 1) * 8; }   // two stages of 16 / 32 rows + y
+constexpr int kJtjFdpStageRows = 32;                                                                // JtjFdpCfg<NCB, false>::RS
 constexpr size_t jtj_fdp_flat_bytes(int ncb) { return (size_t)16 * ncb * 8; }                       // + the 1 / twh table of the flat producer
 constexpr size_t jtj_fdp8_lds_bytes(int ncb) { return (size_t)2 * 16 * (16 * ncb + 17) * 8; }
 constexpr size_t jtj_pc32_lds_bytes(int ncb) { return (size_t)2 * 64 * (16 * ncb + 17) * 4; }
@@ -82,8 +87,8 @@ struct JtjUnpack {
     T* JJ = nullptr; T* Jy = nullptr;
 };
 
-enum class JtjKernel { none, stream, fdp, pc32, ring8, fdp8, wide };   // none: the shape is not covered for this operation
-enum class JtjOp { plain, rewrite, fd, fd_diff };
+enum class JtjKernel { none, stream, fdp, pc32, ring8, fdp8, wide, fdp_nw };   // none: the shape is not covered for this operation
+enum class JtjOp { plain, rewrite, fd, fd_diff, fd_diff_keep };
 struct JtjLaunch {
     JtjKernel kernel = JtjKernel::none;
     int ncb = 0;        // 16-column blocks the kernel is compiled for = the layout of its slabs (fdp8: even, >= ceil(n / 16)); wide: ceil(n / 16)
@@ -94,9 +99,13 @@ struct JtjLaunch {
     bool flat = false;  // fdp: the flat producer
 };
 struct JtjPlan {
-    JtjLaunch plain, rewrite, fd, fd_diff;
+    JtjLaunch plain, rewrite, fd, fd_diff, fd_diff_keep;
     JtjLaunch stream_fallback;      // what `plain` becomes when J is not 16-byte aligned (pc32 only; else none)
-    const JtjLaunch& of(JtjOp op) const { return op == JtjOp::plain ? plain : (op == JtjOp::rewrite ? rewrite : (op == JtjOp::fd ? fd : fd_diff)); }
+    const JtjLaunch& of(JtjOp op) const
+    {
+        const JtjLaunch* const e[] = {&plain, &rewrite, &fd, &fd_diff, &fd_diff_keep};
+        return *e[(int)op];
+    }
 };
 
 template <typename T>
@@ -125,7 +134,7 @@ JtjPlan jtj_plan(size_t m, int n, int num_cu)
         // fdp8, any n: compiled for an even number of blocks; ring8 and fdp8: 16-row stages, at least ~8 a workgroup, one workgroup per CU
         const int ncb8 = 2 * ((n + 31) / 32), nblk = grid(16, 8, (size_t)num_cu);
         p.fd = {K::fdp8, ncb8, nblk, 1, slab_len(ncb8), jtj_fdp8_lds_bytes(ncb8)};
-        if (n % 64 == 0) p.fd_diff = p.fd;      // two columns per 16-byte load: whole loads per row
+        if (n % 64 == 0) p.fd_diff = p.fd_diff_keep = p.fd;      // two columns per 16-byte load: whole loads per row
         if (n % 16 == 0 && m % 2 == 0) p.plain = p.rewrite = {K::ring8, ncb, nblk, 1, slab_len(ncb), jtj8_lds_bytes(ncb)};
         else { p.plain = p.fd; p.rewrite = wide(); }
         return p;
@@ -159,6 +168,10 @@ JtjPlan jtj_plan(size_t m, int n, int num_cu)
         p.plain.flat = n % 2 != 0;
         p.fd_diff.flat = n % 16 != 0;
         for (JtjLaunch* l : {&p.plain, &p.fd_diff}) if (l->flat) l->lds += jtj_fdp_flat_bytes(ncb);
+        // the store-free instance addresses a workgroup's rows (`per` stages of kJtjFdpStageRows) with 32-bit byte offsets
+        p.fd_diff_keep = p.fd_diff;
+        const size_t stages = (m + kJtjFdpStageRows - 1) / kJtjFdpStageRows, per = (stages + p.fd_diff.nblk - 1) / p.fd_diff.nblk;
+        if (!p.fd_diff.flat && per * kJtjFdpStageRows * (size_t)n * sizeof(double) < (size_t{1} << 32)) p.fd_diff_keep.kernel = K::fdp_nw;
     } else if (n % 4 == 0) {
         // 64-row stages, at least ~4 a workgroup, two workgroups per CU
         p.plain = {K::pc32, ncb, grid(64, 4, (size_t)num_cu * 2), 1, slab_len(ncb), jtj_pc32_lds_bytes(ncb)};
@@ -171,12 +184,14 @@ JtjPlan jtj_plan(size_t m, int n, int num_cu)
 
 // The two choices that depend on the POINTER, made at the launch: k_jtj_pc32 reads J with 16-byte loads of four floats and
 // k_jtj_fdp's strided producer with 16-byte loads of two doubles; a J that is not 16-byte aligned (an offset view handed to a
-// unit entry) takes the register-streaming kernel / the flat producer (the pair panel of `fd` is the library's own buffer).
+// unit entry) takes the register-streaming kernel / the flat producer (the pair panel of `fd` is the library's own buffer);
+// so does the store-free instance, whose lean producer loads 16 bytes too.
 inline JtjLaunch jtj_resolve(const JtjPlan& p, JtjOp op, bool aligned16)
 {
     JtjLaunch l = p.of(op);
     if (aligned16) return l;
     if (l.kernel == JtjKernel::pc32) return p.stream_fallback;
+    if (l.kernel == JtjKernel::fdp_nw) l.kernel = JtjKernel::fdp;      // the lean producer's 16-byte loads: the flat one, as fd_diff
     if (l.kernel == JtjKernel::fdp && op != JtjOp::fd && !l.flat) { l.flat = true; l.lds += jtj_fdp_flat_bytes(l.ncb); }
     return l;
 }
@@ -185,7 +200,7 @@ inline JtjLaunch jtj_resolve(const JtjPlan& p, JtjOp op, bool aligned16)
 inline size_t jtj_slab_elems(const JtjPlan& p)
 {
     size_t e = 0;
-    for (const JtjLaunch* l : {&p.plain, &p.rewrite, &p.fd, &p.fd_diff, &p.stream_fallback}) {
+    for (const JtjLaunch* l : {&p.plain, &p.rewrite, &p.fd, &p.fd_diff, &p.fd_diff_keep, &p.stream_fallback}) {
         const size_t el = (size_t)l->nblk * l->njobs * l->slab_len;
         e = e > el ? e : el;
     }
@@ -197,8 +212,9 @@ inline bool jtj_unpacks(const JtjPlan& p, JtjOp op) { return p.of(op).kernel != 
 
 // ---- launch entry points (launch_jtj.hip; instantiated for double and float). Every kernel they launch is counted in
 //      tl_launches. `packed` receives [J^T J lower | J^T y]; `u` additionally the unpacked form (see JtjUnpack).
-// the operation `op` on a.J -- plain / rewrite: J; fd: the m x 2n row-major pair panel, fd_diff: the m x n difference panel
-// D_ij = f(x + h e_j)_i - f(x - h e_j)_i (both with a.twh; a.Jout receives J). hipErrorInvalidValue: the shape is not covered.
+// the operation `op` on a.J -- plain / rewrite: J; fd: the m x 2n row-major pair panel, fd_diff / fd_diff_keep: the m x n difference
+// panel D_ij = f(x + h e_j)_i - f(x - h e_j)_i (all with a.twh; a.Jout receives J -- fd_diff_keep: a.Jout == nullptr, and only then).
+// hipErrorInvalidValue: the shape is not covered, or a.Jout does not fit the operation.
 template <typename T>
 hipError_t jtj_run(const JtjPlan& p, JtjOp op, const JtjArgs<T>& a, T* packed, hipStream_t s, const JtjUnpack<T>& u = {});
 // packed [J^T J lower | J^T y] -> full symmetric JJ, Jy, st->jy_inf (behind a communicator's all-reduce)

@@ -42,13 +42,8 @@ hipError_t fdp_one(const JtjLaunch& l, const JtjArgs<double>& a, hipStream_t s)
 {
     using FC = JtjFdpCfg<NCB, FD>;
     static_assert(jtj_fdp_lds_bytes(NCB, FD) == FC::LDS_BYTES && jtj_fdp_flat_bytes(NCB) == FC::N * sizeof(double), "jtj_plan.h: k_jtj_fdp LDS size");
+    static_assert(JtjFdpCfg<NCB, false>::RS == kJtjFdpStageRows, "jtj_plan.h: the stage of the 4 GB rule of fd_diff_keep");
     if constexpr (!FD) if (l.flat) return launch_one<k_jtj_fdp<NCB, FD, DIFF, true>>(l, FC::THREADS, s, a);
-    // the store-free instance: the aligned difference panel whose caller keeps it as J0 (the flat producer writes J itself);
-    // its producer addresses a workgroup's rows with 32-bit byte offsets
-    if constexpr (DIFF) if (a.Jout == nullptr) {
-        const size_t stages = (a.m + FC::RS - 1) / FC::RS, per = (stages + l.nblk - 1) / l.nblk;
-        if (per * FC::RS * (size_t)a.n * sizeof(double) < (size_t{1} << 32)) return launch_one<k_jtj_fdp_nw<NCB>>(l, FC::THREADS, s, a);
-    }
     return launch_one<k_jtj_fdp<NCB, FD, DIFF>>(l, FC::THREADS, s, a);
 }
 // k_jtj_fdp8 (jtj_fdp8.h); PLAIN: J^T J of a given J
@@ -64,7 +59,7 @@ template <typename T>
 hipError_t launch_kernel(const JtjLaunch& l, JtjOp op, const JtjArgs<T>& a, hipStream_t s)
 {
     constexpr bool f64 = sizeof(T) == 8;
-    const bool rewrite = op == JtjOp::rewrite;
+    const bool rewrite = op == JtjOp::rewrite, diff = op == JtjOp::fd_diff || op == JtjOp::fd_diff_keep;
     switch (l.kernel) {
     case JtjKernel::stream:
         return dispatch_ncb<1, 8>(l.ncb, [&](auto NCB) {
@@ -75,7 +70,12 @@ hipError_t launch_kernel(const JtjLaunch& l, JtjOp op, const JtjArgs<T>& a, hipS
     case JtjKernel::fdp:
         if constexpr (f64) return dispatch_ncb<1, 8>(l.ncb, [&](auto NCB) {
             return op == JtjOp::fd ? fdp_one<NCB, true, false>(l, a, s)
-                 : (op == JtjOp::fd_diff ? fdp_one<NCB, false, true>(l, a, s) : fdp_one<NCB, false, false>(l, a, s));
+                 : (diff ? fdp_one<NCB, false, true>(l, a, s) : fdp_one<NCB, false, false>(l, a, s));
+        });
+        break;
+    case JtjKernel::fdp_nw:                                // fdp's store-free instance (fd_diff_keep): the plan entry is fdp's
+        if constexpr (f64) return dispatch_ncb<1, 8>(l.ncb, [&](auto NCB) {
+            return launch_one<k_jtj_fdp_nw<NCB>>(l, JtjFdpCfg<NCB, false>::THREADS, s, a);
         });
         break;
     case JtjKernel::pc32:
@@ -92,7 +92,7 @@ hipError_t launch_kernel(const JtjLaunch& l, JtjOp op, const JtjArgs<T>& a, hipS
         break;
     case JtjKernel::fdp8:                                  // compiled for n rounded up to a multiple of 32; DIFF: of 64
         if constexpr (f64) {
-            if (op == JtjOp::fd_diff) return dispatch_ncb<12, 16, 4>(l.ncb, [&](auto NCB) { return fdp8_one<NCB, true, false>(l, a, s); });
+            if (diff) return dispatch_ncb<12, 16, 4>(l.ncb, [&](auto NCB) { return fdp8_one<NCB, true, false>(l, a, s); });
             return dispatch_ncb<10, 16, 2>(l.ncb, [&](auto NCB) {
                 return op == JtjOp::plain ? fdp8_one<NCB, false, true>(l, a, s) : fdp8_one<NCB, false, false>(l, a, s);
             });
@@ -123,6 +123,8 @@ hipError_t launch_kernel(const JtjLaunch& l, JtjOp op, const JtjArgs<T>& a, hipS
 template <typename T>
 hipError_t jtj_run(const JtjPlan& p, JtjOp op, const JtjArgs<T>& a, T* packed, hipStream_t s, const JtjUnpack<T>& u)
 {
+    // the difference panel: fd_diff writes J, fd_diff_keep does not -- the operation says it, not the pointer
+    if ((op == JtjOp::fd_diff || op == JtjOp::fd_diff_keep) && (op == JtjOp::fd_diff_keep) != (a.Jout == nullptr)) return hipErrorInvalidValue;
     const JtjLaunch l = jtj_resolve(p, op, reinterpret_cast<uintptr_t>(a.J) % 16 == 0);
     const hipError_t e = launch_kernel<T>(l, op, a, s);
     if (e != hipSuccess) return e;

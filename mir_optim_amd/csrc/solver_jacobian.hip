@@ -63,18 +63,19 @@ bool Solver<T>::plain_products(const T* y_vec)
     JtjArgs<T> a{};
     a.J = B.J; a.Jout = B.J; a.y = y_vec; a.y_old = y_vec; a.dx = B.dx_acc; a.dx_dot = &B.st->dx_dot;
     a.slabs = B.slabs; a.m = m; a.n = (int)n;
-    const bool direct = unpack_in_reduce(JtjOp::plain);
-    ev_begin(0);
-    if (!ok(jtj_run<T>(plan, JtjOp::plain, a, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "jtj kernel")) return false;
-    ev_end();
-    return finish_products(direct);
+    return run_products(JtjOp::plain, a, 0, "jtj kernel");
 }
 
-// Single GPU: the slab reduction writes J^T J (both triangles) and J^T y itself (the solve kernel takes |J^T y|_inf); with a
-// communicator the packed buffer is all-reduced first and k_unpack_grad expands it
+// One J^T J operation as event kind `kind`, then its result in JJ, Jy. Single GPU: the slab reduction writes J^T J (both
+// triangles) and J^T y itself (the solve kernel takes |J^T y|_inf); with a communicator the packed buffer is all-reduced first and
+// k_unpack_grad expands it
 template <typename T>
-bool Solver<T>::finish_products(bool direct)
+bool Solver<T>::run_products(JtjOp op, const JtjArgs<T>& a, int kind, const char* what)
 {
+    const bool direct = unpack_in_reduce(op);
+    ev_begin(kind);
+    if (!ok(jtj_run<T>(plan, op, a, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), what)) return false;
+    ev_end();
     if (direct) return ok(hipGetLastError(), "jtj reduce");
     if (comm && !allreduce(B.packed, (size_t)n * (n + 1) / 2 + n, 0)) return false;
     return ok(jtj_unpack<T>(B.packed, (int)n, B.JJ, B.Jy, B.st, stream), "unpack");
@@ -88,30 +89,19 @@ bool Solver<T>::jacobian_products(bool broyden, const T* y_dev, const T* yold_de
     JtjArgs<T> a{};
     a.J = B.J; a.Jout = B.J; a.y = y_dev; a.y_old = yold_dev; a.dx = B.dx_acc; a.dx_dot = &B.st->dx_dot;
     a.slabs = B.slabs; a.m = m; a.n = (int)n;
-    if (!broyden && fd_fused) {
-        // the row-major FD panel is still in ws->ypanel: one kernel forms the Jacobian rows (LS:1041-1047), writes
-        // them to J and accumulates J^T J / J^T y from the same registers
-        const JtjOp op = fd_fused == 2 ? JtjOp::fd_diff : JtjOp::fd;
-        fd_fused = 0;
-        a.J = static_cast<const T*>(ws->ypanel); a.twh = B.twh;
-        // ... unless this is the difference panel and only read-only sweeps will want J0: the 1 GB write of J = D (1 / twh) is
-        // left out, the panel stays where it is until the next refresh replaces it and the sweeps scale what they load
-        if (op == JtjOp::fd_diff && lowrank && n <= (uint32_t)kLrScaledMaxN && !(variant & MIR_LSQ_VARIANT_FD_WRITE_J)) {
-            j0_in_panel = true;
-            a.Jout = nullptr;
-        }
-        const bool direct = unpack_in_reduce(op);
-        ev_begin(3);
-        if (!ok(jtj_run<T>(plan, op, a, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "fd + jtj kernel")) return false;
-        ev_end();
-        return finish_products(direct);
+    if (broyden || !fd_fused) return run_products(broyden ? JtjOp::rewrite : JtjOp::plain, a, broyden ? 1 : 0, "jtj kernel");
+    // the row-major FD panel is still in ws->ypanel: one kernel forms the Jacobian rows (LS:1041-1047), writes
+    // them to J and accumulates J^T J / J^T y from the same registers
+    JtjOp op = fd_fused == 2 ? JtjOp::fd_diff : JtjOp::fd;
+    fd_fused = 0;
+    a.J = static_cast<const T*>(ws->ypanel); a.twh = B.twh;
+    // ... unless this is the difference panel and only read-only sweeps will want J0: the 1 GB write of J = D (1 / twh) is
+    // left out, the panel stays where it is until the next refresh replaces it and the sweeps scale what they load
+    if (op == JtjOp::fd_diff && lowrank && n <= (uint32_t)kLrScaledMaxN && !(variant & MIR_LSQ_VARIANT_FD_WRITE_J)) {
+        j0_in_panel = true;
+        op = JtjOp::fd_diff_keep; a.Jout = nullptr;
     }
-    const JtjOp op = broyden ? JtjOp::rewrite : JtjOp::plain;
-    const bool direct = unpack_in_reduce(op);
-    ev_begin(broyden ? 1 : 0);
-    if (!ok(jtj_run<T>(plan, op, a, B.packed, stream, direct ? unpack_target() : JtjUnpack<T>{}), "jtj kernel")) return false;
-    ev_end();
-    return finish_products(direct);
+    return run_products(op, a, 3, "fd + jtj kernel");
 }
 
 // ---- finite-difference Jacobian, device callbacks (LS:1016-1050 restructured: all perturbed
@@ -447,7 +437,7 @@ bool Solver<T>::analytic_jacobian()
 #define MIRLSQ_INSTANTIATE(T)                                                                       \
     template bool Solver<T>::broyden_lowrank(const T*, const T*);                                   \
     template bool Solver<T>::plain_products(const T*);                                              \
-    template bool Solver<T>::finish_products(bool);                                                 \
+    template bool Solver<T>::run_products(JtjOp, const JtjArgs<T>&, int, const char*);              \
     template bool Solver<T>::jacobian_products(bool, const T*, const T*);                           \
     template void Solver<T>::fd_widths_host();                                                      \
     template bool Solver<T>::fd_panel(size_t&, bool&);                                              \

@@ -500,73 +500,56 @@ int unpack_grad_entry(size_t n_, const T* packed, void* state, T* JJ, T* Jy, int
     return 0;
 }
 
+// The body of mir_lsq_jtj_* / mir_lsq_fd_jtj_d / mir_lsq_fd_diff_jtj_d: ONE jtj_run of `op` on the caller's operands in `a` (the call
+// adds the slabs and, for the rewrite, ||dx||^2) and jtj_unpack; kernel_ms brackets jtj_run alone.
 template <typename T>
-int jtj_entry(size_t m, size_t n, T* J, const T* y, const T* y_old, const T* dx, int broyden, T* JJ, T* Jy,
-              void* stream_, float* kernel_ms)
+int jtj_entry(JtjOp op, JtjArgs<T> a, T* JJ, T* Jy, void* stream_, float* kernel_ms)
 {
     if (!device_available()) return -1;
-    if (n == 0 || m == 0) return -2;
+    if (a.n == 0 || a.m == 0) return -2;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const JtjPlan plan = jtj_plan<T>(m, (int)n, query_num_cu());
-    const size_t packed_len = n * (n + 1) / 2 + n + 8;
-    T *slabs = nullptr, *packed = nullptr, *dxdot = nullptr;
+    const JtjPlan plan = jtj_plan<T>(a.m, a.n, query_num_cu());
+    if (plan.of(op).kernel == JtjKernel::none) return -6;   // shape not covered by a fused kernel
+    const size_t n = (size_t)a.n, packed_len = n * (n + 1) / 2 + n + 8;
+    T* packed = nullptr;
     LmState<T>* st = nullptr;
-    const size_t slab_count = jtj_slab_elems(plan);
-    if (hipMalloc((void**)&slabs, sizeof(T) * slab_count) != hipSuccess) return -3;
-    if (hipMalloc((void**)&packed, sizeof(T) * packed_len) != hipSuccess) { (void)hipFree(slabs); return -3; }
-    if (hipMalloc((void**)&st, sizeof(LmState<T>) + sizeof(T) * 8) != hipSuccess) { (void)hipFree(slabs); (void)hipFree(packed); return -3; }
-    dxdot = reinterpret_cast<T*>(st + 1);
+    if (hipMalloc((void**)&a.slabs, sizeof(T) * jtj_slab_elems(plan)) != hipSuccess) return -3;
+    if (hipMalloc((void**)&packed, sizeof(T) * packed_len) != hipSuccess) { (void)hipFree(a.slabs); return -3; }
+    if (hipMalloc((void**)&st, sizeof(LmState<T>) + sizeof(T) * 8) != hipSuccess) { (void)hipFree(a.slabs); (void)hipFree(packed); return -3; }
     int rc = 0;
-    if (broyden) {
+    if (op == JtjOp::rewrite) {
         // ||dx||^2 on the device (n-vector, one block)
-        hipLaunchKernelGGL(k_sumsq_partial<T>, dim3(1), dim3(256), 0, stream, dx, n, packed);
+        T* dxdot = reinterpret_cast<T*>(st + 1);
+        hipLaunchKernelGGL(k_sumsq_partial<T>, dim3(1), dim3(256), 0, stream, a.dx, n, packed);
         hipLaunchKernelGGL(k_sumsq_final<T>, dim3(1), dim3(256), 0, stream, packed, 1, dxdot);
+        a.dx_dot = dxdot;
     }
-    JtjArgs<T> a{};
-    a.J = J; a.Jout = J; a.y = y; a.y_old = y_old; a.dx = dx; a.dx_dot = dxdot; a.slabs = slabs; a.m = m; a.n = (int)n;
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, stream);
-    if (jtj_run<T>(plan, broyden ? JtjOp::rewrite : JtjOp::plain, a, packed, stream) != hipSuccess) rc = -4;
+    if (jtj_run<T>(plan, op, a, packed, stream) != hipSuccess) rc = -4;
     (void)hipEventRecord(e1, stream);
     (void)jtj_unpack<T>(packed, (int)n, JJ, Jy, st, stream);
     if (hipStreamSynchronize(stream) != hipSuccess) rc = -5;
     if (kernel_ms) { float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); *kernel_ms = ms; }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(slabs); (void)hipFree(packed); (void)hipFree(st);
+    (void)hipFree(a.slabs); (void)hipFree(packed); (void)hipFree(st);
     return rc;
 }
-int fd_jtj_entry(size_t m, size_t n, const double* Yrm, const double* twh, const double* y, double* J,
-                 double* JJ, double* Jy, void* stream_, float* kernel_ms, bool diff)
+template <typename T>
+int plain_jtj_entry(size_t m, size_t n, T* J, const T* y, const T* y_old, const T* dx, int broyden, T* JJ, T* Jy, void* stream, float* kernel_ms)
 {
-    if (!device_available()) return -1;
-    if (n == 0 || m == 0) return -2;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const JtjPlan plan = jtj_plan<double>(m, (int)n, query_num_cu());
-    const JtjOp op = diff ? JtjOp::fd_diff : JtjOp::fd;
-    if (plan.of(op).kernel == JtjKernel::none) return -6;   // shape not covered by a fused kernel
-    const size_t packed_len = n * (n + 1) / 2 + n + 8;
-    double *slabs = nullptr, *packed = nullptr;
-    LmState<double>* st = nullptr;
-    const size_t slab_count = jtj_slab_elems(plan);
-    if (hipMalloc((void**)&slabs, sizeof(double) * slab_count) != hipSuccess) return -3;
-    if (hipMalloc((void**)&packed, sizeof(double) * packed_len) != hipSuccess) { (void)hipFree(slabs); return -3; }
-    if (hipMalloc((void**)&st, sizeof(LmState<double>)) != hipSuccess) { (void)hipFree(slabs); (void)hipFree(packed); return -3; }
-    int rc = 0;
+    JtjArgs<T> a{};
+    a.J = J; a.Jout = J; a.y = y; a.y_old = y_old; a.dx = dx; a.m = m; a.n = (int)n;
+    return jtj_entry<T>(broyden ? JtjOp::rewrite : JtjOp::plain, a, JJ, Jy, stream, kernel_ms);
+}
+// op: fd (Yrm the pair panel), fd_diff (the difference panel) or, J == NULL, fd_diff_keep
+int fd_jtj_entry(JtjOp op, size_t m, size_t n, const double* Yrm, const double* twh, const double* y, double* J, double* JJ, double* Jy,
+                 void* stream, float* kernel_ms)
+{
     JtjArgs<double> a{};
-    a.J = Yrm; a.Jout = J; a.y = y; a.y_old = y; a.dx = nullptr; a.dx_dot = nullptr; a.slabs = slabs; a.m = m; a.n = (int)n;
-    a.twh = twh;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, stream);
-    if (jtj_run<double>(plan, op, a, packed, stream) != hipSuccess) rc = -4;
-    (void)hipEventRecord(e1, stream);
-    (void)jtj_unpack<double>(packed, (int)n, JJ, Jy, st, stream);
-    if (hipStreamSynchronize(stream) != hipSuccess) rc = -5;
-    if (kernel_ms) { float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); *kernel_ms = ms; }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(slabs); (void)hipFree(packed); (void)hipFree(st);
-    return rc;
+    a.J = Yrm; a.Jout = J; a.y = y; a.y_old = y; a.m = m; a.n = (int)n; a.twh = twh;
+    return jtj_entry<double>(op, a, JJ, Jy, stream, kernel_ms);
 }
 }  // namespace
 
@@ -586,21 +569,21 @@ int mir_solve_box_qp_gpu_s(const mir_box_qp_settings_s* settings, size_t n, cons
 int mir_lsq_jtj_d(size_t m, size_t n, double* J, const double* y, const double* y_old, const double* dx, int broyden,
                   double* JJ, double* Jy, void* stream, float* kernel_ms)
 {
-    return jtj_entry<double>(m, n, J, y, y_old, dx, broyden, JJ, Jy, stream, kernel_ms);
+    return plain_jtj_entry<double>(m, n, J, y, y_old, dx, broyden, JJ, Jy, stream, kernel_ms);
 }
 int mir_lsq_fd_jtj_d(size_t m, size_t n, const double* Yrm, const double* twh, const double* y, double* J,
                      double* JJ, double* Jy, void* stream_, float* kernel_ms)
 {
-    return fd_jtj_entry(m, n, Yrm, twh, y, J, JJ, Jy, stream_, kernel_ms, false);
+    return fd_jtj_entry(JtjOp::fd, m, n, Yrm, twh, y, J, JJ, Jy, stream_, kernel_ms);
 }
 int mir_lsq_fd_diff_jtj_d(size_t m, size_t n, const double* Drm, const double* twh, const double* y, double* J,
                           double* JJ, double* Jy, void* stream_, float* kernel_ms)
 {
-    return fd_jtj_entry(m, n, Drm, twh, y, J, JJ, Jy, stream_, kernel_ms, true);
+    return fd_jtj_entry(J ? JtjOp::fd_diff : JtjOp::fd_diff_keep, m, n, Drm, twh, y, J, JJ, Jy, stream_, kernel_ms);
 }
 int mir_lsq_jtj_plan(size_t elem_size, size_t m, size_t n, int num_cu, int op, int aligned16, size_t out[10])
 {
-    if ((elem_size != 4 && elem_size != 8) || m == 0 || n == 0 || n > (size_t)1 << 20 || num_cu < 1 || op < 0 || op > 3 || !out) return -1;
+    if ((elem_size != 4 && elem_size != 8) || m == 0 || n == 0 || n > (size_t)1 << 20 || num_cu < 1 || op < 0 || op > 4 || !out) return -1;
     const JtjPlan p = elem_size == 8 ? jtj_plan<double>(m, (int)n, num_cu) : jtj_plan<float>(m, (int)n, num_cu);
     const JtjLaunch l = jtj_resolve(p, (JtjOp)op, aligned16 != 0);
     const bool wide = l.kernel == JtjKernel::wide;
@@ -741,7 +724,7 @@ int mir_lsq_unpack_grad_s(size_t n, const float* packed, mir_lsq_lm_state_s* sta
 int mir_lsq_jtj_s(size_t m, size_t n, float* J, const float* y, const float* y_old, const float* dx, int broyden,
                   float* JJ, float* Jy, void* stream, float* kernel_ms)
 {
-    return jtj_entry<float>(m, n, J, y, y_old, dx, broyden, JJ, Jy, stream, kernel_ms);
+    return plain_jtj_entry<float>(m, n, J, y, y_old, dx, broyden, JJ, Jy, stream, kernel_ms);
 }
 int mir_lsq_selftest_reductions(int rounds, int mismatches[4])
 {

@@ -1,6 +1,6 @@
 // jtj_store_free_ab.hip -- the fused FD kernel alone, for an A/B of two trees (profiles/r26): HIP events, ROUNDS rounds of REPS
 // launches each, cases interleaved, ms per launch (median, min .. max over the rounds), the method of lr_scaled_ab.hip:
-//   the difference panel with Jout = nullptr (k_jtj_fdp_nw at n % 16 == 0, n <= 128; k_jtj_fdp8 above) and with Jout = J,
+//   the difference panel with Jout = nullptr (JtjOp::fd_diff_keep: k_jtj_fdp_nw at n % 16 == 0, n <= 128; k_jtj_fdp8 above) and with Jout = J,
 //   and the plain J^T J of the J that the second case wrote.
 // Every figure includes the slab reduction that jtj_run launches behind the kernel (a few microseconds, the same in both trees).
 // Build it in EACH tree against that tree's library (from the tree's root, after the library) and run the two alternately:
@@ -64,7 +64,7 @@ int main(int argc, char** argv)
         if (c == PLAIN) return jtj_run<double>(plan, JtjOp::plain, pa, packed, nullptr);
         JtjArgs<double> a = fa;
         if (c == FD_NULL) a.Jout = nullptr;
-        return jtj_run<double>(plan, JtjOp::fd_diff, a, packed, nullptr);
+        return jtj_run<double>(plan, c == FD_NULL ? JtjOp::fd_diff_keep : JtjOp::fd_diff, a, packed, nullptr);
     };
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0));

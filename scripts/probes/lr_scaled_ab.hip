@@ -1,6 +1,6 @@
 // lr_scaled_ab.hip -- what does it cost to keep J0 as the unscaled difference panel? HIP events on the kernels alone, cases
 // interleaved, ROUNDS rounds of REPS launches each, ms per launch (median, min .. max over the rounds):
-//   the fused FD kernel of the difference panel (jtj_run, JtjOp::fd_diff) with Jout = J and with Jout = nullptr;
+//   the fused FD kernel of the difference panel (jtj_run) with Jout = J (JtjOp::fd_diff) and with Jout = nullptr (fd_diff_keep);
 //   the read-only Broyden sweep (lr_sweep) over J and over the panel with twh (the scaled instance), at k = 1 and k = 4.
 // The break-even of a solve with 2 refreshes and 4 sweeps: the FD kernel's saving must exceed twice the sweep's loss.
 // Build (from the repository root, after the library) + run on the GPU box:
@@ -80,7 +80,7 @@ int main(int argc, char** argv)
         if (c == FD_WRITE || c == FD_NOWRITE) {
             JtjArgs<double> a = ja;
             if (c == FD_NOWRITE) a.Jout = nullptr;
-            return jtj_run<double>(plan, JtjOp::fd_diff, a, packed, nullptr);
+            return jtj_run<double>(plan, c == FD_NOWRITE ? JtjOp::fd_diff_keep : JtjOp::fd_diff, a, packed, nullptr);
         }
         LrArgs<double> a = la;
         a.k = (c == LR_PLAIN_1 || c == LR_SCALED_1) ? 1 : 4;

@@ -68,10 +68,11 @@ def run_jtj(J, y, y_old=None, dx=None, dtype=np.float64, j_offset_elems=0):
     return out["JJ"].reshape(n, n), out["Jy"], out["J"].reshape(m, n)
 
 
-def run_fd_jtj(panel, twh, y, diff, j_offset_elems=0, jout_offset_elems=0):
+def run_fd_jtj(panel, twh, y, diff, j_offset_elems=0, jout_offset_elems=0, keep=False):
     """mir_lsq_fd_jtj_d (panel: m x 2n pairs) / mir_lsq_fd_diff_jtj_d (diff: the m x n difference panel) on guarded buffers.
     The difference panel and Jout may be shifted independently; the pair panel is the library's own buffer in the solver and
-    jtj_resolve does not reroute it, so it stays aligned. -> (J, JJ, Jy)"""
+    jtj_resolve does not reroute it, so it stays aligned. keep (fd_diff_keep): the call is made with J = NULL and the J buffer,
+    which no kernel is given, must come back untouched. -> (J, JJ, Jy); keep: (the panel as it came back, JJ, Jy)"""
     panel = np.ascontiguousarray(panel, dtype=np.float64)
     m, n = panel.shape[0], panel.shape[1] if diff else panel.shape[1] // 2
     assert diff or j_offset_elems == 0
@@ -80,11 +81,13 @@ def run_fd_jtj(panel, twh, y, diff, j_offset_elems=0, jout_offset_elems=0):
     gJ = Guarded(np.float64, m * n, None, jout_offset_elems)
     gJJ, gJy = Guarded(np.float64, n * n), Guarded(np.float64, n)
     L = api.lib()
-    rc = (L.mir_lsq_fd_diff_jtj_d if diff else L.mir_lsq_fd_jtj_d)(m, n, gP.ptr, gt.ptr, gy.ptr, gJ.ptr, gJJ.ptr, gJy.ptr, None, None)
-    out = {k: g.finish(k, w) for k, g, w in (("panel", gP, False), ("twh", gt, False), ("y", gy, False), ("Jout", gJ, True),
+    assert diff or not keep
+    rc = (L.mir_lsq_fd_diff_jtj_d if diff else L.mir_lsq_fd_jtj_d)(m, n, gP.ptr, gt.ptr, gy.ptr, None if keep else gJ.ptr, gJJ.ptr, gJy.ptr,
+                                                                 None, None)
+    out = {k: g.finish(k, w) for k, g, w in (("panel", gP, False), ("twh", gt, False), ("y", gy, False), ("Jout", gJ, not keep),
                                              ("JJ", gJJ, True), ("Jy", gJy, True))}
     assert rc == 0, f"mir_lsq_fd_jtj: {rc}"
-    return out["Jout"].reshape(m, n), out["JJ"].reshape(n, n), out["Jy"]
+    return out["panel" if keep else "Jout"].reshape(m, n), out["JJ"].reshape(n, n), out["Jy"]
 
 
 # ---- references and bounds -----------------------------------------------------------------------------------------------
@@ -283,12 +286,14 @@ def _cells():
         c += [(8, "fd", M_EVEN, on, 0), (8, "fd", M_ODD, odd, 0)]                                        # fdp fd
         c += [(8, "fd_diff", M_EVEN, on, 0), (8, "fd_diff", M_ODD, on, 0)]                               # fdp fd_diff
         c += [(8, "fd_diff", M_ODD, odd, 0), (8, "fd_diff", M_EVEN, even, 0)]                            # ... flat (n % 16 != 0)
+        c += [(8, "fd_diff_keep", M_EVEN, on, 0), (8, "fd_diff_keep", M_ODD, on, 0)]                     # fdp_nw
+        c += [(8, "fd_diff_keep", M_ODD, odd, 0), (8, "fd_diff_keep", M_EVEN, even, 0)]                  # fdp flat with a null Jout
     for k in range(9, 17):               # ring8: n % 16 == 0 and even m
         c += [(8, "plain", M_EVEN, 16 * k, 0), (8, "rewrite", M_EVEN, 16 * k, 0)]
     for n in (160, 192, 224, 256):       # fdp8 at 10, 12, 14, 16 blocks: on the grid (plain: odd m) and off it (padding columns)
         c += [(8, "plain", M_ODD, n, 0), (8, "plain", M_ODD, n - 3, 0), (8, "plain", M_EVEN, n - 24, 0)]
         c += [(8, "fd", M_EVEN, n, 0), (8, "fd", M_ODD, n - 3, 0), (8, "fd", M_ODD, n - 24, 0)]
-    c += [(8, "fd_diff", m, n, 0) for n in (192, 256) for m in (M_ODD, M_EVEN)]
+    c += [(8, op, m, n, 0) for op in ("fd_diff", "fd_diff_keep") for n in (192, 256) for m in (M_ODD, M_EVEN)]
     # wide: every tile grid here has an off-diagonal job
     c += [(4, op, M_ODD, n, 0) for op in ("plain", "rewrite") for n in (129, 200, 256, 300)]
     c += [(8, "plain", M_ODD, 300, 0), (8, "plain", M_EVEN, 257, 0)]
@@ -298,13 +303,14 @@ def _cells():
         c += [(8, "rewrite", m, 77, 0), (4, "rewrite", m, 100, 0), (4, "plain", m, 90, 0), (4, "plain", m, 64, 0)]
         c += [(8, "plain", m, 64, 0), (8, "plain", m, 33, 0), (8, "fd", m, 48, 0), (8, "fd_diff", m, 64, 0), (8, "fd_diff", m, 33, 0)]
         c += [(8, "plain", m, 200, 0), (8, "fd", m, 200, 0), (8, "fd_diff", m, 192, 0)]
+        c += [(8, "fd_diff_keep", m, 64, 0), (8, "fd_diff_keep", m, 33, 0), (8, "fd_diff_keep", m, 192, 0)]
         c += [(4, "plain", m, 200, 0), (4, "rewrite", m, 200, 0), (4, "rewrite", m, 300, 0), (8, "plain", m, 300, 0),
               (8, "rewrite", m, 200, 0), (8, "rewrite", m, 300, 0)]
     c += [(8, op, m, 144, 0) for op in ("plain", "rewrite") for m in (2, 66)]
     # J one element off the 16-byte grid
     c += [(4, "plain", M_ODD, n, 1) for n in (64, 100, 128)]                  # pc32 -> stream
     c += [(8, "plain", M_EVEN, n, 1) for n in (16, 64, 126, 128)]             # fdp -> flat producer, even n
-    c += [(8, "fd_diff", M_EVEN, n, 1) for n in (64, 128)]                    # ... for the difference panel
+    c += [(8, op, M_EVEN, n, 1) for op in ("fd_diff", "fd_diff_keep") for n in (64, 128)]   # ... for the difference panel (fdp_nw too)
     c += [(8, "rewrite", M_ODD, 77, 1), (4, "rewrite", M_ODD, 100, 1), (8, "plain", M_ODD, 200, 1),
           (4, "plain", M_ODD, 300, 1), (8, "rewrite", M_ODD, 300, 1)]         # same kernel for both alignments
     assert len(set(c)) == len(c)
@@ -324,9 +330,13 @@ def cell_id(cell):
 # ---- what launch_jtj.hip instantiates, written out independently of jtj_plan<T>() ---------------------------------------
 # key: (elem_size, op, family, blocks, flat, pointer). blocks: the NCB template argument; wide is one instance per type, so its
 # classes are named instead ("any" / "n<=256" / "n>256": k_broyden_wide or k_broyden_rows in front). pointer: "any", or "offset" for
-# a launch that exists only for a J that is not 16-byte aligned (the two jtj_resolve outcomes).
+# a launch that exists only for a J that is not 16-byte aligned (the jtj_resolve outcomes).
 RING8_OFFSET = ("unverified_offset: k_jtj8 issues 16-byte global_load_lds from J, y and y_old, jtj_resolve keeps ring8 for an "
                 "unaligned J, and nothing in the code establishes that a 16-byte LDS-DMA from an 8-byte-aligned address is defined")
+
+
+FDP_KEEP_4GB = ("unverified_4gb: fd_diff_keep stays on k_jtj_fdp's strided producer (Jout == nullptr) only where a workgroup's rows span "
+                "at least 4 GB of panel; the plan's side of the rule is tests/test_jtj_plan.py's, the kernel is fd_diff's")
 
 
 def _instantiated():
@@ -334,8 +344,10 @@ def _instantiated():
     for k in range(1, 9):
         for es, op in ((4, "plain"), (4, "rewrite"), (8, "rewrite")):
             u[(es, op, "stream", k, False, "any")] = "run"
-        for op, flat in (("fd", False), ("fd_diff", False), ("fd_diff", True), ("plain", False), ("plain", True)):
+        for op, flat in (("fd", False), ("fd_diff", False), ("fd_diff", True), ("plain", False), ("plain", True), ("fd_diff_keep", True)):
             u[(8, op, "fdp", k, flat, "any")] = "run"
+        u[(8, "fd_diff_keep", "fdp_nw", k, False, "any")] = "run"
+        u[(8, "fd_diff_keep", "fdp", k, False, "any")] = FDP_KEEP_4GB
         u[(4, "plain", "pc32", k, False, "any")] = "run"
     for k in range(9, 17):
         for op in ("plain", "rewrite"):
@@ -344,7 +356,7 @@ def _instantiated():
     for k in (10, 12, 14, 16):
         u[(8, "plain", "fdp8", k, False, "any")] = u[(8, "fd", "fdp8", k, False, "any")] = "run"
     for k in (12, 16):
-        u[(8, "fd_diff", "fdp8", k, False, "any")] = "run"
+        u[(8, "fd_diff", "fdp8", k, False, "any")] = u[(8, "fd_diff_keep", "fdp8", k, False, "any")] = "run"
     for es in (4, 8):
         for op, cls in (("plain", "any"), ("rewrite", "n<=256"), ("rewrite", "n>256")):
             u[(es, op, "wide", cls, False, "any")] = "run"
@@ -354,7 +366,7 @@ def _instantiated():
     for k in (1, 4, 8):
         u[(8, "plain", "fdp", k, True, "offset")] = "run"
     for k in (4, 8):
-        u[(8, "fd_diff", "fdp", k, True, "offset")] = "run"
+        u[(8, "fd_diff", "fdp", k, True, "offset")] = u[(8, "fd_diff_keep", "fdp", k, True, "offset")] = "run"
     return u
 
 

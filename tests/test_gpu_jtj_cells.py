@@ -64,19 +64,25 @@ def run_plain_or_rewrite(cell, off):
 
 
 def run_fd(cell, off, jout_off=0):
+    """fd, fd_diff: J, JJ, Jy. fd_diff_keep: the call with J = NULL -- JJ and Jy held to the same references and bounds, and to the
+    BITS of the fd_diff call on the same data (same grid, slabs and MFMA order); the panel comes back unchanged."""
     es, op, m, n, _ = cell
-    diff, tag = op == "fd_diff", K.cell_id(cell)
+    diff, keep, tag = op != "fd", op == "fd_diff_keep", K.cell_id(cell)
     c = K.fd_case(m, n, diff, True)
-    J, JJ, Jy = K.run_fd_jtj(c["panel"], c["twh"], c["y"], diff, off, jout_off)
-    assert K.same_bits(J, c["J"]) and K.same_bits(JJ, c["JJ"]) and K.same_bits(Jy, c["Jy"])
+    J, JJ, Jy = K.run_fd_jtj(c["panel"], c["twh"], c["y"], diff, off, jout_off, keep)
+    assert K.same_bits(J, c["panel"] if keep else c["J"]) and K.same_bits(JJ, c["JJ"]) and K.same_bits(Jy, c["Jy"])
     assert K.same_bits(JJ, np.ascontiguousarray(JJ.T))
     exact = (J, JJ, Jy)
     r = K.fd_case(m, n, diff, False)
-    J, JJ, Jy = K.run_fd_jtj(r["panel"], r["twh"], r["y"], diff, off, jout_off)
-    assert K.same_bits(J, r["J"])                           # the Jacobian of ref_fill, bit for bit
-    check_products(tag, JJ, Jy, J, r["y"], np.float64)
-    again = K.run_fd_jtj(r["panel"], r["twh"], r["y"], diff, off, jout_off)
+    J, JJ, Jy = K.run_fd_jtj(r["panel"], r["twh"], r["y"], diff, off, jout_off, keep)
+    assert K.same_bits(J, r["panel"] if keep else r["J"])   # the Jacobian of ref_fill, bit for bit (keep: the panel, untouched)
+    check_products(tag, JJ, Jy, r["J"], r["y"], np.float64)
+    again = K.run_fd_jtj(r["panel"], r["twh"], r["y"], diff, off, jout_off, keep)
     assert all(K.same_bits(a, b) for a, b in zip((J, JJ, Jy), again))
+    if keep:
+        for data, got in ((c, exact), (r, (J, JJ, Jy))):
+            Jw, JJw, Jyw = K.run_fd_jtj(data["panel"], data["twh"], data["y"], True, off, jout_off)
+            assert K.same_bits(Jw, data["J"]) and K.same_bits(got[1], JJw) and K.same_bits(got[2], Jyw), tag
     return exact, (J, JJ, Jy)
 
 
@@ -99,7 +105,7 @@ def same_after_roundtrip(g, payload):
 
 
 def run_cell(cell, off, jout_off=0):
-    return run_fd(cell, off, jout_off) if cell[1] in ("fd", "fd_diff") else run_plain_or_rewrite(cell, off)
+    return run_fd(cell, off, jout_off) if cell[1] in ("fd", "fd_diff", "fd_diff_keep") else run_plain_or_rewrite(cell, off)
 
 
 @pytest.mark.parametrize("cell", [c for c in K.CELLS if c[4] == 0], ids=K.cell_id)

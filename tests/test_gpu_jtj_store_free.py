@@ -3,7 +3,8 @@ store-free consumers, the lean producer) against the WRITING instance of the sam
 with a J buffer on the same panel. Every comparison is BITWISE.
 
   * n = 16, 48, 128 run k_jtj_fdp_nw; n = 100 (padding columns, a row of J off the 128-byte grid), an odd n and an offset view
-    run the flat producer, which is the parent's code: they must still agree with their J-buffer runs.
+    run the flat producer of k_jtj_fdp: they must still agree with their J-buffer runs. Which kernel a shape runs is asked of the
+    library's plan (operation fd_diff_keep: what the J = NULL call names), not inferred from n.
   * Every shape runs twice: with live columns only (the lean producer's steady state: multiplies and LDS writes alone) and with
     one collapsed column whose panel entries are NaN and Inf (every wave then takes the selects; the column contributes exactly 0).
   * m: around one and two 32-row stages; the smallest even m at which the plan's grid leaves workgroups without a stage; and
@@ -41,9 +42,18 @@ def num_cu():
     return n
 
 
+def keep_plan(m, n, aligned=True):
+    """what the J = NULL call launches, from the library's plan; the J-buffer call it is compared with runs fd_diff's entry, fdp on
+    the same grid, LDS and slabs"""
+    p, w = (api.jtj_plan(8, m, n, num_cu(), op, aligned) for op in ("fd_diff_keep", "fd_diff"))
+    assert w["family"] == "fdp" and {k: v for k, v in p.items() if k != "family"} == {k: v for k, v in w.items() if k != "family"}, (m, n, p, w)
+    return p
+
+
 def grid(m, n):
-    p = api.jtj_plan(8, m, n, num_cu(), "fd_diff", True)
-    assert p["family"] == "fdp"
+    p = keep_plan(m, n)
+    # the store-free kernel at n % 16 == 0, else the flat producer of k_jtj_fdp
+    assert (p["family"], p["flat"]) == (("fdp_nw", 0) if n % 16 == 0 else ("fdp", 1)), (m, n, p)
     return p["grid"]
 
 
@@ -138,11 +148,13 @@ def test_null_j_has_the_bits_of_the_writing_instance(n, collapsed):
 
 
 def test_the_cases_reach_what_they_are_for():
-    """the shapes above on this device's plan: n % 16 == 0 is off the flat producer (the store-free kernel), n = 100 is on it; the
-    idle-workgroup shape leaves a workgroup without a stage; the whole-workgroup shape has as many full stages in every workgroup"""
+    """the shapes above on this device's plan: n = 16, 48, 128 run the store-free kernel at every m of the test, n = 100 the flat
+    producer; the idle-workgroup shape leaves a workgroup without a stage; the whole-workgroup shape has as many full stages in
+    every workgroup"""
     for n in NS:
-        p = api.jtj_plan(8, 1024, n, num_cu(), "fd_diff", True)
-        assert p["family"] == "fdp" and bool(p["flat"]) == (n % 16 != 0), (n, p)
+        for m in ms_of(n):
+            p = keep_plan(m, n)
+            assert (p["family"], p["flat"]) == (("fdp", 1) if n == 100 else ("fdp_nw", 0)), (m, n, p)
         m = m_with_idle_workgroups(n)
         assert m % 2 == 0 and grid(m, n) > 1 and stages_of_last_workgroup(m, n) == 0, (n, m)
         m = m_of_whole_workgroups(n)
@@ -152,7 +164,8 @@ def test_the_cases_reach_what_they_are_for():
 @pytest.mark.parametrize("n,off", [(33, 0), (127, 0), (64, 1), (128, 1)])
 def test_flat_producer_paths_keep_agreeing(n, off):
     """odd n and an offset view: the flat producer (the parent's code) with J = NULL against its J-buffer run"""
-    assert api.jtj_plan(8, 1031, n, num_cu(), "fd_diff", off == 0)["flat"] == 1
     for m in (1, 65, 1031):
+        p = keep_plan(m, n, off == 0)
+        assert (p["family"], p["flat"]) == ("fdp", 1), (m, n, off, p)
         for collapsed in (False, True):
             check_shape(m, n, collapsed, off)
