@@ -1,10 +1,10 @@
 // covariance.hip -- Solver<T>::covariance(): the covariance of the fitted parameters, cov = s^2 inv(J^T J), at a given x.
 //
 // The J a solve ends with is usually a Broyden-aged approximation, sometimes with pending rank-one terms, so the step makes
-// ONE full refresh at x exactly as a refresh of the solve makes it (solver_jacobian.hip: the analytic g, fd_device() or
-// fd_host() with the same callbacks, fd_batch and clipping of x +- jacobianEpsilon to the bounds, LS:1018-1049), forms J^T J
-// with jacobian_products(false, ...) (the plan's kernel, the all-reduce of the packed buffer over the row shards), inverts it
-// on the device (spd_inverse.h) and scales by s^2 = ||f(x)||^2 / (M - n_free). Nothing of the LM loop runs.
+// ONE full refresh at x with the function a refresh of the solve calls (full_refresh(), solver_jacobian.hip: the analytic g,
+// fd_device() or fd_host() with the same callbacks, fd_batch and clipping of x +- jacobianEpsilon to the bounds, LS:1018-1049,
+// then J^T J with jacobian_products(false, ...): the plan's kernel, the all-reduce of the packed buffer over the row shards),
+// inverts it on the device (spd_inverse.h) and scales by s^2 = ||f(x)||^2 / (M - n_free). Nothing of the LM loop runs.
 //
 // A parameter with l_j == u_j is FIXED: the refresh has made its column zero (LS:1045), the mask takes its row and column out
 // of the system, and they are 0 in the result. A parameter that merely sits on a bound with l_j < u_j is NOT fixed: its
@@ -17,69 +17,54 @@
 
 namespace mirlsq {
 
+// the device side of covariance(): f(x) and its sum of squares, the refresh, the inverse, the scaling, the read-back
 template <typename T>
-int Solver<T>::covariance(uint32_t flags, T* cov, T* residual_out, int* info_out)
+bool Solver<T>::covariance_steps(uint32_t flags, const unsigned char* fixed_h, uint32_t n_free, T* cov, T* residual_h, int* info_h)
 {
-    const auto t_start = std::chrono::steady_clock::now();
-    launches_mark = launches_now();
-    // validation of run(), LS:930-943 -- needs no device
-    {
-        bool finite = true;
-        for (uint32_t i = 0; i < n; ++i) if (!(-Lim<T>::inf() < xh[i] && xh[i] < Lim<T>::inf())) finite = false;
-        if (m == 0 || n == 0 || !finite) return mir_ls_badGuess;
-        for (uint32_t i = 0; i < n; ++i) if (!(lh[i] <= xh[i]) || !(xh[i] <= uh[i])) return mir_ls_badBounds;
-        if (const int bad = bad_settings(S)) return bad;
-    }
-    ret.status = mir_ls_numericError; ret.iterations = 0; ret.fCalls = 0; ret.gCalls = 0;
-    if (!device_available()) return mir_ls_numericError;
-    if (!setup()) { teardown(); return mir_ls_numericError; }
-
-    // the columns the refresh makes zero: l_j == u_j
-    std::vector<unsigned char> fixed_h(n);
-    uint32_t n_free = 0;
-    for (uint32_t j = 0; j < n; ++j) { fixed_h[j] = lh[j] == uh[j] ? 1 : 0; n_free += fixed_h[j] ? 0u : 1u; }
     // carve() of workspace.hip gives a ladder entry Pm and A of n x n, vec of 12 n elements and ivec of 2 n int32: the factor, the
     // result, the n scale factors, and -- in ivec -- the mask (n bytes at byte 0) and info (one int at int index n, byte 4 n >= n)
     static_assert(sizeof(int32_t) == 4 && sizeof(int) == 4, "mask and info share the 2 n int32 of SolveScratch::ivec");
     const SolveScratch<T>& sc = B.sc[kChainMax - 1];
     unsigned char* fixed_d = reinterpret_cast<unsigned char*>(sc.ivec);          // n bytes of the 2 n int32
     int* info_d = reinterpret_cast<int*>(sc.ivec) + n;
-    T* X = sc.A;
+    if (!eval_f(B.x, xh, y) || !sumsq(y, 0)) return false;               // LS:953, 955 -> B.sum[0], all-reduced
+    round_kind = 0;
+    if (!full_refresh()) return false;                                   // LS:1008-1052, 1065 -> B.JJ
+    if (!ok(hipMemcpyAsync(fixed_d, fixed_h, n, hipMemcpyHostToDevice, stream), "H2D fixed mask")
+        || !ok(spd_inverse<T>((int)n, B.JJ, fixed_d, sc.Pm, sc.vec, sc.A, info_d, stream), "covariance: inverse")) return false;
+    const bool absolute = (flags & MIR_LSQ_COVARIANCE_ABSOLUTE_SIGMA) != 0;
+    // M = the rows of all ranks, through the communicator's all-reduce
+    if (comm && !absolute && (!ok(cov_rows<T>(B.sum, m, stream), "covariance: rows") || !allreduce(B.sum + 1, 2, 2))) return false;
+    return ok(cov_scale<T>((int)n, sc.A, fixed_d, info_d, B.sum, comm != nullptr && !absolute, (double)m, (double)n_free, absolute, stream),
+              "covariance: scale")
+        && ok(hipMemcpyAsync(cov, sc.A, (size_t)n * n * sizeof(T), hipMemcpyDeviceToHost, stream), "D2H covariance")
+        && ok(hipMemcpyAsync(info_h, info_d, sizeof(int), hipMemcpyDeviceToHost, stream), "D2H info")
+        && ok(hipMemcpyAsync(residual_h, B.sum, sizeof(T), hipMemcpyDeviceToHost, stream), "D2H residual")
+        && ok(hipStreamSynchronize(stream), "sync");
+}
+
+template <typename T>
+int Solver<T>::covariance(uint32_t flags, T* cov, T* residual_out, int* info_out)
+{
+    const auto t_start = std::chrono::steady_clock::now();
+    launches_mark = launches_now();
+    if (const int bad = invalid_input()) return bad;                     // the validation of run(), LS:930-943
+    ret.status = mir_ls_numericError; ret.iterations = 0; ret.fCalls = 0; ret.gCalls = 0;
+    if (!device_available()) return mir_ls_numericError;
+    // the columns the refresh makes zero: l_j == u_j
+    std::vector<unsigned char> fixed_h(n);
+    uint32_t n_free = 0;
+    for (uint32_t j = 0; j < n; ++j) { fixed_h[j] = lh[j] == uh[j] ? 1 : 0; n_free += fixed_h[j] ? 0u : 1u; }
     int info_h = 0;
     T residual_h = 0;
-
-    bool fail = false;
-    do {   // single-exit block for device errors
-        if (!eval_f(B.x, xh, y)) { fail = true; break; }                 // LS:953
-        if (!sumsq(y, 0)) { fail = true; break; }                        // LS:955 -> B.sum[0], all-reduced
-        round_kind = 0;
-        if (stats) stats->jacobian_full++;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool okj;
-        if (g) okj = analytic_jacobian();                                // LS:1011-1015
-        else okj = device_cb ? fd_device() : fd_host();                  // LS:1016-1050
-        if (!okj) { fail = true; break; }
-        if (stats && !device_cb)
-            stats->fd_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (!jacobian_products(false, y, mB)) { fail = true; break; }    // LS:1052, 1065 -> B.JJ
-        if (!ok(hipMemcpyAsync(fixed_d, fixed_h.data(), n, hipMemcpyHostToDevice, stream), "H2D fixed mask")) { fail = true; break; }
-        if (!ok(spd_inverse<T>((int)n, B.JJ, fixed_d, sc.Pm, sc.vec, X, info_d, stream), "covariance: inverse")) { fail = true; break; }
-        const bool absolute = (flags & MIR_LSQ_COVARIANCE_ABSOLUTE_SIGMA) != 0;
-        if (comm && !absolute) {
-            // M = the rows of all ranks, through the communicator's all-reduce
-            if (!ok(cov_rows<T>(B.sum, m, stream), "covariance: rows") || !allreduce(B.sum + 1, 2, 2)) { fail = true; break; }
-        }
-        if (!ok(cov_scale<T>((int)n, X, fixed_d, info_d, B.sum, comm != nullptr && !absolute, (double)m, (double)n_free, absolute, stream),
-                "covariance: scale")) { fail = true; break; }
-        if (!ok(hipMemcpyAsync(cov, X, (size_t)n * n * sizeof(T), hipMemcpyDeviceToHost, stream), "D2H covariance")
-            || !ok(hipMemcpyAsync(&info_h, info_d, sizeof(int), hipMemcpyDeviceToHost, stream), "D2H info")
-            || !ok(hipMemcpyAsync(&residual_h, B.sum, sizeof(T), hipMemcpyDeviceToHost, stream), "D2H residual")
-            || !ok(hipStreamSynchronize(stream), "sync")) { fail = true; break; }
-    } while (false);
-    close_round();
-    if (stats) stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    bool good = setup();
+    if (good) {
+        good = covariance_steps(flags, fixed_h.data(), n_free, cov, &residual_h, &info_h);
+        close_round();
+        if (stats) stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
     teardown();
-    if (fail) return mir_ls_numericError;
+    if (!good) return mir_ls_numericError;
     if (info_out) *info_out = info_h;
     if (residual_out) *residual_out = residual_h;
     return 0;
@@ -108,6 +93,7 @@ int covariance_entry(const typename Abi<T>::Settings* settings, size_t m, size_t
 }
 
 #define MIRLSQ_INSTANTIATE(T)                                                                                              \
+    template bool Solver<T>::covariance_steps(uint32_t, const unsigned char*, uint32_t, T*, T*, int*);                     \
     template int Solver<T>::covariance(uint32_t, T*, T*, int*);                                                            \
     template int covariance_entry<T>(const Abi<T>::Settings*, size_t, size_t, const T*, const T*, const T*,                \
                                      const mir_lsq_gpu_options*, void*, Abi<T>::F, void*, Abi<T>::G, void*,                \

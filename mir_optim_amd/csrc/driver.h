@@ -237,7 +237,7 @@ struct Solver {
     T* fr = nullptr;     // third m-vector: the trial residual of a round goes here; accepting rotates (y, mB, fr) <- (fr, y, mB)
     // null steps (trial == x bit for bit; kFlagNullStep): once a round ended on one, the next round's solves are looked
     // at before the callbacks are launched, and when every entry is a null step nothing is evaluated
-    bool has_bounds = true;    // some lower / upper entry is finite (set in run()); MIR_LSQ_VARIANT_SOLVE_BOUNDED forces the full kernel
+    bool has_bounds = true;    // some lower / upper entry is finite (set in enter()); MIR_LSQ_VARIANT_SOLVE_BOUNDED forces the full kernel
     bool tail_null = false;
     // ---- the fused round (solver_loop.hip, setup() and enqueue_fused_tail()): behind a round's one trial residual the next
     // pass's Broyden sweep runs speculatively and carries the trial's sum of squares; one kernel then decides the trial and, if
@@ -260,6 +260,27 @@ struct Solver {
     std::vector<T> twh_h;
     std::vector<EventPair> events;
     Result ret;
+
+    // ---- the LM loop (solver_loop.hip): what run() carries from pass to pass, and what one pass works out for itself
+    struct Loop {
+        bool fConverged = false, needJacobian = true, last_rejected = false;   // LS:956, 959
+        bool spec_live = false;            // the Jacobian side and the solve of the round at the top of the loop have run already (fused round)
+        bool spec_predict = true;          // the last first trial after a Jacobian update was accepted
+        bool speculate = false;            // ladder trials: one fb call, or ks calls of f
+        T mu = 1;
+        uint32_t age = 0, maxAge = 0;      // LS:945
+    } lp;
+    struct Round {
+        T* ytr;                            // the trial residuals: the free buffer, or the ladder's ks vectors
+        int ks = 1;                        // ladder entries of the round, lam[0 .. ks)
+        T lam[kChainMax];
+        bool newJacobian = false, lambda_from_state = false, skip_eval = false;
+        bool solve_enqueued = false;       // the previous round's fused kernel has solved already
+        bool fuse = false;                 // this round's decision is the head of a fused kernel
+    };
+    // what a stage answers: on with this pass, on to the next pass, stop with ret.status, or a device error
+    enum class Flow { go, next, stop, error };
+    Flow stop(int status) { ret.status = status; return Flow::stop; }
 
     // host-callback finite differences (reference thread-manager contract, LS:1019-1048)
     struct Slot { T* p = nullptr; T* yp = nullptr; T* ym = nullptr; };
@@ -309,6 +330,14 @@ struct Solver {
     }
     void ev_begin(int kind);
     void ev_end();
+    // validation, LS:930-943 (quirk Q9), of the solve and of the covariance step -- needs no device: the status, or 0
+    int invalid_input() const
+    {
+        if (m == 0 || n == 0) return mir_ls_badGuess;
+        for (uint32_t i = 0; i < n; ++i) if (!(-Lim<T>::inf() < xh[i] && xh[i] < Lim<T>::inf())) return mir_ls_badGuess;
+        for (uint32_t i = 0; i < n; ++i) if (!(lh[i] <= xh[i]) || !(xh[i] <= uh[i])) return mir_ls_badBounds;
+        return bad_settings(S);
+    }
 
     // ---- solver_loop.hip
     bool setup();
@@ -320,15 +349,20 @@ struct Solver {
     void trace_emit(int event, uint32_t iterations, T lambda, T residual, T trial_residual, T dx_dot);
     bool trace_round(int ks, T residual_before, uint32_t iterations_before);
     bool wait_state(uint32_t expect);
-    bool read_state(const T* vec_dev);
     void print_solve_dbg(bool fused_round);
     LmSolveArgs<T> solve_args(int ks, const T* lam, bool check_grad, bool lambda_from_state);
-    bool enqueue_solve(int ks, const T* lam, bool check_grad, bool lambda_from_state);
     DecideArgs<T> decide_args(int ks, bool check_grad, bool lambda_from_state);
     bool enqueue_decide(int ks, bool check_grad, bool lambda_from_state, const T* sum_v = nullptr);
     bool enqueue_fused_tail(const T* ytr, bool check_grad, bool lambda_from_state);
     void commit_spec_round();
     void drop_spec_round();
+    bool enter();
+    Flow top_of_pass();
+    bool adopt_spec_round(Round& r), jacobian_side(Round& r);
+    void ladder(Round& r);
+    bool solve_round(Round& r), trial_residuals(Round& r), decide(Round& r);
+    Flow book(Round& r);
+    Flow pass();
     Result run();
     void apply_options(const mir_lsq_gpu_options* opt);
 
@@ -339,6 +373,7 @@ struct Solver {
     JtjUnpack<T> unpack_target() { JtjUnpack<T> u; u.JJ = B.JJ; u.Jy = B.Jy; return u; }
     bool run_products(JtjOp op, const JtjArgs<T>& a, int kind, const char* what);
     bool jacobian_products(bool broyden, const T* y_dev, const T* yold_dev);
+    bool full_refresh();
     bool fd_panel(size_t& pb, bool& use_diff);
     void fd_widths_host();
     bool fd_entry(bool& done);
@@ -351,6 +386,7 @@ struct Solver {
     bool analytic_jacobian();
 
     // ---- covariance.hip: cov = s^2 inv(J^T J) of ONE full refresh at x, nothing of the LM loop
+    bool covariance_steps(uint32_t flags, const unsigned char* fixed_h, uint32_t n_free, T* cov, T* residual_h, int* info_h);
     int covariance(uint32_t flags, T* cov, T* residual_out, int* info_out);
 };
 

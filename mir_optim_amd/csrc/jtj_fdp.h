@@ -226,7 +226,7 @@ __device__ __forceinline__ void fdp_producer_plain(const JtjArgs<double>& a, dou
 //   * Loads: 16-byte BUFFER loads over this workgroup's rows (the panel) and 8-byte ones over its y -- a scalar stage base
 //     plus a per-lane constant, no address registers, no clamp and no compare against m: what lies past row m - 1 is past the
 //     end of the buffer and reads as zero. Every stage issues the same loads, so the waits are counted across the back edge.
-//     (The offsets are 32-bit: the launcher takes this kernel only when a workgroup's rows span less than 4 GB.)
+//     (The offsets are 32-bit: jtj_plan<T>() plans this kernel only where a workgroup's rows span less than 4 GB, jtj_plan.h.)
 //   * Convert: a stage whose 32 rows all exist (every stage but the last of the matrix), in a wave that has neither a padding
 //     column nor a collapsed interval among its columns (decided once per launch), is the multiplies and the LDS writes
 //     alone -- v * inv is what `inv == 0 ? 0 : v * inv` selects when inv != 0, the same bits. Every other stage runs the

@@ -104,6 +104,22 @@ bool Solver<T>::jacobian_products(bool broyden, const T* y_dev, const T* yold_de
     return run_products(op, a, 3, "fd + jtj kernel");
 }
 
+// A full refresh at x with its products (LS:1008-1052, 1065), for a pass of the solve and for the covariance step alike:
+// the analytic g or finite differences through the caller's callbacks, then J^T J, J^T y -> B.JJ, B.Jy
+template <typename T>
+bool Solver<T>::full_refresh()
+{
+    if (stats) stats->jacobian_full++;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!(g ? analytic_jacobian()                                        // LS:1011-1015
+            : device_cb ? fd_device() : fd_host())) return false;        // LS:1016-1050
+    // fd_ms: host-callback mode is synchronous anyway (wall clock); in device-callback mode the refresh is only
+    // ENQUEUED here -- no stream synchronisation for the sake of a statistic: fd_callback_ms (events) covers it
+    if (stats && !device_cb)
+        stats->fd_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return jacobian_products(false, y, mB);
+}
+
 // ---- finite-difference Jacobian, device callbacks (LS:1016-1050 restructured: all perturbed
 //      points are generated at once, evaluated one by one or in batches, and written to J in
 //      coalesced column panels)
@@ -441,6 +457,7 @@ bool Solver<T>::analytic_jacobian()
     template bool Solver<T>::jacobian_products(bool, const T*, const T*);                           \
     template void Solver<T>::fd_widths_host();                                                      \
     template bool Solver<T>::fd_panel(size_t&, bool&);                                              \
+    template bool Solver<T>::full_refresh();                                                        \
     template bool Solver<T>::fd_entry(bool&);                                                       \
     template void Solver<T>::fd_entry_discard();                                                    \
     template bool Solver<T>::fd_device();                                                           \

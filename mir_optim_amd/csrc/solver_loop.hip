@@ -262,15 +262,6 @@ bool Solver<T>::wait_state(uint32_t expect)
     return true;
 }
 
-template <typename T>
-bool Solver<T>::read_state(const T* vec_dev)
-{
-    HpScope hp(this, 3);
-    if (!ok(hipMemcpyAsync(st_h, B.st, sizeof(LmState<T>), hipMemcpyDeviceToHost, stream), "D2H state")) return false;
-    if (vec_dev && !ok(hipMemcpyAsync(trial_h, vec_dev, n * sizeof(T), hipMemcpyDeviceToHost, stream), "D2H vec")) return false;
-    return ok(hipStreamSynchronize(stream), "sync");
-}
-
 // MIR_LSQ_VARIANT_DEBUG_SOLVE: the phase stamps of the solve kernel that has just been enqueued (synchronises the stream)
 template <typename T>
 void Solver<T>::print_solve_dbg(bool fused_round)
@@ -310,19 +301,6 @@ LmSolveArgs<T> Solver<T>::solve_args(int ks, const T* lam, bool check_grad, bool
     a.coop_epoch = a.coop_w > 1 ? ++ws->solve_epoch : 0;
     a.coop_absent = (variant & MIR_LSQ_VARIANT_DEBUG_HELPERS_ABSENT) ? 1 : 0;
     return a;
-}
-template <typename T>
-bool Solver<T>::enqueue_solve(int ks, const T* lam, bool check_grad, bool lambda_from_state)
-{
-    const LmSolveArgs<T> a = solve_args(ks, lam, check_grad, lambda_from_state);
-    ev_begin(2);
-    {
-        HpScope hp(this, 4);
-        // all bounds infinite: the variant without the BOXCQP active-set loop (solve_kernel.h, BOUNDED = false)
-        if (!ok(launch_lm_solve<T>(a, ks, has_bounds, big_solve, stream), "solve launch")) return false;
-    }
-    ev_end();
-    return true;
 }
 
 // the decision of a round (LS:1080-1161) for ks trials; publishes decision point ++seq
@@ -413,6 +391,258 @@ void Solver<T>::drop_spec_round()
     for (size_t i = spec_events_from; i < events.size(); ++i) if (events[i].kind >= 100) events[i].kind = -1;
 }
 
+// ---- the stages of run() in the order a pass takes them: bool where a stage can only fail on the device, Flow (driver.h) where it can stop
+
+// entry, LS:945-971: f(x0), its sum of squares, the state on the device and its first image in the mirror
+template <typename T>
+bool Solver<T>::enter()
+{
+    has_bounds = (variant & MIR_LSQ_VARIANT_SOLVE_BOUNDED) != 0;
+    for (uint32_t i = 0; i < n; ++i) if (lh[i] > -Lim<T>::inf() || uh[i] < Lim<T>::inf()) has_bounds = true;
+    bool entry_done = false;                                             // f(x0) came with the first refresh's panel (fd_entry)
+    if (!fd_entry(entry_done)) return false;
+    if (!entry_done && !eval_f(B.x, xh, y)) return false;                // LS:953
+    ++ret.fCalls;
+    ++seq;
+    if (!sumsq(y, 0)) return false;                                      // LS:955
+    MIRLSQ_LAUNCH(k_init_state<T>, dim3(1), dim3(1), 0, stream, B.sum, B.st, st_slot_d[seq & 1], seq);
+    if (!ok(hipGetLastError(), "init state") || !wait_state(seq)) return false;
+    ret.residual = st_h->residual;
+    lp.fConverged = LM_F_CONVERGED(ret.residual, sd);                    // LS:956
+    lp.speculate = device_cb && !no_speculation;
+    lp.maxAge = S->maxAge ? S->maxAge : (g ? 3 : 2 * n);                 // LS:945 (quirk Q4)
+    lp.age = lp.maxAge;
+    ret.lambda = 0;
+    ret.status = mir_ls_maxIterations;                                   // LS:971
+    return true;
+}
+
+// top of a pass, LS:972-995: the reference's tests before anything is computed
+template <typename T>
+typename Solver<T>::Flow Solver<T>::top_of_pass()
+{
+    close_round();
+    if (stats) stats->passes++;
+    if (lp.fConverged) return stop(mir_ls_fConverged);                   // LS:974-978
+    if (!LM_LAMBDA_IN_RANGE(ret.lambda, sd)) return stop(mir_ls_furtherImprovement);   // LS:979-983
+    if (lp.mu > kSuspiciousMu && lp.age) {                               // LS:984-989
+        lp.needJacobian = true;
+        lp.age = lp.maxAge;
+        lp.mu = 1;
+        MIRLSQ_LAUNCH(k_reset_mu<T>, dim3(1), dim3(1), 0, stream, B.st);
+    }
+    for (uint32_t i = 0; i < n; ++i) if (!(xh[i] <= xh[i])) return stop(mir_ls_numericError);   // LS:990-995
+    return Flow::go;
+}
+
+// the pass the previous round's fused kernel ran ahead: its Jacobian side and its solve have run already
+template <typename T>
+bool Solver<T>::adopt_spec_round(Round& r)
+{
+    if (!lp.spec_live) return true;
+    lp.spec_live = false;
+    if (!lp.needJacobian || !(lp.age < lp.maxAge) || lr_k >= lr_cap) {
+        std::fprintf(stderr, "[mir_optim_amd] internal error: the pass run ahead by the fused round is not the next pass\n");
+        return false;
+    }
+    lp.needJacobian = lp.last_rejected = false;
+    r.newJacobian = r.solve_enqueued = true;
+    lp.age++;
+    commit_spec_round();
+    return true;
+}
+
+// the Jacobian side of a pass, LS:996-1063: a Broyden pass or a full refresh, then J^T J and J^T y
+template <typename T>
+bool Solver<T>::jacobian_side(Round& r)
+{
+    round_kind = r.solve_enqueued ? 1 : 2;
+    if (!lp.needJacobian) return true;
+    lp.needJacobian = lp.last_rejected = false;
+    r.newJacobian = true;
+    const bool broyden = lp.age < lp.maxAge;
+    round_kind = broyden ? 1 : 0;
+    lp.age = broyden ? lp.age + 1 : 0;
+    if (broyden && stats) stats->jacobian_broyden++;
+    if (!(broyden ? jacobian_products(true, y, mB)                       // Broyden, LS:999-1007
+                  : full_refresh())) return false;                       // LS:1008-1052, 1065
+    trace_emit(broyden ? 1 : 0, ret.iterations, ret.lambda, ret.residual, 0, st_h->dx_dot);
+    return true;
+}
+
+// ---- one ROUND: the n x n solve for a ladder of lambdas, the trial residuals, the decision.
+// LS:1053-1062 (gradient test, inside the kernel when a new Jy exists), LS:1067-1110, 1141-1142
+// (damping, BOXCQP, step rounding, trial point, prediction), LS:1112-1161 (trial residual, acceptance).
+//
+// Speculation: after a rejection the reference re-solves with lambda * lambdaIncrease * mu, mu * 2
+// (LS:1103, 1127) and J^T J, J^T y unchanged -- the whole ladder lambda_0 .. lambda_{ks-1} is known in
+// advance. Workgroup k solves with lambda_k, all trial points are evaluated (one sweep of the batched
+// residual callback, or one call of f per point) and k_decide_chain walks them in the reference's order; entries after the
+// first accepted one are discarded, so results, counters and callback-visible semantics of accepted
+// points are unchanged. The ladder stops where the reference's top-of-loop checks would intervene
+// (lambda > maxLambda LS:979, forced refresh LS:984).
+template <typename T>
+void Solver<T>::ladder(Round& r)
+{
+    r.lambda_from_state = !r.solve_enqueued && !LM_LAMBDA_SET(ret.lambda, sd);   // first pass: lambda_0 rule inside the kernel
+    r.lam[0] = ret.lambda;
+    if (lp.speculate && !r.newJacobian && !r.lambda_from_state && lp.last_rejected) {
+        T l2 = ret.lambda, m2 = lp.mu;
+        while (r.ks < kChainMax) {
+            LM_REJECT(l2, m2, sd);                                        // LS:1103-1104, 1127-1128
+            if (!LM_LAMBDA_IN_RANGE(l2, sd)) break;                       // LS:979 would exit there
+            if (m2 > kSuspiciousMu && lp.age) break;                      // LS:984 would force a refresh there
+            r.lam[r.ks++] = l2;
+        }
+    }
+}
+
+// the ladder's solves, unless the fused round has solved already; then the null-step probe
+template <typename T>
+bool Solver<T>::solve_round(Round& r)
+{
+    if (!r.solve_enqueued) {
+        const LmSolveArgs<T> a = solve_args(r.ks, r.lam, r.newJacobian, r.lambda_from_state);
+        ev_begin(2);
+        {
+            HpScope hp(this, 4);
+            // all bounds infinite: the variant without the BOXCQP active-set loop (solve_kernel.h, BOUNDED = false)
+            if (!ok(launch_lm_solve<T>(a, r.ks, has_bounds, big_solve, stream), "solve launch")) return false;
+        }
+        ev_end();
+        if (dbg_solve) print_solve_dbg(false);
+    }
+    // null-step probe: one small read-back instead of ks residual evaluations, only while the tail is running
+    if (!(device_cb && tail_null && lp.last_rejected && !r.newJacobian && !no_null_skip)) return true;
+    HpScope hp(this, 3);
+    ChainRec<T> rr[kChainMax];
+    if (!ok(hipMemcpyAsync(rr, B.rec, (size_t)r.ks * sizeof(ChainRec<T>), hipMemcpyDeviceToHost, stream), "D2H rec")
+        || !ok(hipStreamSynchronize(stream), "sync")) return false;
+    r.skip_eval = true;
+    for (int k = 0; k < r.ks; ++k) if (!(rr[k].flags & kFlagNullStep)) r.skip_eval = false;
+    if (r.skip_eval && stats) stats->elided_evaluations += (uint64_t)r.ks;
+    return true;
+}
+
+// trial residuals -> r.ytr (k-th vector at ytr + k * m); with one trial they go straight into the free buffer
+template <typename T>
+bool Solver<T>::trial_residuals(Round& r)
+{
+    if (r.ks > 1) r.ytr = static_cast<T*>(ws->ytrial);
+    if (r.skip_eval) return true;      // every trial of the round equals x: the decision kernel substitutes the residual it already has
+    if (device_cb) {
+        // no host round trip before the residual: it is evaluated speculatively even when the record will
+        // forbid it (gradient converged, QP failure, step guard) -- the decision kernel then ignores it
+        HpScope hp(this, 2);
+        ev_begin(5);
+        if (r.ks > 1 && fb) fb(fbctx, m, n, (size_t)r.ks, B.trial, r.ytr);
+        else for (int k = 0; k < r.ks; ++k) f(fctx, m, n, B.trial + (size_t)k * n, r.ytr + (size_t)k * m);
+        ev_end();
+        if (stats) { stats->trial_callback_points += (uint64_t)r.ks; stats->trial_callback_calls++; }
+    } else {
+        // reference contract: the callback needs the trial point on the host
+        ChainRec<T> r0;
+        if (!ok(hipMemcpyAsync(&r0, B.rec, sizeof r0, hipMemcpyDeviceToHost, stream), "D2H rec")) return false;
+        {
+            HpScope hp(this, 3);
+            if (!ok(hipMemcpyAsync(st_h, B.st, sizeof(LmState<T>), hipMemcpyDeviceToHost, stream), "D2H state")
+                || !ok(hipMemcpyAsync(trial_h, B.trial, n * sizeof(T), hipMemcpyDeviceToHost, stream), "D2H vec")
+                || !ok(hipStreamSynchronize(stream), "sync")) return false;
+        }
+        const bool null_step = (r0.flags & kFlagNullStep) && !no_null_skip;     // trial_h == xh bit for bit
+        if (null_step && stats) stats->elided_evaluations++;
+        const bool no_f = (r.newJacobian && (r0.flags & kFlagGradSmall)) || r0.qp_status != 0
+            || (r0.flags & (kFlagDxNaN | kFlagStepTooLong)) || null_step;
+        if (!no_f && !eval_f(B.trial, trial_h, r.ytr)) return false;
+    }
+    return true;
+}
+
+// the decision of the round, alone or as the head of a fused round's kernel; then the host waits for its image
+template <typename T>
+bool Solver<T>::decide(Round& r)
+{
+    // Fused round: one trial now, and -- if it is accepted and no exit test fires (decided on the device) -- a Broyden pass
+    // next that needs neither a full refresh (age) nor a flush of the pending terms (lr_k). One-bit predictor: only while
+    // first trials are being accepted (the rejection tail of a noisy fit would waste a sweep per miss).
+    r.fuse = fused && lp.spec_predict && r.ks == 1 && !r.skip_eval && lp.age < lp.maxAge && lr_k < lr_cap;
+    if (r.fuse ? !enqueue_fused_tail(r.ytr, r.newJacobian, r.lambda_from_state)
+               : !enqueue_decide(r.ks, r.newJacobian, r.lambda_from_state, r.skip_eval ? nullptr : r.ytr)) return false;
+    if (!wait_state(seq)) return false;
+    if (r.fuse) {
+        if (st_h->spec_ok) lp.spec_live = true; else drop_spec_round();
+        if (dbg_solve && lp.spec_live) print_solve_dbg(true);
+    }
+    if (r.ks == 1 && r.newJacobian) lp.spec_predict = st_h->decision == kDecideAccept;
+    return true;
+}
+
+// booking of the decision, LS:1112-1173: the counters, the reference's exits, and on acceptance x, the residual buffers, the tests
+template <typename T>
+typename Solver<T>::Flow Solver<T>::book(Round& r)
+{
+    if (trace && !trace_round(r.ks, ret.residual, ret.iterations)) return Flow::error;
+    if (st_h->coop_rescued) {
+        // helper workgroups of the any-n solve did not answer within kCoopSpinSeconds (a GPU shared with other work, a
+        // starved queue): the rescue launch has solved those entries on one workgroup; the rest of THIS solve does not ask
+        // for helpers again (one stall per solve at most) and the caller's statistics say so
+        if (stats) stats->coop_timeouts += st_h->coop_rescued;
+        coop_disabled = true;
+    }
+    const int dec = st_h->decision;
+    tail_null = st_h->null_tail != 0;
+    ret.fCalls += st_h->fcalls;                                          // LS:1112
+    if (stats) {
+        if (st_h->consumed > 1) stats->passes += st_h->consumed - 1;
+        stats->rejected += st_h->rejects;
+        stats->step_guard_rejects += st_h->guards;
+        stats->qp_active_set_passes += st_h->qp_active;
+    }
+    if (dec == kDecideGradSmall) {                                       // LS:1053-1062
+        if (lp.age == 0) return stop(mir_ls_gConverged);
+        lp.age = lp.maxAge;
+        return Flow::next;
+    }
+    ret.lambda = st_h->lambda;
+    lp.mu = st_h->mu;
+    if (dec == kDecideNumericError) return stop(mir_ls_numericError);    // LS:1080-1092, 1117-1122
+    if (dec == kDecideReject) { lp.last_rejected = true; return Flow::next; }   // LS:1101-1106, 1125-1130
+    lp.last_rejected = false;
+
+    lp.needJacobian = true;                                              // LS:1132-1139
+    ret.iterations = st_h->iterations;
+    for (uint32_t i = 0; i < n; ++i) xh[i] = x_h[i];                     // the decision kernel published the new x
+    if (r.ytr != fr
+        && !ok(hipMemcpyAsync(fr, r.ytr + (size_t)st_h->accepted_k * m, m * sizeof(T), hipMemcpyDeviceToDevice, stream), "D2D y"))
+        return Flow::error;
+    { T* t = mB; mB = y; y = fr; fr = t; }                               // swap(mBuffer, y) of LS:1136 as a rotation of three
+    ret.residual = st_h->residual;
+    lp.fConverged = LM_F_CONVERGED(ret.residual, sd);
+    if (stats) stats->accepted++;
+
+    if (dec == kDecideAcceptNoPrediction) return stop(mir_ls_furtherImprovement);   // LS:1144-1148
+
+    const T dxn = std::sqrt(st_h->dx_dot);                               // LS:1164-1173 (quirk Q6)
+    if (!LM_X_MOVING(dxn, st_h->trial_xnorm, sd)) {
+        if (lp.age == 0) return stop(mir_ls_xConverged);
+        lp.age = lp.maxAge;
+    }
+    return Flow::next;
+}
+
+// one pass of the loop, LS:972-1174
+template <typename T>
+typename Solver<T>::Flow Solver<T>::pass()
+{
+    Round r{fr};
+    const Flow top = top_of_pass();
+    if (top != Flow::go) return top;
+    if (!adopt_spec_round(r) || !jacobian_side(r)) return Flow::error;
+    ladder(r);
+    if (!solve_round(r) || !trial_residuals(r) || !decide(r)) return Flow::error;
+    return book(r);
+}
+
 template <typename T>
 typename Solver<T>::Result Solver<T>::run()
 {
@@ -420,240 +650,18 @@ typename Solver<T>::Result Solver<T>::run()
     ret.residual = Lim<T>::inf(); ret.lambda = 0;
     const auto t_start = std::chrono::steady_clock::now();
     launches_mark = launches_now();
-
-    // validation, LS:930-943 (quirk Q9) -- needs no device
-    {
-        bool finite = true;
-        for (uint32_t i = 0; i < n; ++i) if (!(-Lim<T>::inf() < xh[i] && xh[i] < Lim<T>::inf())) finite = false;
-        if (m == 0 || n == 0 || !finite) { ret.status = mir_ls_badGuess; return ret; }
-        for (uint32_t i = 0; i < n; ++i) if (!(lh[i] <= xh[i]) || !(xh[i] <= uh[i])) { ret.status = mir_ls_badBounds; return ret; }
-        if (const int bad = bad_settings(S)) { ret.status = bad; return ret; }
-    }
+    if (const int bad = invalid_input()) { ret.status = bad; return ret; }   // LS:930-943
     if (!device_available()) return ret;
-    if (!setup()) { teardown(); return ret; }
-    has_bounds = (variant & MIR_LSQ_VARIANT_SOLVE_BOUNDED) != 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (lh[i] > -Lim<T>::inf() || uh[i] < Lim<T>::inf()) has_bounds = true;
-
-    const uint32_t maxAge = S->maxAge ? S->maxAge : (g ? 3 : 2 * n);     // LS:945 (quirk Q4)
-
-    bool fail = false;
-    do {   // single-exit block for device errors
-        bool entry_done = false;                                         // f(x0) came with the first refresh's panel (fd_entry)
-        if (!fd_entry(entry_done)) { fail = true; break; }
-        if (!entry_done && !eval_f(B.x, xh, y)) { fail = true; break; }  // LS:953
-        ++ret.fCalls;
-        ++seq;
-        if (!sumsq(y, 0)) { fail = true; break; }                        // LS:955
-        MIRLSQ_LAUNCH(k_init_state<T>, dim3(1), dim3(1), 0, stream, B.sum, B.st, st_slot_d[seq & 1], seq);
-        if (!ok(hipGetLastError(), "init state") || !wait_state(seq)) { fail = true; break; }
-    } while (false);
-    if (fail) { teardown(); ret.status = mir_ls_numericError; return ret; }
-
-    ret.residual = st_h->residual;
-    bool fConverged = LM_F_CONVERGED(ret.residual, sd);                  // LS:956
-    bool needJacobian = true;                                            // LS:959
-    bool last_rejected = false;
-    bool spec_live = false;            // the Jacobian side and the solve of the round at the top of the loop have run already (fused round)
-    bool spec_predict = true;          // the last first trial after a Jacobian update was accepted
-    const bool speculate = device_cb && !no_speculation;        // ladder trials: one fb call, or ks calls of f
-    uint32_t age = maxAge;
-    ret.lambda = 0;
-    T mu = 1;
-    ret.status = mir_ls_maxIterations;                                   // LS:971
-
-    do {
+    bool good = setup() && enter();
+    if (good) {
+        Flow fl;
+        do fl = pass(); while (fl == Flow::next && ret.iterations < S->maxIterations);   // LS:1175
+        good = fl != Flow::error;
+        if (fd_entry_ready) fd_entry_discard();                          // ended before the first refresh
         close_round();
-        if (stats) stats->passes++;
-        if (fConverged) { ret.status = mir_ls_fConverged; break; }       // LS:974-978
-        if (!LM_LAMBDA_IN_RANGE(ret.lambda, sd)) { ret.status = mir_ls_furtherImprovement; break; }   // LS:979-983
-        if (mu > kSuspiciousMu && age) {                                 // LS:984-989
-            needJacobian = true;
-            age = maxAge;
-            mu = 1;
-            MIRLSQ_LAUNCH(k_reset_mu<T>, dim3(1), dim3(1), 0, stream, B.st);
-        }
-        {                                                                // LS:990-995
-            bool nan = false;
-            for (uint32_t i = 0; i < n; ++i) if (!(xh[i] <= xh[i])) nan = true;
-            if (nan) { ret.status = mir_ls_numericError; break; }
-        }
-        bool newJacobian = false;
-        int ks = 1;
-        bool lambda_from_state = false, skip_eval = false;
-        T* ytr = fr;
-        bool solve_enqueued = false;
-        if (spec_live) {
-            // the Jacobian side and the solve of this round have run in the previous round's fused kernel
-            spec_live = false;
-            if (!needJacobian || !(age < maxAge) || lr_k >= lr_cap) {
-                std::fprintf(stderr, "[mir_optim_amd] internal error: the pass run ahead by the fused round is not the next pass\n");
-                fail = true;
-                break;
-            }
-            needJacobian = false;
-            newJacobian = true;
-            last_rejected = false;
-            age++;
-            commit_spec_round();
-            solve_enqueued = true;
-        }
-        round_kind = solve_enqueued ? 1 : 2;
-        if (needJacobian) {                                              // LS:996-1063
-            needJacobian = false;
-            newJacobian = true;
-            last_rejected = false;
-            round_kind = age < maxAge ? 1 : 0;
-            if (age < maxAge) {                                          // Broyden, LS:999-1007
-                age++;
-                if (stats) stats->jacobian_broyden++;
-                if (!jacobian_products(true, y, mB)) { fail = true; break; }
-                trace_emit(1, ret.iterations, ret.lambda, ret.residual, 0, st_h->dx_dot);
-            } else {
-                age = 0;
-                if (stats) stats->jacobian_full++;
-                const auto t0 = std::chrono::steady_clock::now();
-                bool okj;
-                if (g) okj = analytic_jacobian();                        // LS:1011-1015
-                else okj = device_cb ? fd_device() : fd_host();          // LS:1016-1050
-                if (!okj) { fail = true; break; }
-                // fd_ms: host-callback mode is synchronous anyway (wall clock); in device-callback mode the refresh is only
-                // ENQUEUED here -- no stream synchronisation for the sake of a statistic: fd_callback_ms (events) covers it
-                if (stats && !device_cb)
-                    stats->fd_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-                if (!jacobian_products(false, y, mB)) { fail = true; break; }
-                trace_emit(0, ret.iterations, ret.lambda, ret.residual, 0, st_h->dx_dot);
-            }
-        }
-
-        // ---- one ROUND: the n x n solve for a ladder of lambdas, the trial residuals, the decision.
-        // LS:1053-1062 (gradient test, inside the kernel when a new Jy exists), LS:1067-1110, 1141-1142
-        // (damping, BOXCQP, step rounding, trial point, prediction), LS:1112-1161 (trial residual, acceptance).
-        //
-        // Speculation: after a rejection the reference re-solves with lambda * lambdaIncrease * mu, mu * 2
-        // (LS:1103, 1127) and J^T J, J^T y unchanged -- the whole ladder lambda_0 .. lambda_{ks-1} is known in
-        // advance. Workgroup k solves with lambda_k, all trial points are evaluated (one sweep of the batched
-        // residual callback, or one call of f per point) and k_decide_chain walks them in the reference's order; entries after the
-        // first accepted one are discarded, so results, counters and callback-visible semantics of accepted
-        // points are unchanged. The ladder stops where the reference's top-of-loop checks would intervene
-        // (lambda > maxLambda LS:979, forced refresh LS:984).
-        lambda_from_state = !solve_enqueued && !LM_LAMBDA_SET(ret.lambda, sd);   // first pass: lambda_0 rule inside the kernel
-        T lam[kChainMax];
-        lam[0] = ret.lambda;
-        if (speculate && !newJacobian && !lambda_from_state && last_rejected) {
-            T l2 = ret.lambda, m2 = mu;
-            while (ks < kChainMax) {
-                LM_REJECT(l2, m2, sd);                                    // LS:1103-1104, 1127-1128
-                if (!LM_LAMBDA_IN_RANGE(l2, sd)) break;                   // LS:979 would exit there
-                if (m2 > kSuspiciousMu && age) break;                     // LS:984 would force a refresh there
-                lam[ks++] = l2;
-            }
-        }
-        if (!solve_enqueued && !enqueue_solve(ks, lam, newJacobian, lambda_from_state)) { fail = true; break; }
-        if (dbg_solve && !solve_enqueued) print_solve_dbg(false);
-
-        // null-step probe: one small read-back instead of ks residual evaluations, only while the tail is running
-        if (device_cb && tail_null && last_rejected && !newJacobian && !no_null_skip) {
-            HpScope hp(this, 3);
-            ChainRec<T> rr[kChainMax];
-            if (!ok(hipMemcpyAsync(rr, B.rec, (size_t)ks * sizeof(ChainRec<T>), hipMemcpyDeviceToHost, stream), "D2H rec")
-                || !ok(hipStreamSynchronize(stream), "sync")) { fail = true; break; }
-            skip_eval = true;
-            for (int k = 0; k < ks; ++k) if (!(rr[k].flags & kFlagNullStep)) skip_eval = false;
-            if (skip_eval && stats) stats->elided_evaluations += (uint64_t)ks;
-        }
-
-        // trial residuals -> ytr (k-th vector at ytr + k * m); with one trial they go straight into the free buffer
-        if (ks > 1) ytr = static_cast<T*>(ws->ytrial);
-        if (skip_eval) {
-            // every trial of the round equals x: the decision kernel substitutes the residual it already has
-        } else if (device_cb) {
-            // no host round trip before the residual: it is evaluated speculatively even when the record will
-            // forbid it (gradient converged, QP failure, step guard) -- the decision kernel then ignores it
-            HpScope hp(this, 2);
-            ev_begin(5);
-            if (ks > 1 && fb) fb(fbctx, m, n, (size_t)ks, B.trial, ytr);
-            else for (int k = 0; k < ks; ++k) f(fctx, m, n, B.trial + (size_t)k * n, ytr + (size_t)k * m);
-            ev_end();
-            if (stats) { stats->trial_callback_points += (uint64_t)ks; stats->trial_callback_calls++; }
-        } else {
-            // reference contract: the callback needs the trial point on the host
-            ChainRec<T> r0;
-            if (!ok(hipMemcpyAsync(&r0, B.rec, sizeof r0, hipMemcpyDeviceToHost, stream), "D2H rec") || !read_state(B.trial)) { fail = true; break; }
-            const bool null_step = (r0.flags & kFlagNullStep) && !no_null_skip;     // trial_h == xh bit for bit
-            if (null_step && stats) stats->elided_evaluations++;
-            const bool no_f = (newJacobian && (r0.flags & kFlagGradSmall)) || r0.qp_status != 0
-                || (r0.flags & (kFlagDxNaN | kFlagStepTooLong)) || null_step;
-            if (!no_f && !eval_f(B.trial, trial_h, ytr)) { fail = true; break; }
-        }
-
-        // Fused round: one trial now, and -- if it is accepted and no exit test fires (decided on the device) -- a Broyden pass
-        // next that needs neither a full refresh (age) nor a flush of the pending terms (lr_k). One-bit predictor: only while
-        // first trials are being accepted (the rejection tail of a noisy fit would waste a sweep per miss).
-        const bool fuse = fused && spec_predict && ks == 1 && !skip_eval && age < maxAge && lr_k < lr_cap;
-        if (fuse ? !enqueue_fused_tail(ytr, newJacobian, lambda_from_state)
-                 : !enqueue_decide(ks, newJacobian, lambda_from_state, skip_eval ? nullptr : ytr)) { fail = true; break; }
-        const uint32_t round_seq = seq;
-        if (!wait_state(round_seq)) { fail = true; break; }
-        if (fuse) {
-            if (st_h->spec_ok) spec_live = true; else drop_spec_round();
-            if (dbg_solve && spec_live) print_solve_dbg(true);
-        }
-        if (ks == 1 && newJacobian) spec_predict = st_h->decision == kDecideAccept;
-
-        if (trace && !trace_round(ks, ret.residual, ret.iterations)) { fail = true; break; }
-        if (st_h->coop_rescued) {
-            // helper workgroups of the any-n solve did not answer within kCoopSpinSeconds (a GPU shared with other work, a
-            // starved queue): the rescue launch has solved those entries on one workgroup; the rest of THIS solve does not ask
-            // for helpers again (one stall per solve at most) and the caller's statistics say so
-            if (stats) stats->coop_timeouts += st_h->coop_rescued;
-            coop_disabled = true;
-        }
-        const int dec = st_h->decision;
-        tail_null = st_h->null_tail != 0;
-        ret.fCalls += st_h->fcalls;                                      // LS:1112
-        if (stats) {
-            if (st_h->consumed > 1) stats->passes += st_h->consumed - 1;
-            stats->rejected += st_h->rejects;
-            stats->step_guard_rejects += st_h->guards;
-            stats->qp_active_set_passes += st_h->qp_active;
-        }
-        if (dec == kDecideGradSmall) {                                   // LS:1053-1062
-            if (age == 0) { ret.status = mir_ls_gConverged; break; }
-            age = maxAge;
-            continue;
-        }
-        ret.lambda = st_h->lambda;
-        mu = st_h->mu;
-        if (dec == kDecideNumericError) { ret.status = mir_ls_numericError; break; }   // LS:1080-1092, 1117-1122
-        if (dec == kDecideReject) { last_rejected = true; continue; }    // LS:1101-1106, 1125-1130
-        last_rejected = false;
-
-        needJacobian = true;                                             // LS:1132-1139
-        ret.iterations = st_h->iterations;
-        for (uint32_t i = 0; i < n; ++i) xh[i] = x_h[i];                 // the decision kernel published the new x
-        if (ytr != fr) {
-            if (!ok(hipMemcpyAsync(fr, ytr + (size_t)st_h->accepted_k * m, m * sizeof(T), hipMemcpyDeviceToDevice, stream), "D2D y")) { fail = true; break; }
-        }
-        { T* t = mB; mB = y; y = fr; fr = t; }                           // swap(mBuffer, y) of LS:1136 as a rotation of three
-        ret.residual = st_h->residual;
-        fConverged = LM_F_CONVERGED(ret.residual, sd);
-        if (stats) stats->accepted++;
-
-        if (dec == kDecideAcceptNoPrediction) { ret.status = mir_ls_furtherImprovement; break; }   // LS:1144-1148
-
-        const T dxn = std::sqrt(st_h->dx_dot);                           // LS:1164-1173 (quirk Q6)
-        if (!LM_X_MOVING(dxn, st_h->trial_xnorm, sd)) {
-            if (age == 0) { ret.status = mir_ls_xConverged; break; }
-            age = maxAge;
-            continue;
-        }
-    } while (ret.iterations < S->maxIterations);                         // LS:1175
-
-    if (fd_entry_ready) fd_entry_discard();                              // ended before the first refresh
-    close_round();
-    if (fail) ret.status = mir_ls_numericError;
-    if (stats) stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        if (stats) stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    if (!good) ret.status = mir_ls_numericError;                         // a device error, wherever it happened
     teardown();
     return ret;
 }

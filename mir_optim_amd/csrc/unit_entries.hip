@@ -91,205 +91,11 @@ int box_qp_entry(const QS* settings, size_t n_, const T* P, const T* q, const T*
     return out[0];
 }
 
-// mir_lsq_lm_solve_*: ONE launch_lm_solve (one round's n x n part, ks ladder entries) on operands of the caller's, every device
-// region the kernels are handed -- the five inputs, dx, trial, rec, the state, and each ladder entry's Pm, A, Fg, vec, ivec, coop,
-// cS, at workspace.hip's sizes -- inside one allocation with at least kLmGuardBytes of 0xFF bytes (a NaN in both types) in front
-// of it and behind it: a band starts at the last byte of the region before it and ends where the next region starts (256-byte
-// aligned, as the workspace's). The scratch regions start as that pattern too (a read of scratch nobody wrote shows as a NaN), the
-// helpers' sync words as zero with epoch 1 (a fresh workspace's first solve), dx / trial as MIR_LSQ_LM_SOLVE_SENTINEL.
+// The allocation of the entries below: regions between guard bands -- at least kLmGuardBytes of 0xFF bytes (a NaN in both types)
+// in front of each region and behind the last, regions 256-byte aligned as the workspace's; band b starts at the last byte of
+// region b - 1 and ends where region b starts -- everything preset to 0xFF (a read of scratch nobody wrote shows as a NaN).
+// Device memory, or -- pinned -- device-mapped coherent host memory as the solver's mirror (workspace.hip).
 constexpr size_t kLmGuardBytes = 4096;
-template <typename T, typename S, typename R>
-int lm_solve_entry(const S* settings, size_t n_, T* JJ, T* Jy, T* x, T* lower, T* upper, int ks, const T* lam, T state_lambda,
-                   unsigned mode, R* rec, T* dx, T* trial, T* jy_inf, int info[6])
-{
-    if (!settings || !JJ || !Jy || !x || !lower || !upper || !lam || !rec || !dx || !trial || !jy_inf || !info) return -1;
-    if (n_ == 0 || n_ > 4096 || ks < 1 || ks > kChainMax || (mode & ~31u)) return -1;
-    if (!device_available()) return -2;
-    const int n = (int)n_;
-    const size_t nn = (size_t)n * n;
-    struct Region { size_t off, bytes; };
-    std::vector<Region> reg;
-    size_t off = 0;
-    auto take = [&](size_t count, size_t elem) {
-        off = align_up(off + kLmGuardBytes, 256);
-        reg.push_back({off, count * elem});
-        off += count * elem;
-        return reg.size() - 1;
-    };
-    const size_t rJJ = take(nn, sizeof(T)), rJy = take(n, sizeof(T)), rx = take(n, sizeof(T)), rlo = take(n, sizeof(T)),
-                 rup = take(n, sizeof(T)), rdx = take((size_t)kChainMax * n, sizeof(T)), rtr = take((size_t)kChainMax * n, sizeof(T)),
-                 rrec = take(kChainMax, sizeof(ChainRec<T>)), rst = take(1, sizeof(LmState<T>));
-    size_t rsc[kChainMax][7];
-    for (int k = 0; k < kChainMax; ++k) {
-        rsc[k][0] = take(nn, sizeof(T)); rsc[k][1] = take(nn, sizeof(T)); rsc[k][2] = take((size_t)n * (n | 1), sizeof(T));
-        rsc[k][3] = take((size_t)12 * n, sizeof(T)); rsc[k][4] = take((size_t)2 * n, sizeof(int32_t));
-        rsc[k][5] = take(n > kSolveMaxN ? kCoopWords : 0, sizeof(unsigned long long));
-        rsc[k][6] = take(coop_scratch_elems(n), sizeof(T));
-    }
-    const size_t total = align_up(off + kLmGuardBytes, 256);
-    char* base = nullptr;
-    if (hipMalloc((void**)&base, total) != hipSuccess) return -3;
-    auto at = [&](size_t r) { return base + reg[r].off; };
-    LmSolveArgs<T> a{};
-    a.JJ = (T*)at(rJJ); a.Jy = (T*)at(rJy); a.x = (T*)at(rx); a.lower = (T*)at(rlo); a.upper = (T*)at(rup);
-    a.dx = (T*)at(rdx); a.trial = (T*)at(rtr); a.rec = (ChainRec<T>*)at(rrec); a.st = (LmState<T>*)at(rst);
-    a.set = lm_settings_dev(settings); a.n = n;
-    for (int k = 0; k < kChainMax; ++k) {
-        a.sc[k].Pm = (T*)at(rsc[k][0]); a.sc[k].A = (T*)at(rsc[k][1]); a.sc[k].Fg = (T*)at(rsc[k][2]); a.sc[k].vec = (T*)at(rsc[k][3]);
-        a.sc[k].ivec = (int32_t*)at(rsc[k][4]); a.sc[k].dbg = nullptr; a.sc[k].coop = (unsigned long long*)at(rsc[k][5]);
-        a.sc[k].cS = (T*)at(rsc[k][6]);
-        a.lam[k] = k < ks ? lam[k] : T(0);
-    }
-    a.f_in_lds = solve_nb(n, (int)sizeof(T)) > 0;
-    a.check_grad = (mode & 1u) ? 1 : 0;
-    a.lambda_from_state = (mode & 2u) ? 1 : 0;
-    bool bounded = (mode & 4u) != 0;
-    for (int i = 0; i < n; ++i)
-        if (lower[i] > -Lim<T>::inf() || upper[i] < Lim<T>::inf()) bounded = true;
-    const bool generic = (mode & 8u) != 0;
-    a.coop_w = coop_width(n, query_num_cu(), !(mode & 16u));
-    a.coop_epoch = a.coop_w > 1 ? 1u : 0u;
-    const LmSolveClass cls = lm_solve_class((int)sizeof(T), n, bounded, generic, false);
-    info[0] = cls.kind; info[1] = cls.nb; info[2] = cls.bounded; info[3] = a.coop_w; info[4] = -1; info[5] = (int)reg.size() + 1;
-
-    LmState<T> st{};
-    st.lambda = state_lambda;
-    std::vector<T> sentinel((size_t)kChainMax * n, T(MIR_LSQ_LM_SOLVE_SENTINEL));
-    bool good = hipMemset(base, 0xFF, total) == hipSuccess;
-    auto up_ = [&](size_t r, const void* src) { good = good && hipMemcpy(at(r), src, reg[r].bytes, hipMemcpyHostToDevice) == hipSuccess; };
-    up_(rJJ, JJ); up_(rJy, Jy); up_(rx, x); up_(rlo, lower); up_(rup, upper); up_(rdx, sentinel.data()); up_(rtr, sentinel.data());
-    up_(rst, &st);
-    for (int k = 0; k < kChainMax; ++k)
-        if (reg[rsc[k][5]].bytes) good = good && hipMemset(at(rsc[k][5]), 0, reg[rsc[k][5]].bytes) == hipSuccess;
-    if (!good) { (void)hipFree(base); return -3; }
-    if (launch_lm_solve<T>(a, ks, bounded, generic, nullptr) != hipSuccess) { (void)hipDeviceSynchronize(); (void)hipFree(base); return -4; }
-    // host image of the allocation: everything up to the first scratch region in one copy, behind it the bands alone (the scratch
-    // is 3 n^2 elements a ladder entry and nobody reads it here). Band b lies in front of region b, the last one behind the last.
-    std::unique_ptr<unsigned char[]> img(new unsigned char[total]);
-    auto band = [&](size_t b, size_t& lo, size_t& hi) {
-        lo = b ? reg[b - 1].off + reg[b - 1].bytes : 0; hi = b < reg.size() ? reg[b].off : total;
-    };
-    good = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess
-        && hipMemcpy(img.get(), base, reg[rsc[0][0]].off, hipMemcpyDeviceToHost) == hipSuccess;
-    for (size_t b = rsc[0][0] + 1; b <= reg.size() && good; ++b) {
-        size_t lo, hi;
-        band(b, lo, hi);
-        good = hipMemcpy(img.get() + lo, base + lo, hi - lo, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    (void)hipFree(base);
-    if (!good) return -5;
-    for (size_t b = 0; b <= reg.size() && info[4] < 0; ++b) {
-        size_t lo, hi;
-        band(b, lo, hi);
-        for (size_t i = lo; i < hi; ++i)
-            if (img[i] != 0xFF) { info[4] = (int)b; break; }
-    }
-    auto down = [&](size_t r, void* dst, size_t bytes) { std::memcpy(dst, img.get() + reg[r].off, bytes); };
-    down(rJJ, JJ, reg[rJJ].bytes); down(rJy, Jy, reg[rJy].bytes); down(rx, x, reg[rx].bytes); down(rlo, lower, reg[rlo].bytes);
-    down(rup, upper, reg[rup].bytes); down(rdx, dx, reg[rdx].bytes); down(rtr, trial, reg[rtr].bytes);
-    std::vector<ChainRec<T>> rh(kChainMax);
-    down(rrec, rh.data(), reg[rrec].bytes);
-    for (int k = 0; k < ks; ++k) {
-        rec[k].lambda = rh[k].lambda; rec[k].new_dx_dot = rh[k].new_dx_dot; rec[k].predicted = rh[k].predicted;
-        rec[k].trial_xnorm = rh[k].trial_xnorm; rec[k].qp_status = rh[k].qp_status; rec[k].qp_iterations = rh[k].qp_iterations;
-        rec[k].flags = rh[k].flags; rec[k].reserved = 0;
-    }
-    down(rst, &st, sizeof st);
-    *jy_inf = st.jy_inf;
-    return 0;
-}
-
-// mir_lsq_lr_pass_*: the launches of Solver::broyden_lowrank behind its flush, without a communicator -- lr_sweep, lr_reduce,
-// lr_finish (not in speculation mode: the fused round's n x n side lives in the solve kernel) on the solver's lr_blocks(m, num_cu)
-// workgroups -- and then lr_sumsq + lr_sumsq_final over `count` m-vectors at y (vector 0 is the sweep's y). J, U, D, dx, dx_dot, y,
-// y_old, JJ, Jy are DEVICE pointers of the caller's; what the solver keeps in its workspace -- the partials, the reduced vector,
-// the stage-1 partials of the sums (pstride = the workgroup count, so that the region ends with the last partial), the sums, the
-// state and the record -- lies in one allocation of the call's, banded as lm_solve_entry's and preset to the same 0xFF bytes.
-template <typename T, typename R>
-int lr_pass_entry(size_t m, size_t n_, int k, const T* J, const T* twh, T* U, T* D, const T* dx, const T* dx_dot, const T* y, int count,
-                  const T* y_old, T* JJ, T* Jy, const R* spec, T absTolerance, T relTolerance, T* partials, T* reduced, T* sums,
-                  T* jy_inf, int info[6])
-{
-    if (!J || !U || !D || !dx || !dx_dot || !y || !y_old || !JJ || !Jy || !partials || !reduced || !sums || !jy_inf || !info) return -1;
-    if (m == 0 || n_ == 0 || n_ > (size_t)kLrMaxN || k < 0 || k >= kLrMax || count < 1 || count > kChainMax) return -1;
-    if (!device_available()) return -2;
-    const int n = (int)n_, len = lr_len(n);
-    const int nblk = lr_blocks(m, query_num_cu());
-    struct Region { size_t off, bytes; };
-    std::vector<Region> reg;
-    size_t off = 0;
-    auto take = [&](size_t cnt, size_t elem) {
-        off = align_up(off + kLmGuardBytes, 256);
-        reg.push_back({off, cnt * elem});
-        off += cnt * elem;
-        return reg.size() - 1;
-    };
-    const size_t rpart = take((size_t)nblk * len, sizeof(T)), rvec = take(len, sizeof(T)), rsp = take((size_t)count * nblk, sizeof(T)),
-                 rsum = take(count, sizeof(T)), rst = take(1, sizeof(LmState<T>)), rrec = take(1, sizeof(ChainRec<T>));
-    const size_t total = align_up(off + kLmGuardBytes, 256);
-    char* base = nullptr;
-    if (hipMalloc((void**)&base, total) != hipSuccess) return -3;
-    auto at = [&](size_t r) { return base + reg[r].off; };
-    const LrClass cls = lr_class_of<T>(n, J);
-    info[0] = cls.ncp; info[1] = cls.vec; info[2] = nblk; info[3] = -1; info[4] = (int)reg.size() + 1; info[5] = 0;
-    ChainRec<T> rec{};
-    if (spec) {
-        rec.lambda = spec->lambda; rec.new_dx_dot = spec->new_dx_dot; rec.predicted = spec->predicted; rec.trial_xnorm = spec->trial_xnorm;
-        rec.qp_status = spec->qp_status; rec.qp_iterations = spec->qp_iterations; rec.flags = spec->flags; rec.pad = spec->reserved;
-    }
-    bool good = hipMemset(base, 0xFF, total) == hipSuccess;
-    if (spec) good = good && hipMemcpy(at(rrec), &rec, sizeof rec, hipMemcpyHostToDevice) == hipSuccess;
-    if (!good) { (void)hipFree(base); return -3; }
-    LrArgs<T> a{};
-    a.J = J; a.U = U; a.D = D; a.dx = dx; a.dx_dot = dx_dot; a.y = y; a.y_old = y_old;
-    a.partials = (T*)at(rpart); a.m = m; a.n = n; a.k = k;
-    a.spec_rec = spec ? (const ChainRec<T>*)at(rrec) : nullptr;
-    a.absTolerance = absTolerance; a.relTolerance = relTolerance;
-    good = lr_sweep<T>(a, nblk, nullptr, twh) == hipSuccess     // twh != nullptr: J is the unscaled difference panel
-        && lr_reduce<T>((const T*)at(rpart), nblk, n, (T*)at(rvec), nullptr) == hipSuccess
-        && (spec || lr_finish<T>((const T*)at(rvec), D, dx, k, n, JJ, Jy, (LmState<T>*)at(rst), nullptr) == hipSuccess)
-        && lr_sumsq<T>(y, m, count, m, (T*)at(rsp), nblk, nblk, nullptr) == hipSuccess
-        && lr_sumsq_final<T>((const T*)at(rsp), nblk, nblk, count, (T*)at(rsum), nullptr) == hipSuccess;
-    if (!good) { (void)hipDeviceSynchronize(); (void)hipFree(base); return -4; }
-    std::unique_ptr<unsigned char[]> img(new unsigned char[total]);
-    good = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess
-        && hipMemcpy(img.get(), base, total, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(base);
-    if (!good) return -5;
-    for (size_t b = 0; b <= reg.size() && info[3] < 0; ++b) {
-        const size_t lo = b ? reg[b - 1].off + reg[b - 1].bytes : 0, hi = b < reg.size() ? reg[b].off : total;
-        for (size_t i = lo; i < hi; ++i)
-            if (img[i] != 0xFF) { info[3] = (int)b; break; }
-    }
-    // the state but for jy_inf, and the record: nobody writes them (info[5]: 1 the state, 2 the record, 3 both)
-    const size_t jlo = offsetof(LmState<T>, jy_inf), jhi = jlo + sizeof(T);
-    for (size_t i = 0; i < sizeof(LmState<T>); ++i)
-        if ((i < jlo || i >= jhi || spec) && img[reg[rst].off + i] != 0xFF) info[5] |= 1;
-    std::vector<unsigned char> want(sizeof rec, 0xFF);
-    if (spec) std::memcpy(want.data(), &rec, sizeof rec);
-    if (std::memcmp(img.get() + reg[rrec].off, want.data(), sizeof rec) != 0) info[5] |= 2;
-    std::memcpy(partials, img.get() + reg[rpart].off, reg[rpart].bytes);
-    std::memcpy(reduced, img.get() + reg[rvec].off, reg[rvec].bytes);
-    std::memcpy(sums, img.get() + reg[rsum].off, reg[rsum].bytes);
-    std::memcpy(jy_inf, img.get() + reg[rst].off + jlo, sizeof(T));
-    return 0;
-}
-
-// mir_lsq_lr_flush_*: one lr_flush on device pointers of the caller's
-template <typename T>
-int lr_flush_entry(size_t m, size_t n, int k, T* J, const T* U, const T* D, int info[2])
-{
-    if (!J || !U || !D || !info || m == 0 || n == 0 || n > (size_t)kLrMaxN || k < 1 || k > kLrMax) return -1;
-    if (!device_available()) return -2;
-    const LrClass cls = lr_class_of<T>((int)n, J);
-    info[0] = cls.ncp; info[1] = cls.vec;
-    if (lr_flush<T>(J, U, D, k, m, (int)n, query_num_cu(), nullptr) != hipSuccess) { (void)hipDeviceSynchronize(); return -4; }
-    return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -5;
-}
-
-// The allocation of the entries below: regions between guard bands as lm_solve_entry lays them out (at least kLmGuardBytes of
-// 0xFF bytes in front of each region and behind the last, regions 256-byte aligned, band b in front of region b), everything
-// preset to 0xFF. Device memory, or -- pinned -- device-mapped coherent host memory as the solver's mirror (workspace.hip).
 struct Banded {
     struct Region { size_t off, bytes; };
     std::vector<Region> reg;
@@ -319,33 +125,179 @@ struct Banded {
         return hipMemset(base, 0xFF, total) == hipSuccess;
     }
     char* at(size_t r) const { return base + reg[r].off; }
-    bool up(size_t r, const void* src, size_t bytes) const
+    bool up(size_t r, const void* src) const
     {
-        if (bytes > reg[r].bytes) return false;
-        if (!bytes) return true;
-        if (pinned) { std::memcpy(host + reg[r].off, src, bytes); return true; }
-        return hipMemcpy(at(r), src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        if (!reg[r].bytes) return true;
+        if (pinned) { std::memcpy(host + reg[r].off, src, reg[r].bytes); return true; }
+        return hipMemcpy(at(r), src, reg[r].bytes, hipMemcpyHostToDevice) == hipSuccess;
     }
-    bool up(size_t r, const void* src) const { return up(r, src, reg[r].bytes); }
-    bool fetch()                 // behind a device synchronisation
+    bool zero(size_t r) const { return !reg[r].bytes || hipMemset(at(r), 0, reg[r].bytes) == hipSuccess; }   // (device memory)
+    void band(size_t b, size_t& lo, size_t& hi) const { lo = b ? reg[b - 1].off + reg[b - 1].bytes : 0; hi = b < reg.size() ? reg[b].off : total; }
+    // the host image, behind a device synchronisation. payload < regions: everything up to region `payload` in one copy, behind
+    // it the bands alone (scratch nobody reads on the host)
+    bool fetch(size_t payload = (size_t)-1)
     {
         img.reset(new unsigned char[total]);
         if (pinned) { std::memcpy(img.get(), host, total); return true; }
-        return hipMemcpy(img.get(), base, total, hipMemcpyDeviceToHost) == hipSuccess;
+        if (payload >= reg.size()) return hipMemcpy(img.get(), base, total, hipMemcpyDeviceToHost) == hipSuccess;
+        bool good = hipMemcpy(img.get(), base, reg[payload].off, hipMemcpyDeviceToHost) == hipSuccess;
+        for (size_t b = payload + 1; b <= reg.size() && good; ++b) {
+            size_t lo, hi;
+            band(b, lo, hi);
+            good = hipMemcpy(img.get() + lo, base + lo, hi - lo, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        return good;
     }
     int damaged() const          // the first band that is not intact, or -1
     {
         for (size_t b = 0; b <= reg.size(); ++b) {
-            const size_t lo = b ? reg[b - 1].off + reg[b - 1].bytes : 0, hi = b < reg.size() ? reg[b].off : total;
+            size_t lo, hi;
+            band(b, lo, hi);
             for (size_t i = lo; i < hi; ++i)
                 if (img[i] != 0xFF) return (int)b;
         }
         return -1;
     }
     int bands() const { return (int)reg.size() + 1; }
-    void down(size_t r, void* dst) const { if (reg[r].bytes) std::memcpy(dst, img.get() + reg[r].off, reg[r].bytes); }
+    const unsigned char* image(size_t r) const { return img.get() + reg[r].off; }
+    void down(size_t r, void* dst) const { if (reg[r].bytes) std::memcpy(dst, image(r), reg[r].bytes); }
 };
 inline bool launches_done() { return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess; }
+
+// mir_lsq_lm_solve_*: ONE launch_lm_solve (one round's n x n part, ks ladder entries) on operands of the caller's, every device
+// region the kernels are handed -- the five inputs, dx, trial, rec, the state, and each ladder entry's Pm, A, Fg, vec, ivec, coop,
+// cS, at workspace.hip's sizes -- in one Banded allocation. The scratch regions start as its 0xFF pattern, the helpers' sync words
+// as zero with epoch 1 (a fresh workspace's first solve), dx / trial as MIR_LSQ_LM_SOLVE_SENTINEL.
+template <typename T, typename S, typename R>
+int lm_solve_entry(const S* settings, size_t n_, T* JJ, T* Jy, T* x, T* lower, T* upper, int ks, const T* lam, T state_lambda,
+                   unsigned mode, R* rec, T* dx, T* trial, T* jy_inf, int info[6])
+{
+    if (!settings || !JJ || !Jy || !x || !lower || !upper || !lam || !rec || !dx || !trial || !jy_inf || !info) return -1;
+    if (n_ == 0 || n_ > 4096 || ks < 1 || ks > kChainMax || (mode & ~31u)) return -1;
+    if (!device_available()) return -2;
+    const int n = (int)n_;
+    const size_t nn = (size_t)n * n;
+    Banded d;
+    const size_t rJJ = d.take(nn, sizeof(T)), rJy = d.take(n, sizeof(T)), rx = d.take(n, sizeof(T)), rlo = d.take(n, sizeof(T)),
+                 rup = d.take(n, sizeof(T)), rdx = d.take((size_t)kChainMax * n, sizeof(T)), rtr = d.take((size_t)kChainMax * n, sizeof(T)),
+                 rrec = d.take(kChainMax, sizeof(ChainRec<T>)), rst = d.take(1, sizeof(LmState<T>));
+    size_t rsc[kChainMax][7];
+    for (int k = 0; k < kChainMax; ++k) {
+        rsc[k][0] = d.take(nn, sizeof(T)); rsc[k][1] = d.take(nn, sizeof(T)); rsc[k][2] = d.take((size_t)n * (n | 1), sizeof(T));
+        rsc[k][3] = d.take((size_t)12 * n, sizeof(T)); rsc[k][4] = d.take((size_t)2 * n, sizeof(int32_t));
+        rsc[k][5] = d.take(n > kSolveMaxN ? kCoopWords : 0, sizeof(unsigned long long));
+        rsc[k][6] = d.take(coop_scratch_elems(n), sizeof(T));
+    }
+    if (!d.alloc()) return -3;
+    LmSolveArgs<T> a{};
+    a.JJ = (T*)d.at(rJJ); a.Jy = (T*)d.at(rJy); a.x = (T*)d.at(rx); a.lower = (T*)d.at(rlo); a.upper = (T*)d.at(rup);
+    a.dx = (T*)d.at(rdx); a.trial = (T*)d.at(rtr); a.rec = (ChainRec<T>*)d.at(rrec); a.st = (LmState<T>*)d.at(rst);
+    a.set = lm_settings_dev(settings); a.n = n;
+    for (int k = 0; k < kChainMax; ++k) {
+        a.sc[k].Pm = (T*)d.at(rsc[k][0]); a.sc[k].A = (T*)d.at(rsc[k][1]); a.sc[k].Fg = (T*)d.at(rsc[k][2]); a.sc[k].vec = (T*)d.at(rsc[k][3]);
+        a.sc[k].ivec = (int32_t*)d.at(rsc[k][4]); a.sc[k].dbg = nullptr; a.sc[k].coop = (unsigned long long*)d.at(rsc[k][5]);
+        a.sc[k].cS = (T*)d.at(rsc[k][6]);
+        a.lam[k] = k < ks ? lam[k] : T(0);
+    }
+    a.f_in_lds = solve_nb(n, (int)sizeof(T)) > 0;
+    a.check_grad = (mode & 1u) ? 1 : 0;
+    a.lambda_from_state = (mode & 2u) ? 1 : 0;
+    bool bounded = (mode & 4u) != 0;
+    for (int i = 0; i < n; ++i)
+        if (lower[i] > -Lim<T>::inf() || upper[i] < Lim<T>::inf()) bounded = true;
+    const bool generic = (mode & 8u) != 0;
+    a.coop_w = coop_width(n, query_num_cu(), !(mode & 16u));
+    a.coop_epoch = a.coop_w > 1 ? 1u : 0u;
+    const LmSolveClass cls = lm_solve_class((int)sizeof(T), n, bounded, generic, false);
+    info[0] = cls.kind; info[1] = cls.nb; info[2] = cls.bounded; info[3] = a.coop_w; info[4] = -1; info[5] = d.bands();
+
+    LmState<T> st{};
+    st.lambda = state_lambda;
+    std::vector<T> sentinel((size_t)kChainMax * n, T(MIR_LSQ_LM_SOLVE_SENTINEL));
+    bool good = d.up(rJJ, JJ) && d.up(rJy, Jy) && d.up(rx, x) && d.up(rlo, lower) && d.up(rup, upper) && d.up(rdx, sentinel.data())
+        && d.up(rtr, sentinel.data()) && d.up(rst, &st);
+    for (int k = 0; k < kChainMax; ++k) good = good && d.zero(rsc[k][5]);
+    if (!good) return -3;
+    if (launch_lm_solve<T>(a, ks, bounded, generic, nullptr) != hipSuccess) { (void)hipDeviceSynchronize(); return -4; }
+    // the scratch is 3 n^2 elements a ladder entry and nobody reads it here: the payloads in front of it, behind them the bands
+    if (!launches_done() || !d.fetch(rsc[0][0])) return -5;
+    info[4] = d.damaged();
+    d.down(rJJ, JJ); d.down(rJy, Jy); d.down(rx, x); d.down(rlo, lower); d.down(rup, upper); d.down(rdx, dx); d.down(rtr, trial);
+    std::vector<ChainRec<T>> rh(kChainMax);
+    d.down(rrec, rh.data());
+    for (int k = 0; k < ks; ++k) {
+        rec[k].lambda = rh[k].lambda; rec[k].new_dx_dot = rh[k].new_dx_dot; rec[k].predicted = rh[k].predicted;
+        rec[k].trial_xnorm = rh[k].trial_xnorm; rec[k].qp_status = rh[k].qp_status; rec[k].qp_iterations = rh[k].qp_iterations;
+        rec[k].flags = rh[k].flags; rec[k].reserved = 0;
+    }
+    d.down(rst, &st);
+    *jy_inf = st.jy_inf;
+    return 0;
+}
+
+// mir_lsq_lr_pass_*: the launches of Solver::broyden_lowrank behind its flush, without a communicator -- lr_sweep, lr_reduce,
+// lr_finish (not in speculation mode: the fused round's n x n side lives in the solve kernel) on the solver's lr_blocks(m, num_cu)
+// workgroups -- and then lr_sumsq + lr_sumsq_final over `count` m-vectors at y (vector 0 is the sweep's y). J, U, D, dx, dx_dot, y,
+// y_old, JJ, Jy are DEVICE pointers of the caller's; what the solver keeps in its workspace -- the partials, the reduced vector,
+// the stage-1 partials of the sums (pstride = the workgroup count, so that the region ends with the last partial), the sums, the
+// state and the record -- lies in one Banded allocation of the call's.
+template <typename T, typename R>
+int lr_pass_entry(size_t m, size_t n_, int k, const T* J, const T* twh, T* U, T* D, const T* dx, const T* dx_dot, const T* y, int count,
+                  const T* y_old, T* JJ, T* Jy, const R* spec, T absTolerance, T relTolerance, T* partials, T* reduced, T* sums,
+                  T* jy_inf, int info[6])
+{
+    if (!J || !U || !D || !dx || !dx_dot || !y || !y_old || !JJ || !Jy || !partials || !reduced || !sums || !jy_inf || !info) return -1;
+    if (m == 0 || n_ == 0 || n_ > (size_t)kLrMaxN || k < 0 || k >= kLrMax || count < 1 || count > kChainMax) return -1;
+    if (!device_available()) return -2;
+    const int n = (int)n_, len = lr_len(n), nblk = lr_blocks(m, query_num_cu());
+    Banded d;
+    const size_t rpart = d.take((size_t)nblk * len, sizeof(T)), rvec = d.take(len, sizeof(T)), rsp = d.take((size_t)count * nblk, sizeof(T)),
+                 rsum = d.take(count, sizeof(T)), rst = d.take(1, sizeof(LmState<T>)), rrec = d.take(1, sizeof(ChainRec<T>));
+    if (!d.alloc()) return -3;
+    const LrClass cls = lr_class_of<T>(n, J);
+    info[0] = cls.ncp; info[1] = cls.vec; info[2] = nblk; info[3] = -1; info[4] = d.bands(); info[5] = 0;
+    ChainRec<T> rec{};
+    if (spec) {
+        rec.lambda = spec->lambda; rec.new_dx_dot = spec->new_dx_dot; rec.predicted = spec->predicted; rec.trial_xnorm = spec->trial_xnorm;
+        rec.qp_status = spec->qp_status; rec.qp_iterations = spec->qp_iterations; rec.flags = spec->flags; rec.pad = spec->reserved;
+        if (!d.up(rrec, &rec)) return -3;
+    }
+    LrArgs<T> a{};
+    a.J = J; a.U = U; a.D = D; a.dx = dx; a.dx_dot = dx_dot; a.y = y; a.y_old = y_old;
+    a.partials = (T*)d.at(rpart); a.m = m; a.n = n; a.k = k;
+    a.spec_rec = spec ? (const ChainRec<T>*)d.at(rrec) : nullptr;
+    a.absTolerance = absTolerance; a.relTolerance = relTolerance;
+    const bool good = lr_sweep<T>(a, nblk, nullptr, twh) == hipSuccess     // twh != nullptr: J is the unscaled difference panel
+        && lr_reduce<T>((const T*)d.at(rpart), nblk, n, (T*)d.at(rvec), nullptr) == hipSuccess
+        && (spec || lr_finish<T>((const T*)d.at(rvec), D, dx, k, n, JJ, Jy, (LmState<T>*)d.at(rst), nullptr) == hipSuccess)
+        && lr_sumsq<T>(y, m, count, m, (T*)d.at(rsp), nblk, nblk, nullptr) == hipSuccess
+        && lr_sumsq_final<T>((const T*)d.at(rsp), nblk, nblk, count, (T*)d.at(rsum), nullptr) == hipSuccess;
+    if (!good) { (void)hipDeviceSynchronize(); return -4; }
+    if (!launches_done() || !d.fetch()) return -5;
+    info[3] = d.damaged();
+    // the state but for jy_inf, and the record: nobody writes them (info[5]: 1 the state, 2 the record, 3 both)
+    const size_t jlo = offsetof(LmState<T>, jy_inf), jhi = jlo + sizeof(T);
+    for (size_t i = 0; i < sizeof(LmState<T>); ++i)
+        if ((i < jlo || i >= jhi || spec) && d.image(rst)[i] != 0xFF) info[5] |= 1;
+    std::vector<unsigned char> want(sizeof rec, 0xFF);
+    if (spec) std::memcpy(want.data(), &rec, sizeof rec);
+    if (std::memcmp(d.image(rrec), want.data(), sizeof rec) != 0) info[5] |= 2;
+    d.down(rpart, partials); d.down(rvec, reduced); d.down(rsum, sums);
+    std::memcpy(jy_inf, d.image(rst) + jlo, sizeof(T));
+    return 0;
+}
+
+// mir_lsq_lr_flush_*: one lr_flush on device pointers of the caller's
+template <typename T>
+int lr_flush_entry(size_t m, size_t n, int k, T* J, const T* U, const T* D, int info[2])
+{
+    if (!J || !U || !D || !info || m == 0 || n == 0 || n > (size_t)kLrMaxN || k < 1 || k > kLrMax) return -1;
+    if (!device_available()) return -2;
+    const LrClass cls = lr_class_of<T>((int)n, J);
+    info[0] = cls.ncp; info[1] = cls.vec;
+    if (lr_flush<T>(J, U, D, k, m, (int)n, query_num_cu(), nullptr) != hipSuccess) { (void)hipDeviceSynchronize(); return -4; }
+    return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -5;
+}
 
 template <typename T> struct StateAbi;
 template <> struct StateAbi<double> { using type = mir_lsq_lm_state_d; using rec = mir_lsq_lm_solve_record_d; };

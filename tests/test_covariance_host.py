@@ -80,6 +80,52 @@ def test_argument_checks_answer_without_a_device():
     assert _raw(np.float64, [np.nan, 5.0], lo, up, settings=s) == -31 and _raw(np.float64, [0.0, 5.0], lo, up, settings=s) == -32
 
 
+def _raw_solve(dtype, x, l, u, settings=None, m=4):
+    """mir_optimize_least_squares_gpu_* with raw pointers; f is never called by the paths tested here"""
+    ct = C.c_double if dtype == np.float64 else C.c_float
+    ft = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(ct), C.POINTER(ct))
+    called = []
+    thunk = ft(lambda *a: called.append(1))
+    s = settings if settings is not None else M.LeastSquaresSettings(dtype)
+    xa, la, ua = (np.ascontiguousarray(v, dtype=dtype) for v in (x, l, u))
+    x0 = xa.copy()
+    fn = getattr(api.lib(), "mir_optimize_least_squares_gpu_" + ("d" if dtype == np.float64 else "s"))
+    r = fn(C.byref(s), m, xa.size, xa.ctypes.data, la.ctypes.data, ua.ctypes.data, None, None, C.cast(thunk, C.c_void_p),
+           None, None, None, None)
+    assert not called and r.iterations == 0 and r.fCalls == 0 and r.gCalls == 0    # nothing evaluated
+    assert np.array_equal(xa, x0, equal_nan=True)                                 # x untouched
+    return r.status
+
+
+def test_the_solve_and_the_covariance_step_share_one_validation():
+    """LS:930-943 is one function for both entry points: the same status for every invalid input, in the same order (the guess
+    before the bounds before the settings), answered before a device is asked for and before f is called."""
+    lo, up = [-1.0, -1.0], [1.0, 1.0]
+    good = [0.0, 0.0]
+    bad_set = (("minStepQuality", 1.0, -30), ("minStepQuality", -0.5, -30), ("goodStepQuality", 1.5, -29),
+               ("goodStepQuality", 0.05, -28), ("lambdaIncrease", 0.5, -27), ("lambdaDecrease", 2.0, -27))
+    for dt in (np.float64, np.float32):
+        def worst():
+            s = M.LeastSquaresSettings(dt)
+            s.minStepQuality = 1.0
+            return s
+        rows = [(x, lo, up, None, 4, -31) for x in ([np.nan, 0.0], [0.0, np.nan], [np.inf, 0.0], [0.0, -np.inf])]
+        rows += [(good, lo, up, None, 0, -31)]                           # m == 0
+        rows += [([-1.5, 0.0], lo, up, None, 4, -32), ([0.0, -2.0], lo, up, None, 4, -32)]     # x below l
+        rows += [([2.0, 0.0], lo, up, None, 4, -32), ([0.0, 1.5], lo, up, None, 4, -32)]       # x above u
+        rows += [(good, [np.nan, -1.0], up, None, 4, -32), (good, lo, [1.0, np.nan], None, 4, -32)]   # a NaN bound compares false
+        for field, val, code in bad_set:
+            s = M.LeastSquaresSettings(dt)
+            setattr(s, field, val)
+            rows.append((good, lo, up, s, 4, code))
+        # the order: the guess before the bounds before the settings
+        rows += [([np.nan, 5.0], lo, up, worst(), 4, -31), (good, lo, up, worst(), 0, -31), ([0.0, 5.0], lo, up, worst(), 4, -32),
+                 ([np.inf, 0.0], [3.0, 3.0], up, None, 4, -31), (good, lo, up, worst(), 4, -30)]
+        for x, l, u, s, m, code in rows:
+            assert _raw_solve(dt, x, l, u, settings=s, m=m) == code, (dt, x, l, u, m, code)
+            assert _raw(dt, x, l, u, settings=s, m=m) == code, (dt, x, l, u, m, code)
+
+
 def test_python_layer_raises_the_validation_status():
     def f(x, y):
         raise AssertionError("not evaluated")
