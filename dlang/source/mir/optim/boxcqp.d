@@ -61,6 +61,15 @@ extern(C) @system nothrow @nogc pure
     int mir_lsq_batched_box_qp16_s(scope const BoxQPSettings!float* settings, size_t count, size_t n, const(float)* P,
         const(float)* q, const(float)* l, const(float)* u, size_t bound_stride, float* x, int* status, int* iterations,
         uint flags, void* stream);
+
+    /// the same for n = 17 .. 64 in the dense layout (P count x n x n with row stride n, q / x count x n, l / u n values or
+    /// count x n with bound_stride 0 / n); enqueued on `stream`, no synchronisation. 0, -1 or -5.
+    int mir_lsq_batched_box_qp64_d(scope const BoxQPSettings!double* settings, size_t count, size_t n, const(double)* P,
+        const(double)* q, const(double)* l, const(double)* u, size_t bound_stride, double* x, int* status, int* iterations,
+        uint flags, void* stream);
+    int mir_lsq_batched_box_qp64_s(scope const BoxQPSettings!float* settings, size_t count, size_t n, const(float)* P,
+        const(float)* q, const(float)* l, const(float)* u, size_t bound_stride, float* x, int* status, int* iterations,
+        uint flags, void* stream);
 }
 
 /// flag of mir_lsq_batched_box_qp_*: x holds the unconstrained minimisers on entry

@@ -412,6 +412,21 @@ int mir_lsq_batched_box_qp16_d(const mir_box_qp_settings_d* settings, size_t cou
                                const double* l, const double* u, size_t bound_stride, double* x, int* status, int* iterations,
                                unsigned flags, void* stream);
 
+/* The same for orders n = 17 .. 64 (csrc/boxqp_wave.h: one problem a wavefront at n > 32, two at n <= 32; the matrices live
+ * in LDS and n is a run-time argument of the kernel), in the DENSE layout: P count x n x n values, problem p at P + n n p,
+ * row-major with row stride n, the LOWER triangle is read (what stands above it is never touched); q and x count x n; l and u
+ * n values shared by all problems (bound_stride = 0) or count x n (bound_stride = n). settings, status, iterations, flags and
+ * stream as above. Returns 0; -1 for bad arguments (a NULL pointer other than iterations, n outside 17 .. 64, bound_stride
+ * neither 0 nor n, count above 2^30); -5 when no device is usable or the launch failed. count == 0 returns 0, launches nothing
+ * and needs no device. What a problem returns does not depend on its position in the batch. mir_lsq_batched_box_qp16_* keeps
+ * rejecting n > 16: the layouts are separate entries. */
+int mir_lsq_batched_box_qp64_s(const mir_box_qp_settings_s* settings, size_t count, size_t n, const float* P, const float* q,
+                               const float* l, const float* u, size_t bound_stride, float* x, int* status, int* iterations,
+                               unsigned flags, void* stream);
+int mir_lsq_batched_box_qp64_d(const mir_box_qp_settings_d* settings, size_t count, size_t n, const double* P, const double* q,
+                               const double* l, const double* u, size_t bound_stride, double* x, int* status, int* iterations,
+                               unsigned flags, void* stream);
+
 /* Batched small fits, ONE WAVEFRONT PER PROBLEM (BASELINE cfg 5): `count` independent problems of the same shape
  * with a built-in residual model r_i = model(t_i; x) - data_i evaluated inside the kernel (no callback):
  *   MIR_LSQ_MODEL_EXP_DECAY   n = 3   p0 exp(-t p1) + p2
@@ -727,6 +742,15 @@ int mir_lsq_batched_posvx_d(size_t count, size_t n, const double* P, const doubl
  * synchronisation. Returns 0; -1 bad arguments; -2 no device; -5 a failed launch. */
 int mir_lsq_batched_posvx16_s(size_t count, size_t n, const float* P, const float* rhs, float* x, int* info, void* stream);
 int mir_lsq_batched_posvx16_d(size_t count, size_t n, const double* P, const double* rhs, double* x, int* info, void* stream);
+/* Unit-level access to the grid of mir_lsq_batched_box_qp64_*: the same call with a cap on the number of wavefronts launched
+ * (max_waves; 0 = the default cap, which is the public entry). With max_waves = 1 one wavefront solves every problem in
+ * sequence; the answers are those of any other grid, bit for bit. */
+int mir_lsq_batched_box_qp64_waves_s(const mir_box_qp_settings_s* settings, size_t count, size_t n, const float* P, const float* q,
+                                     const float* l, const float* u, size_t bound_stride, float* x, int* status, int* iterations,
+                                     unsigned flags, void* stream, unsigned max_waves);
+int mir_lsq_batched_box_qp64_waves_d(const mir_box_qp_settings_d* settings, size_t count, size_t n, const double* P, const double* q,
+                                     const double* l, const double* u, size_t bound_stride, double* x, int* status, int* iterations,
+                                     unsigned flags, void* stream, unsigned max_waves);
 
 /* Unit-level access to the hot kernels (parity tests and micro-benchmarks). All pointers are
  * DEVICE pointers; stream may be NULL (default stream; the call synchronises before returning).

@@ -31,7 +31,7 @@ __all__ = [
     "mir_least_squares_work_length", "mir_least_squares_iwork_length", "mir_box_qp_work_length",
     "mir_box_qp_iwork_length", "GpuOptions", "Stats", "lib", "workloads_lib", "device_count",
     "DeviceBuffer", "Stream", "jtj", "fd_jtj", "DEVICE_CALLBACKS", "TIME_KERNELS", "optimizeLeastSquaresBatched", "batchedPosvx", "predictBatched", "BATCHED_ANALYTIC_JACOBIAN", "BATCHED_NO_LADDER", "BATCHED_DEVICE_BOUNDS",
-    "solveBoxQPBatched", "BOX_QP_UNCONSTRAINED_SOLUTION",
+    "solveBoxQPBatched", "solveBoxQPBatchedWide", "BOX_QP_UNCONSTRAINED_SOLUTION",
     "MODEL_EXP_DECAY", "MODEL_EXP3_AFFINE", "MODEL_EXP_DECAY_PAD8", "MODEL16_EXP_HARM16", "MODEL16_GAUSS3_AFFINE", "batched16JtJ", "optimizeLeastSquaresBatched16", "ResultS", "Trace", "TraceRecord", "Spline", "FitSplineResult", "fitSpline",
     "fit_spline_residuals", "variant_lr_cap",
     "VARIANT_BROYDEN_REWRITE", "VARIANT_FD_SEPARATE_FILL", "VARIANT_NO_SPECULATION", "VARIANT_NO_NULL_SKIP",
@@ -394,6 +394,11 @@ def lib():
             fn.restype = C.c_int
             fn.argtypes = [C.c_void_p, sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_uint, C.c_void_p]
+        for name in ("box_qp64_s", "box_qp64_d", "box_qp64_waves_s", "box_qp64_waves_d"):
+            fn = getattr(L, "mir_lsq_batched_" + name)
+            fn.restype = C.c_int
+            fn.argtypes = [C.c_void_p, sz, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.c_uint, C.c_void_p] + ([C.c_uint] if "waves" in name else [])
         for suf in ("s", "d"):
             fn = getattr(L, "mir_lsq_batched_posvx16_" + suf)
             fn.restype = C.c_int
@@ -1412,6 +1417,71 @@ def solveBoxQPBatched(P, q, l, u, x=None, settings=None, dtype=np.float64, uncon
         raise RuntimeError(f"{name} failed: {rc}")
     st.synchronize()
     out = dst.download().copy(), bufs[4].download()[:, :n].copy(), dit.download().copy()
+    for b in bufs + [dst, dit]:
+        b.free()
+    return out
+
+
+BOX_QP_WIDE_ORDERS = (17, 64)         # mir_lsq_batched_box_qp64_*: the orders it takes
+
+
+def _box_qp_batched_pack_dense(P, q, l, u, x, dtype, unconstrainedSolution):
+    """The dense layout of mir_lsq_batched_box_qp64_* (n = 17 .. 64) from count x n x n / count x n arrays (host side, no
+    device), by the rules of _box_qp_batched_pack_w without the padding: returns (count, n, P count x n x n, q count x n, l, u
+    (n,) or count x n, bound_stride 0 or n, x count x n), C-contiguous arrays of `dtype`. Raises ValueError."""
+    suf = _batched_suffix(dtype)
+    dtype = np.float32 if suf == "s" else np.float64
+    P = np.ascontiguousarray(P, dtype=dtype)
+    if P.ndim != 3 or P.shape[1] != P.shape[2]:
+        raise ValueError(f"P: count x n x n, not {P.shape}")
+    count, n = P.shape[0], P.shape[1]
+    nmin, nmax = BOX_QP_WIDE_ORDERS
+    if not nmin <= n <= nmax:
+        raise ValueError(f"solveBoxQPBatchedWide: n = {n} is outside {nmin} .. {nmax}")
+    q = np.ascontiguousarray(q, dtype=dtype)
+    if q.shape != (count, n):
+        raise ValueError(f"q: {count} x {n}, not {q.shape}")
+    l, u = np.ascontiguousarray(l, dtype=dtype), np.ascontiguousarray(u, dtype=dtype)
+    if l.shape != u.shape or l.shape not in ((n,), (count, n)):
+        raise ValueError(f"l, u: both {n} values or both {count} x {n}, not {l.shape} and {u.shape}")
+    if x is not None:
+        xp = np.array(x, dtype=dtype, order="C")
+        if xp.shape != (count, n):
+            raise ValueError(f"x: {count} x {n}, not {xp.shape}")
+    elif unconstrainedSolution:
+        raise ValueError("unconstrainedSolution=True needs x, the unconstrained minimisers")
+    else:
+        xp = np.zeros((count, n), dtype=dtype)
+    return count, n, P, q, l, u, (0 if l.ndim == 1 else n), xp
+
+
+def solveBoxQPBatchedWide(P, q, l, u, x=None, settings=None, dtype=np.float64, unconstrainedSolution=False, max_waves=0):
+    """`count` solveBoxQP problems of order n = 17 .. 64 in one launch (mir_lsq_batched_box_qp64_d / _s: one problem a wavefront
+    at n > 32, two at n <= 32, the matrices in LDS): argmin_x(1/2 xPx + qx) : l <= x <= u for every problem. Arguments and
+    results as solveBoxQPBatched's: P count x n x n (lower triangles read), q count x n, l and u n values shared by all problems
+    or count x n; x (only with unconstrainedSolution=True): the unconstrained minimisers. max_waves: a cap on the wavefronts
+    launched (mir_lsq_batched_box_qp64_waves_*; 0: the default) -- the answers do not depend on it. Returns (status[count] of
+    BoxQPStatus values, x[count, n], iterations[count]). Raises ValueError for an order outside 17 .. 64."""
+    count, n, Pp, qp, lp, up, bound_stride, xp = _box_qp_batched_pack_dense(P, q, l, u, x, dtype, unconstrainedSolution)
+    dtype = Pp.dtype.type
+    suf = "s" if dtype == np.float32 else "d"
+    if settings is None:
+        settings = BoxQPSettings(dtype)
+    if count == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros((0, n), dtype=dtype), np.zeros(0, dtype=np.int32)
+    L = lib()
+    bufs = [DeviceBuffer(a) for a in (Pp, qp, lp, up, xp)]
+    dst = DeviceBuffer(nbytes=count * 4, dtype=np.int32, shape=(count,))
+    dit = DeviceBuffer(nbytes=count * 4, dtype=np.int32, shape=(count,))
+    st = Stream()
+    name = "mir_lsq_batched_box_qp64_waves_" + suf
+    rc = getattr(L, name)(C.addressof(settings), count, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bound_stride,
+                          bufs[4].ptr, dst.ptr, dit.ptr, BOX_QP_UNCONSTRAINED_SOLUTION if unconstrainedSolution else 0, st.handle,
+                          int(max_waves))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed: {rc}")
+    st.synchronize()
+    out = dst.download().copy(), bufs[4].download().copy(), dit.download().copy()
     for b in bufs + [dst, dit]:
         b.free()
     return out

@@ -23,9 +23,9 @@ WORKLOADS_LIB = os.path.join(LIBDIR, "libmir_optim_amd_workloads.so")
 
 SOLVER_UNITS = ["abi.hip", "workspace.hip", "solver_loop.hip", "solver_jacobian.hip", "launch_jtj.hip", "launch_broyden.hip",
                 "launch_solve_d.hip", "launch_solve_s.hip", "batched.hip", "batched_d.hip", "comm.hip", "unit_entries.hip", "covariance.hip",
-                "launch_spd_inverse.hip", "launch_boxqp.hip", "launch_boxqp16_s.hip", "launch_boxqp16_d.hip", "batched_bounded.hip",
-                "batched_bounded_d.hip", "batched16_d.hip", "batched16_ex_d.hip", "fit_spline.cpp", "fit_spline_gpu.hip",
-                "batched_predict.hip", "batched_predict_d.hip"]
+                "launch_spd_inverse.hip", "launch_boxqp.hip", "launch_boxqp16_s.hip", "launch_boxqp16_d.hip", "launch_boxqp64_s.hip",
+                "launch_boxqp64_d.hip", "batched_bounded.hip", "batched_bounded_d.hip", "batched16_d.hip", "batched16_ex_d.hip",
+                "fit_spline.cpp", "fit_spline_gpu.hip", "batched_predict.hip", "batched_predict_d.hip"]
 WORKLOAD_UNITS = ["workloads.hip", "workloads_gemm.hip", "workloads_resident.hip"]
 
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("MIR_OPTIM_AMD_CXXFLAGS", "").split()

@@ -1,14 +1,17 @@
 """Time of one batched BOXCQP launch (four problems a wave; --n 8: mir_lsq_batched_box_qp_s / _d, csrc/boxqp_rows.h; --n 16:
-mir_lsq_batched_box_qp16_s / _d, one matrix row per lane, csrc/boxqp_rows16.h) against the only way there was before it, a loop
-over the one-problem host-pointer entry mir_solve_box_qp_gpu_*.
+mir_lsq_batched_box_qp16_s / _d, one matrix row per lane, csrc/boxqp_rows16.h; --n 32 and --n 64: mir_lsq_batched_box_qp64_s /
+_d, two problems or one a wave with the matrices in LDS, csrc/boxqp_wave.h, dense layout) against the only way there was before
+it, a loop over the one-problem host-pointer entry mir_solve_box_qp_gpu_*.
 
-65 536 problems of order n = 8 or 16, P = A^T A / m + 0.05 I (A m x n standard normal, m = n + 4), q = 2 N(0, 1), bounds c -+ w
-with c ~ N(0, 1), w ~ U(0.5, 3): about half the variables end on a bound (the share is printed). float32 and float64.
+65 536 problems of order n = 8 or 16 (16 384 of order 32 or 64: A alone is 2.3 GB of host memory at 65 536 x 68 x 64),
+P = A^T A / m + 0.05 I (A m x n standard normal, m = n + 4), q = 2 N(0, 1), bounds c -+ w with c ~ N(0, 1), w ~ U(0.5, 3):
+about half the variables end on a bound (the share is printed). float32 and float64.
   * batched: device events around `reps` launches on one stream after a warm-up, the median per launch; operands resident.
   * loop: a host clock around a loop over the first 256 problems (each call allocates, copies in, launches, synchronises and
     copies out: that is the entry), per problem, extrapolated to the full count.
-Run from the repository root:  timeout 300 python scripts/probes/batched_boxqp.py --n {8,16} [--out FILE]
-(profiles/r10/batched_boxqp.txt and profiles/r11/batched_boxqp16.txt are the first records at n = 8 and n = 16)
+Run from the repository root:  timeout 300 python scripts/probes/batched_boxqp.py --n {8,16,32,64} [--out FILE]
+(profiles/r10/batched_boxqp.txt and profiles/r11/batched_boxqp16.txt are the first records at n = 8 and n = 16,
+profiles/r29/batched_boxqp_n32.txt and batched_boxqp_n64.txt at n = 32 and n = 64)
 """
 import argparse
 import ctypes as C
@@ -23,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import mir_optim_amd as M          # noqa: E402
 from mir_optim_amd import api      # noqa: E402
 
-COUNT, SAMPLE = 65536, 256
+COUNT, SAMPLE = 65536, 256            # main() takes 16 384 problems at n > 16
 
 
 def problems(N, dtype, seed=10):
@@ -36,8 +39,8 @@ def problems(N, dtype, seed=10):
 
 
 def batched_ms(N, dtype, P, q, l, u, reps=50):
-    W = 8 if N <= 8 else 16                                    # the layout's width: operands are padded to it
-    fn = getattr(api.lib(), "mir_lsq_batched_box_qp" + ("" if W == 8 else "16") + ("_s" if dtype == np.float32 else "_d"))
+    W = 8 if N <= 8 else 16 if N <= 16 else N                  # the layout's width: operands are padded to it (n > 16: dense)
+    fn = getattr(api.lib(), "mir_lsq_batched_box_qp" + ("" if W == 8 else "16" if W == 16 else "64") + ("_s" if dtype == np.float32 else "_d"))
     dev = torch.device("cuda")
     pad = lambda a, shape: torch.from_numpy(np.pad(a, [(0, 0)] + [(0, W - N)] * (a.ndim - 1))).to(dev).reshape(shape).contiguous()
     dP, dq, dl, du = pad(P, (COUNT, W * W)), pad(q, (COUNT, W)), pad(l, (COUNT, W)), pad(u, (COUNT, W))
@@ -75,11 +78,13 @@ def loop_ms_per_problem(dtype, P, q, l, u):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, choices=(8, 16), default=8)
-    ap.add_argument("--out", default=None, help="default: profiles/r12/batched_boxqp_n<N>.txt")
+    ap.add_argument("--n", type=int, choices=(8, 16, 32, 64), default=8)
+    ap.add_argument("--out", default=None, help="default: profiles/r12/batched_boxqp_n<N>.txt (n > 16: profiles/r29)")
     args = ap.parse_args()
     N = args.n
-    out = args.out or os.path.join("profiles", "r12", "batched_boxqp_n%d.txt" % N)
+    global COUNT
+    COUNT = 65536 if N <= 16 else 16384
+    out = args.out or os.path.join("profiles", "r12" if N <= 16 else "r29", "batched_boxqp_n%d.txt" % N)
     lines = [f"batched BOXCQP on {torch.cuda.get_device_name(0)}; {api.lib().mir_lsq_version().decode()}",
              f"{COUNT} problems, n = {N}; loop baseline on the first {SAMPLE}, extrapolated", ""]
     for dtype in (np.float32, np.float64):
